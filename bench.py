@@ -2,6 +2,7 @@
 """bench.py - ligand poses/s of the reverse-diffusion hot path on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--samples 40] [--flex] [--cfg cfg2|cfg1]
+                  [--dump-outputs DIR] [--full]
 
 One "step" = one denoising step over the batch of sample graphs of the 3dpf complex: graph construction + score-model
 forward (HIP) + SDE pose update.  Default workload = BASELINE.json configs[1]: 3dpf, 40 samples, full score model
@@ -20,9 +21,15 @@ collective on the data path is the all_gather of final ligand poses at the end o
                    (SURVEY section 8(e)): 5 samples per GPU at N = 8.
 
 Synthetic data: real 3dpf geometry + random categorical features / ESM block, random-init weights (no network for
-checkpoints).  Inputs are resident in HBM before the timed region.
+checkpoints), all seeded: the same arguments give the same inputs in every run.  Inputs are resident in HBM before the timed
+region.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step, config).  `--dump-outputs DIR` also writes what a caller of the timed path receives
+after its last timed step - the ligand poses (lig_pos, [samples, atoms, 3]; several ranks: gathered over all of them) and the
+pocket atom positions (atom_pos, rank 0's samples) - as DIR/<name>.npy in float32, for an output-for-output comparison of two builds.
+
+With `--full` the JSON line also carries (each costs runs of its own behind the timed region; the --no-* options drop parts)
   roofline      the dominant kernel (ddp_conv_rows16_kernel since round 6, ddp_conv_rows_kernel in round 5; matrix-core bound by its instruction mix).  `achieved` =
                 matrix-core instruction FLOPs of the kernel's own formulation without padding - the two fc products and (rows kernel) the
                 per-edge G contraction as fp16 hi/lo split products = three fp16 MFMA FLOPs per product FLOP, the rest fp32 - / mean
@@ -35,6 +42,7 @@ The JSON line also carries
                 other kernel sources than the ones loaded (source hash).
   cpu_baseline  the CPU oracle (reference-equivalent restatement, kind "port") on a bounded sample of the same workload
   other_workloads  BASELINE configs[2] (flexible side chains) and configs[0] (cfg1, 4 samples) measured in the same run.
+  weak_scaling  several ranks under --scaling auto: the weak run (40 samples per rank) beside the strong headline.
 """
 import argparse
 import functools
@@ -75,12 +83,18 @@ def parse_args(argv=None):
     ap.add_argument("--samples", type=int, default=40)
     ap.add_argument("--scaling", default="auto", choices=["auto", "weak", "strong"],
                     help="auto: one rank -> the 40-sample job; several ranks -> the STRONG split of the 40 samples is the headline "
-                         "(BASELINE configs[3]) and the weak run (40 samples per rank) is measured in the same invocation as a sub-record")
+                         "(BASELINE configs[3]) and, with --full, the weak run (40 samples per rank) is measured in the same invocation as a sub-record")
     ap.add_argument("--cfg", default="cfg2", choices=["cfg1", "cfg2", "small32"])
     ap.add_argument("--flex", action="store_true", help="flexible side chains (BASELINE configs[2])")
     ap.add_argument("--ways", type=int, default=1,
                     help="resident sample groups per GPU (sampler.PipelinedSampler); measured slower than one batch on MI355X "
                          "(DESIGN.md section 4.5), hence 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (instrumented and HBM passes, PMC fields), "
+                         "other_workloads, cpu_baseline, the weak-scaling sub-record of several ranks")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the poses of the last timed step (lig_pos, atom_pos) as DIR/<name>.npy, float32, at most 64 MB "
+                         "(a fixed seeded subset of the samples beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-hbm-pass", action="store_true",
                     help="skip the two extra steps that time the HBM-bound kernels (use under rocprofv3 so that its per-kernel "
@@ -88,7 +102,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the configs[2] / configs[0] sub-records")
     ap.add_argument("--launch-log", default=None,
                     help="write the per-launch (kernel, edges, useful FLOPs) list of every conv launch to this JSON file "
-                         "(tools/pmc_collect.py matches it with the PMC dispatches of the same run)")
+                         "(tools/pmc_collect.py matches it with the PMC dispatches of the same run); needs --full")
     ap.add_argument("--dry-run-ranks", action="store_true",
                     help="launcher test (no GPU needed): every rank prints its RANK / WORLD_SIZE / sample slice as one JSON line and "
                          "exits, rank DDP_BENCH_FAIL_RANK (if set) with code 3")
@@ -114,7 +128,10 @@ def parse_args(argv=None):
                     help="diagnostic: the serial launch order of the conv layers (model.overlap_direct_conv = False) for same-box A/B runs")
     ap.add_argument("--no-flex-sharing", action="store_true",
                     help="diagnostic: flexible side chains without the partial sharing of layers 0 / 1 (model.share_flex_layer0 = False)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.launch_log and not args.full:
+        ap.error("--launch-log lists the launches of the instrumented pass, which only --full runs")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------- rank launcher
@@ -354,9 +371,32 @@ def timed_job(model, complex_graph, n_total, sl, device, flex, steps, warmup, wa
     if hasattr(sampler, "check_overflow"):
         sampler.check_overflow()      # replayed steps never enter the model's Python forward: a truncated edge list is reported here
     info["edges_last_step"] = dict(getattr(sampler, "last_stats", None) or model.last_stats)     # (of THIS job: read before any other runs)
+    # what a caller of the path receives after the last timed step (Sampler.run's lig_pos, atom_pos); taken before on_timed,
+    # whose steps move the poses again
+    info["outputs"] = {"lig_pos": (gathered if gathered is not None else final_pos).clone(), "atom_pos": sampler.atom_pos.clone()}
     if on_timed is not None:
         on_timed(sampler, snap, schedule)
     return elapsed, sampler, final_pos.clone(), gathered, schedule, info
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays (name -> tensor with the samples on axis 0) -> out_dir/<name>.npy in float32.  Beyond DUMP_LIMIT_BYTES in all, every
+    array keeps the same fixed, seeded subset of the samples (so two builds compare the same rows)."""
+    import numpy as np
+    import torch
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    n = min(v.shape[0] for v in arrays.values())
+    total = sum(v.numel() * 4 for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, n * DUMP_LIMIT_BYTES // total)
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays = {k: v[idx] for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.numpy())
 
 
 def shard_hbm_plan(cfg, n_local):
@@ -472,7 +512,7 @@ def main(argv=None):
     sm.set_conv_profiler(None)
 
     def roofline_pass(sampler, snap, schedule):
-        if rank != 0 or args.no_roofline_pass or snap is None:
+        if rank != 0 or not args.full or args.no_roofline_pass or snap is None:
             return
         sampler.restore(snap)
         sampler.graph_enabled = False
@@ -506,8 +546,10 @@ def main(argv=None):
         elapsed = max(float(x.item()) for x in allt)
         assert gathered.shape[0] == n_total
     assert torch.isfinite(final_pos).all(), "non-finite poses"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, info["outputs"])
     weak = None
-    if world > 1 and args.scaling == "auto":     # the weak figure (40 samples per rank) in the same invocation
+    if args.full and world > 1 and args.scaling == "auto":     # the weak figure (40 samples per rank) in the same invocation
         nw = args.samples * world
         slw = shard_slice(rank, world, nw, None)
         elw, _, fpw, gw, _, infow = timed_job(model, complex_graph, nw, slw, device, args.flex, args.steps, args.warmup, sync=sync,
@@ -523,7 +565,7 @@ def main(argv=None):
 
     if rank == 0:
         workload_key = f"{args.cfg} samples={args.samples} flex={args.flex} ways={args.ways} scaling={scaling} n_gpus={world}"
-        pmc, pmc_src = load_pmc(workload_key)
+        pmc, pmc_src = load_pmc(workload_key) if args.full else ({}, None)
         poses = n_total * args.steps / 20.0
         if args.launch_log:
             prof._resolve()
@@ -638,8 +680,9 @@ def main(argv=None):
                            "hbm_plan_rank0": shard_hbm_plan(args.cfg, n_local),
                            "hip_graph_replay": info.get("hip_graph"), "rccl_ranks_seen": ranks_seen, "backend": backend,
                            "all_gather_ms": info.get("all_gather_ms"),
-                           "edges_last_step": info.get("edges_last_step")},
-                "roofline": roof}
+                           "edges_last_step": info.get("edges_last_step")}}
+        if args.full:
+            line["roofline"] = roof
         if weak is not None:
             line["weak_scaling"] = weak
         if roof is not None:
@@ -647,7 +690,7 @@ def main(argv=None):
                                 "launch by launch with HIP events on the launch stream); the timed region itself replays one captured "
                                 "hipGraph per step")
         default_workload = args.samples == 40 and args.cfg == "cfg2" and not args.flex and args.ways == 1
-        if world == 1 and default_workload and not args.no_other_workloads:
+        if args.full and world == 1 and default_workload and not args.no_other_workloads:
             # BASELINE configs[2] and configs[0] in the same driver-run line (short runs: 20 and 20 steps)
             others = {}
 
@@ -734,7 +777,7 @@ def main(argv=None):
                 "configs0_cfg1_4_samples": pick("configs[0]"),
                 "readme_small_model": pick("README small"),
                 "configs3_shard_5_of_40_samples": pick("configs[3] shard")}
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N=1 only (the other ranks must not wait for it)
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N=1 only (the other ranks must not wait for it)
             line["cpu_baseline"] = cpu_baseline(args, model, kw, complex_graph)
         print(json.dumps(line), flush=True)
     if dist is not None:

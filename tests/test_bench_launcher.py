@@ -72,3 +72,28 @@ def test_eight_ranks_bind_their_own_gpu_and_size_memory_per_shard():
     assert 4e9 < one["g_and_messages_bytes_largest_layer"] < 8e9
     weak = _lines(_run(["--gpus", "8", "--scaling", "weak"]).stdout)
     assert all(d["hbm_plan"] == one for d in weak) and [d["slice"] for d in weak] == [[40 * i, 40 * i + 40] for i in range(8)]
+
+
+def test_dump_outputs_are_float32_and_capped_by_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; beyond the size cap every array keeps the SAME seeded subset of the samples,
+    so two runs (two builds) compare the same rows.  --launch-log needs --full (only --full runs the instrumented pass)."""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    lig, atom = torch.randn(40, 37, 3, dtype=torch.float64), torch.randn(40, 1111, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"lig_pos": lig, "atom_pos": atom})
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("lig_pos", "atom_pos")}
+    assert all(v.dtype == np.float32 for v in a.values()) and a["atom_pos"].shape == (40, 1111, 3)
+    assert np.array_equal(a["lig_pos"], lig.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200 * 1024)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"lig_pos": lig, "atom_pos": atom})
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("lig_pos", "atom_pos")}
+    assert sum(v.nbytes for v in b.values()) <= 200 * 1024 and 1 <= b["lig_pos"].shape[0] == b["atom_pos"].shape[0] < 40
+    rows = [int(np.flatnonzero((a["atom_pos"] == r).all(axis=(1, 2)))[0]) for r in b["atom_pos"]]
+    assert rows == sorted(rows) and np.array_equal(b["lig_pos"], a["lig_pos"][rows])
+    assert all(np.array_equal(v, np.load(tmp_path / "c" / f"{k}.npy")) for k, v in b.items())
+    assert not bench.parse_args(["--steps", "5"]).full and bench.parse_args(["--full", "--launch-log", "x.json"]).launch_log == "x.json"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--launch-log", "x.json"])
