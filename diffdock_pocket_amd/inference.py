@@ -30,6 +30,7 @@ import torch
 
 from . import inputs as I
 from .diffusion import get_t_schedule
+from .evaluation import PoseEvaluator, PoseMetrics  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 
 
@@ -41,6 +42,7 @@ class ComplexResult:
     order: Optional[torch.Tensor] = None           # sample indices in ranked order
     original_center: Optional[torch.Tensor] = None
     skipped: Optional[str] = None                  # reason, if the row could not be processed
+    metrics: Optional["PoseMetrics"] = None        # run_csv(evaluate=True): evaluation.PoseMetrics against the input pose, ranked order
 
 
 def _none(v):
@@ -103,7 +105,7 @@ def build_row_graph(row: Dict, esm_embeddings=None, root: str = "", allow_zero_e
 def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_complex: int = 40, inference_steps: int = 20,
             esm_embeddings=None, root: str = "", seed: int = 0, rank: int = 0, world: int = 1, shard: str = "samples",
             dist=None, sampler_cfg: Optional[SamplerConfig] = None, graph_kwargs: Optional[Dict] = None,
-            allow_zero_esm: bool = False) -> List[ComplexResult]:
+            allow_zero_esm: bool = False, evaluate: bool = False) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -111,14 +113,20 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     Exception, like the reference's per-complex try / except, inference.py:282-287) is skipped on ALL ranks: with sample
     sharding the ranks agree on the outcome (one all_reduce of an ok flag per row) before anyone enters the sampling loop and
     its final all_gather, and once more after sampling and the confidence pass (a sampling-time failure is rank-local: every rank
-    holds different poses), so a rank-local failure cannot leave the others waiting in a collective."""
+    holds different poses), so a rank-local failure cannot leave the others waiting in a collective.
+
+    evaluate=True: every processed row also gets `metrics` (evaluation.PoseEvaluator: RMSD, centroid distance, contacts and clashes
+    against the input ligand pose - the csv's ligand file is then the known pose - in the ranked order of `ligand_pos`), computed
+    after the gather so that every rank holds the full set.  Rigid rows are scored against the row's full PDB (the reference's static
+    receptor), flexible rows against the graph's atom nodes at each sample's side-chain positions (+ the side-chain RMSD).  A failure
+    of the evaluation skips the row like any other per-row failure."""
     dev = torch.device(device)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root,
-                            seed, rank, world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm)
+                            seed, rank, world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate)
     return _run_csv(csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed,
-                    rank, world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm)
+                    rank, world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate)
 
 
 def _all_ok(dist, ok: bool, device) -> bool:
@@ -130,7 +138,7 @@ def _all_ok(dist, ok: bool, device) -> bool:
 
 
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
-             world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm) -> List[ComplexResult]:
+             world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if shard not in ("samples", "complexes"):
         raise ValueError(shard)
@@ -162,12 +170,14 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
         # Sampling can fail on ONE rank only (each rank holds other poses: a truncated ligand<-atom list - DdpError after the run's
         # final synchronisation -, DDP_ELIMIT, out of memory): like the reference (inference.py:282-287) the complex is then
         # skipped - on EVERY rank, agreed before anyone enters the gathers below
-        lig = conf = smp = None
+        lig = conf = smp = apos = None
         try:
             smp = Sampler(model, g, n, device, cfg, seed=seed + i, sample_slice=sl)
             smp.randomize()
             smp.run(schedule)
             lig = smp.lig_pos
+            if evaluate and flex:
+                apos = smp.atom_pos.clone()
             if confidence_model is not None:
                 conf, _ = smp.confidence(confidence_model)
         except Exception as e:      # noqa: BLE001
@@ -188,6 +198,8 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             lig = _gather_rows(dist, lig, sizes)
             if conf is not None:
                 conf = _gather_rows(dist, conf, sizes)
+            if apos is not None:
+                apos = _gather_rows(dist, apos, sizes)
         if conf is not None:      # reference inference.py:212-219: descending confidence (first column of a multi-output head)
             key = conf[:, 0] if conf.dim() == 2 else conf
             order = torch.argsort(key, descending=True)
@@ -197,7 +209,30 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
         res.ligand_pos = lig[order].cpu()
         res.confidence = conf[order].cpu() if conf is not None else None
         res.original_center = getattr(g, "original_center", None)
+        if evaluate:
+            metrics = None
+            try:
+                metrics = _evaluate_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order])
+            except Exception as e:      # noqa: BLE001
+                res.skipped = f"evaluation: {type(e).__name__}: {e}"
+            if split and not _all_ok(dist, metrics is not None, device):
+                res.skipped = res.skipped or "skipped: evaluation failed on another rank"
+            if res.skipped is not None:
+                res.ligand_pos = res.confidence = res.order = None
+                continue
+            res.metrics = metrics
     return out
+
+
+def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
+    """PoseMetrics of the ranked poses of one row (see run_csv), on the host."""
+    if flex:
+        ev = PoseEvaluator(g, device)
+    else:
+        with open(os.path.join(root, row["experimental_protein"])) as f:
+            rec = PoseEvaluator.full_receptor(f.read(), g.original_center)
+        ev = PoseEvaluator(g, device, receptor=rec)
+    return ev.evaluate(lig, apos).cpu()
 
 
 def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:

@@ -550,3 +550,56 @@ def clean_pair_maps(touched, recv, src, n_edges, e0, n_graphs, n0, rowmap, rows_
     lib = L.load()
     L.check(lib.ddp_clean_pair_maps(touched.data_ptr(), recv.data_ptr(), src.data_ptr(), ptr(rowptr), n_edges, e0, n_graphs, n0,
                                     rowmap.data_ptr(), rows_v.data_ptr(), stream()), "ddp_clean_pair_maps")
+
+
+# ------------------------------------------------------------------------------------------------ pose evaluation
+def _eval_arg(t, dtype, dev, what):
+    if t.device != dev or t.dtype != dtype or not t.is_contiguous():
+        raise L.DdpError(f"{what}: expected a contiguous {dtype} tensor on {dev}, got {t.dtype} on {t.device}")
+
+
+def pose_rmsd(pred, ref, perms, sel=None, rmsd=None, best=None):
+    """ddp_pose_rmsd: pred [S, rows, 3] fp32, ref [n_ref, 3] fp32, perms int32 atom-major [n, P], sel int32 [n] rows of pred (None:
+    rows 0 .. n-1).  Returns (rmsd [S] fp32, best [S] int32), the minimum over the P columns of perms (ties: the lowest column)."""
+    dev = pred.device
+    S, n, P = pred.shape[0], perms.shape[0], perms.shape[1]
+    for t, dt, w in ((pred, torch.float32, "pred"), (ref, torch.float32, "ref"), (perms, torch.int32, "perms")):
+        _eval_arg(t, dt, dev, f"pose_rmsd {w}")
+    if sel is not None:
+        _eval_arg(sel, torch.int32, dev, "pose_rmsd sel")
+        if sel.shape != (n,):
+            raise L.DdpError("pose_rmsd: sel must have one entry per perms row")
+    elif n > pred.shape[1]:
+        raise L.DdpError("pose_rmsd: more perms rows than pred rows")
+    if pred.dim() != 3 or pred.shape[2] != 3 or ref.dim() != 2 or ref.shape[1] != 3 or perms.dim() != 2:
+        raise L.DdpError("pose_rmsd: pred [S, rows, 3], ref [n_ref, 3], perms [n, P]")
+    rmsd = torch.empty(S, dtype=torch.float32, device=dev) if rmsd is None else rmsd
+    best = torch.empty(S, dtype=torch.int32, device=dev) if best is None else best
+    if S == 0:
+        return rmsd, best
+    L.check(L.load().ddp_pose_rmsd(pred.data_ptr(), S, pred.shape[1] * 3, _p(sel), n, ref.data_ptr(), ref.shape[0], perms.data_ptr(), P,
+                                   rmsd.data_ptr(), best.data_ptr(), stream()), "ddp_pose_rmsd")
+    return rmsd, best
+
+
+def pose_contacts(lig, lig_radii, rec, rec_radii, ref_centroid, overlap=0.4, out=None):
+    """ddp_pose_contacts: lig [S, n, 3], lig_radii [n], rec [m, 3] (one receptor for all samples) or [S, m, 3] (one per sample),
+    rec_radii [m] (< 0: minimum distance only), ref_centroid [3], all fp32.  Returns [S, 4]: clashes, min_cross, min_self, centroid."""
+    dev = lig.device
+    S, n = lig.shape[0], lig.shape[1]
+    for t, w in ((lig, "lig"), (lig_radii, "lig_radii"), (rec, "rec"), (rec_radii, "rec_radii"), (ref_centroid, "ref_centroid")):
+        _eval_arg(t, torch.float32, dev, f"pose_contacts {w}")
+    if lig.dim() != 3 or lig.shape[2] != 3 or rec.dim() not in (2, 3) or rec.shape[-1] != 3:
+        raise L.DdpError("pose_contacts: lig [S, n, 3], rec [m, 3] or [S, m, 3]")
+    m = rec.shape[-2]
+    if rec.dim() == 3 and rec.shape[0] != S:
+        raise L.DdpError("pose_contacts: a per-sample receptor needs one row block per sample")
+    if lig_radii.shape != (n,) or rec_radii.shape != (m,) or ref_centroid.numel() != 3:
+        raise L.DdpError("pose_contacts: radii / centroid shapes")
+    out = torch.empty(S, 4, dtype=torch.float32, device=dev) if out is None else out
+    if S == 0:
+        return out
+    L.check(L.load().ddp_pose_contacts(lig.data_ptr(), S, n, lig_radii.data_ptr(), rec.data_ptr(), m, 3 * m if rec.dim() == 3 else 0,
+                                       rec_radii.data_ptr(), float(overlap), ref_centroid.data_ptr(), out.data_ptr(), stream()),
+            "ddp_pose_contacts")
+    return out

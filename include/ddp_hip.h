@@ -681,6 +681,29 @@ typedef struct {
 } ddp_node_job_t;
 int ddp_node_linear(const ddp_node_job_t* jobs, int njobs, void* stream);
 
+/* ---- evaluation of sampled poses against a reference pose (csrc/ddp_eval.hip; host side diffdock_pocket_amd/evaluation.py).
+ * One workgroup per sample, no atomics: two launches give the same bits.  n_samples = 0: no-op. */
+#define DDP_EVAL_MAX_ATOMS 1024   /* atoms per sample staged in LDS (n and n_ref of ddp_pose_rmsd, n of ddp_pose_contacts) */
+
+/* ddp_pose_rmsd: rmsd[s] = min_p sqrt(sum_i |pred_s[sel[i]] - ref[perms[i * n_perms + p]]|^2 / n), best[s] = that p (ties: lowest p).
+ * Replaces spyrmsd's symmrmsd as called by get_symmetry_rmsd (utils/utils.py:116-130: no centring, no alignment, the minimum over
+ * the element + adjacency automorphisms; perms atom-major [n][n_perms]), the plain RMSD fallback (evaluate_files.py:150-154: n_perms
+ * = 1, identity) and the side-chain RMSD of flexible residues (evaluate_files.py:237: sel = the side-chain rows of atom_pos).
+ * pred: sample s is the pred_stride floats at pred + s * pred_stride, atom row a at [3a, 3a + 3); sel [n] (NULL: rows 0 .. n-1);
+ * ref [n_ref][3].  Squares are summed in fp64 in increasing i.  A sel row outside the sample's stride gives rmsd = NaN, best = -1;
+ * a permutation with an entry outside [0, n_ref) is not considered (none left: NaN, -1). */
+int ddp_pose_rmsd(const float* pred, int n_samples, int pred_stride, const int32_t* sel, int n, const float* ref, int n_ref,
+                  const int32_t* perms, int n_perms, float* rmsd, int32_t* best, void* stream);
+
+/* ddp_pose_contacts: per sample s, out[s][0..3] = [clash count (an exact integer), min ligand-receptor distance, min ligand-ligand
+ * distance over i != j, |centroid(lig_s) - ref_centroid|] (evaluate_files.py:251-256 and datasets/steric_clash.py:99-136: a pair
+ * clashes when d < r_i + r_j - 2 overlap).  lig [n_samples][n][3], lig_radii [n]; receptor sample s = rec + s * rec_stride, [m][3]
+ * (rec_stride 0: one receptor for all samples; n_a * 3: each sample's own atom_pos); rec_radii [m], a negative radius = the atom
+ * counts for the minimum distance and never for clashes (the reference's filter of receptor hydrogens); ref_centroid [3].  Empty
+ * sets (m = 0, n = 1) give +inf minima. */
+int ddp_pose_contacts(const float* lig, int n_samples, int n, const float* lig_radii, const float* rec, int m, int rec_stride,
+                      const float* rec_radii, float overlap, const float* ref_centroid, float* out, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
 /* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, csrc/ddp_internal.h, include/ddp_hip.h) the library was built from */
