@@ -805,14 +805,16 @@ int ddp_conv_rows16_launch(const ddp_conv_shape_t* shape, const ddp_conv_task_t*
     }
   }
   int tiles = 0;
+  const ddp_conv_task_t* ref = nullptr;     // the first non-empty task: the launch's gh_fmt / rows_bias_k
   for (int i = 0; i < ntasks; ++i) {
     const ddp_conv_task_t& T = tasks[i];
     if (T.n_edges <= 0) continue;
-    if (T.gh_fmt != tasks[0].gh_fmt || (unsigned)T.gh_fmt > 1u) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: the tasks of a launch carry one plane form of G (gh_fmt 0 or 1)");
+    if (!ref) ref = &T;
+    if (T.gh_fmt != ref->gh_fmt || (unsigned)T.gh_fmt > 1u) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: the tasks of a launch carry one plane form of G (gh_fmt 0 or 1)");
     if (T.rows_seg0 < 0 || T.rows_seg1 < 0 || T.rows_nts < 0 || (T.rows_seg1 > 0 && (T.rows_seg1 <= T.rows_seg0 || T.rows_nts < nct1)) ||
         (T.rows_nts > nts) || (T.rows_seg1 > 0 && !T.rows_bias_k))      // (a range's bias table is fc.0's: rows_bias_k)
       return ddp_fail(DDP_EINVAL, "ddp_conv_rows: task.rows_seg0 / rows_seg1 / rows_nts");
-    if (T.rows_bias_k != tasks[0].rows_bias_k || (unsigned)T.rows_bias_k > 1u || (T.rows_bias_k && (shape->hid & 15) == 0))
+    if (T.rows_bias_k != ref->rows_bias_k || (unsigned)T.rows_bias_k > 1u || (T.rows_bias_k && (shape->hid & 15) == 0))
       return ddp_fail(DDP_EINVAL, "ddp_conv_rows: rows_bias_k is 0 or 1 for all tasks of a launch and needs hid % 16 != 0");
     if (T.n_edges_dev) L.dev_counts = 1;
     L.tile_start[L.ntasks] = tiles;
@@ -832,14 +834,14 @@ int ddp_conv_rows16_launch(const ddp_conv_shape_t* shape, const ddp_conv_task_t*
   if (priv < NS * 1024) priv = NS * 1024;          // the lo plane of edge_attr_ during fc1
   priv = (priv + 127) / 128 * 128;
   RL.priv_bytes = priv;
-  RL.bias_tiles = tasks[0].rows_bias_k ? nct1 : nts;
+  RL.bias_tiles = ref->rows_bias_k ? nct1 : nts;
   RL.bias_bytes = (RL.bias_tiles * 128 + 127) / 128 * 128;
   size_t lds_bytes = (size_t)2 * (NS * 1024) + RL.bias_bytes + (size_t)R16_NW * priv;
   if (2 * lds_bytes > 160 * 1024) return ddp_fail(DDP_ELIMIT, "ddp_conv_rows: LDS budget of two workgroups per CU exceeded (too many vector features per block)");
   if ((size_t)ddp_shape_rows_min_lds > lds_bytes) lds_bytes = (size_t)ddp_shape_rows_min_lds;
   static int lds_have[6] = {0, 0, 0, 0, 0, 0};
   hipError_t err;
-  const int gf = tasks[0].gh_fmt;
+  const int gf = ref->gh_fmt;
   const bool direct = shape->g_cols[0] == 0 && shape->g_cols[1] == 0;
 #define R16_LAUNCH(SZ_, GF_, I_)                                                                                             \
   {                                                                                                                          \

@@ -78,6 +78,19 @@ def _i32(t):
     return t.to(torch.int32).contiguous()
 
 
+def direct_packs(convs, dev):
+    """The packs of the tasks of one launch of direct convs.  convs: [(TensorProductConvLayer, nsplit)].  The launch runs one kernel, so
+    the convs go through the row-stationary kernel together (nsplit segment-range packs each: packed_rows_direct) or, where one of them
+    cannot, all through ddp_conv_messages, unsplit (one packed() each)."""
+    packs = []
+    for conv, nsplit in convs:
+        pkr = conv.packed_rows_direct(dev, nsplit)
+        packs.append([] if pkr is None else (pkr if nsplit > 1 else [pkr]))
+    if all(pks and all(K.conv_path(pk).rows for pk in pks) for pks in packs):
+        return packs
+    return [[conv.packed(dev)] for conv, _ in convs]
+
+
 class _Fork:
     """Independent launches of one layer on side streams (fork / join with events; inside a captured step they become
     parallel branches of the hipGraph).  Used for SMALL batches only: a layer's direct-conv launch (receptor<-atom: one 64-edge
@@ -767,69 +780,44 @@ class ForwardEngine:
         F.exact = by_ptr
 
     # ================================================================================================ layers
+    def _conv_path(self, conv, dev) -> K.ConvPath:
+        """How factorised conv `conv` runs in this forward: launch.conv_path under the model's all-or-none verdict."""
+        return K.conv_path(conv.packed_g(dev), self.m.rows_all_or_none(dev))
+
     def _stage_a(self, l, convs, x, n_rows, rows=None, rows_cnt=None, dense_rows=None):
         """Stage A of the factorised convs of layer `l` that read the same source rows: ONE ddp_stage_a launch
         rows[(conv, slot)] = x[:, scalars(slot)] @ Wg[(conv, slot)] = [G | Gb | pad] for all of them (weight-stationary
         fp32-MFMA kernel, csrc/ddp_gemm.hip; bound by the HBM write of G).  convs: [(k, TensorProductConvLayer)].  With a row
         list only the listed rows of the [n_rows]-row G arrays are computed.  Returns {(k, slot): G rows}."""
         m = self.m
-        # (G leaves stage A in the layout the conv kernel of this layer reads: plane form for ddp_conv_rows, launch.rows_mode)
-        rows_k = all(K.rows_mode(conv.packed_g(x.device)) for _, conv in convs)
-        key = (l, tuple(k for k, _ in convs), rows_k)
-        ent = m._stage_a_stacks.get(key)
-        if ent is None or ent[0].device != x.device:
-            Ws, meta, ghs, lds, fmts = [], [], [], [], set()
-            for k, conv in convs:
-                pk = conv.packed_g(x.device)
-                for slot in (0, 1):
-                    if pk.wg[slot] is not None:
-                        Ws.append(pk.wgh[slot] if rows_k else pk.wg[slot])
-                        meta.append((k, slot, pk.g_in_off[slot]))
-                        if rows_k:
-                            ghs.append(pk.gh_groups[slot])
-                            lds.append(pk.gh_ld[slot])
-                            fmts.add(pk.gh_fmt)
-            assert len(fmts) <= 1 and len(set(lds)) <= 1, "the convs of one stage-A launch write G rows of one plane form and length"
-            gfmt = fmts.pop() if fmts else 0
-            Wst = torch.stack(Ws).contiguous()
-            # (the bf16x3 split of the weights - 1.5 x their size and three copy kernels - only when that option is on)
-            ent = (Wst, meta, (C.c_int32 * len(meta))(*[mm[2] for mm in meta]), P.split_bf16x3(Wst) if (m.stage_a_bf16x3 and not rows_k) else None,
-                   (P.split_h2(Wst, unified_scale=P.GH_SW) if rows_k else P.split_h2(Wst)) if (m.stage_a_h2 or rows_k) else None,
-                   torch.stack([P.gh_dest_table(ws, (convs[0][1].spec_g.hid + 7) // 8, Wst.shape[2], fmt=gfmt) for ws in ghs]).contiguous().to(x.device) if rows_k else None,
-                   (gfmt, lds[0] if lds else Wst.shape[2]))
-            m._stage_a_stacks[key] = ent
-        if m.stage_a_bf16x3 and ent[3] is None and not rows_k:
-            ent = m._stage_a_stacks[key] = ent[:3] + (P.split_bf16x3(ent[0]),) + ent[4:]
-        if m.stage_a_h2 and ent[4] is None:
-            ent = m._stage_a_stacks[key] = ent[:4] + (P.split_h2(ent[0], unified_scale=P.GH_SW) if rows_k else P.split_h2(ent[0]),) + ent[5:]
-        gh, (gfmt, g_ld) = ent[5], ent[6]
-        ent = ent[:5]
-        Wst, meta, offs, W3, Wh = ent
-        nb = len(meta)
-        if nb > L.DDP_MAX_GEMM_BATCH:
-            raise L.DdpError("more (conv, slot) pairs per source array than DDP_MAX_GEMM_BATCH")
-        Gall = torch.empty((nb, n_rows, g_ld), device=x.device, dtype=torch.float32)   # 128-byte aligned rows (plane form 1: 3 / 4 of the columns)
+        # (G leaves stage A in the layout the conv kernel of this layer reads: the path its conv tasks are built from)
+        paths = {self._conv_path(conv, x.device) for _, conv in convs}
+        if len(paths) != 1:
+            raise L.DdpError("the convs of one stage-A launch run through different conv paths")
+        path = paths.pop()
+        key = (l, tuple(k for k, _ in convs), path.rows)
+        st = m._stage_a_stacks.get(key)
+        if st is None or st.W.device != x.device:
+            st = m._stage_a_stacks[key] = K.stage_a_stack([(k, conv.packed_g(x.device)) for k, conv in convs], convs[0][1].spec_g.hid, path)
+        h2 = m.stage_a_h2 and K.CONV_H2 and not m.stage_a_bf16x3
+        st.prepare(m.stage_a_h2, m.stage_a_bf16x3)
+        Gall = torch.empty((len(st.meta), n_rows, st.ld), device=x.device, dtype=torch.float32)   # 128-byte aligned rows (plane form 1: 3 / 4 of the columns)
         prof = K.profiler(hbm=True)
         if prof is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
         n_list = n_rows if rows is None else int(rows.shape[0])
-        if gh is not None:
-            K.stage_a(x, n_list, offs, nb, Wst, Gall, rows=rows, rows_cnt=rows_cnt, out_rows=n_rows, Wh=Wh, gh=gh, gh_fmt=gfmt, ldo=g_ld)
-        else:
-            K.stage_a(x, n_list, offs, nb, Wst, Gall, rows=rows, rows_cnt=rows_cnt, out_rows=n_rows, W3=W3 if m.stage_a_bf16x3 else None,
-                      Wh=Wh if (m.stage_a_h2 and K.CONV_H2 and not m.stage_a_bf16x3) else None)
+        K.stage_a(x, n_list, st, Gall, rows=rows, rows_cnt=rows_cnt, out_rows=n_rows, h2=h2, x3=m.stage_a_bf16x3)
         if prof is not None:
             e1.record()
             # algorithmic bytes: the G rows written once + the scalar columns of x read once per product + the weights
-            row_bytes = 4.0 * nb * (g_ld + Wst.shape[1])
+            row_bytes = 4.0 * len(st.meta) * (st.ld + st.W.shape[1])
 
-            def nbytes(n_list=n_list, rows_cnt=rows_cnt, row_bytes=row_bytes, wn=Wst.numel()):
+            def nbytes(n_list=n_list, rows_cnt=rows_cnt, row_bytes=row_bytes, wn=st.W.numel()):
                 n = n_list if rows_cnt is None else min(n_list, int(rows_cnt.item()))
                 return row_bytes * n + 4.0 * wn
-            use_h2 = gh is not None or (m.stage_a_h2 and K.CONV_H2 and not m.stage_a_bf16x3)
-            prof.hbm.setdefault("ddp_stage_a_h2_kernel" if use_h2 else "ddp_stage_a_mfma_kernel", []).append((e0, e1, nbytes))
-        return {(k, slot): Gall[i] for i, (k, slot, _) in enumerate(meta)}
+            prof.hbm.setdefault("ddp_stage_a_h2_kernel" if (st.path.rows or h2) else "ddp_stage_a_mfma_kernel", []).append((e0, e1, nbytes))
+        return {(k, slot): Gall[i] for i, (k, slot, _) in enumerate(st.meta)}
 
     def _layers(self, S, F, dev, mark):
         """The conv layers (reference :271-324).  Per layer: stage A of the factorised convs, the 32-edge conv launch (all
@@ -948,38 +936,31 @@ class ForwardEngine:
                 P.keep += [P.g_d, P.g_v, P.x_clean]
 
         def direct_tasks(P):
-            """The direct convs (receptor<-atom: one edge per atom, nothing to factorise): no stage A."""
+            """The direct convs (receptor<-atom: one edge per atom, nothing to factorise): no stage A; one launch (direct_packs)."""
             l, spec = P.l, P.spec
-            tasks, nb_d = [], 0.0
+            direct = [(k, csr, x_src) for k, (csr, so_k, x_src) in P.per.items() if not (so_k is not None or (k == 3 and P.c1 is not None))]
+            live = [(k, csr, x_src) for k, csr, x_src in direct if csr.n_edges > 0]
+            # (model.direct_rows: through the row-stationary kernel - 128-edge workgroups stream the fc.3 tiles once per 128 edges)
+            # one conv as several tasks of segment ranges where its 128-edge workgroups would leave most of the chip empty (measured: 44
+            # workgroups of 340 tiles - the 5-sample shard - 0.36 -> 0.155 ms per launch as six ranges; 347 workgroups - 40 samples - gain
+            # nothing from two ranges, profiles/r06_direct_rows_ab.txt): ceil(256 / workgroups) ranges, at most direct_rows_max_split
             # (the launch holds at most DDP_MAX_TASKS tasks: several direct convs in it - factorize_min_degree = 0 - share them)
-            n_direct = sum(1 for k, (csr, so_k, x_src) in P.per.items() if not (so_k is not None or (k == 3 and P.c1 is not None)) and csr.n_edges > 0)
-            split_cap = max(1, L.DDP_MAX_TASKS // max(1, n_direct))
-            for k, (csr, so_k, x_src) in P.per.items():
-                if so_k is not None or (k == 3 and P.c1 is not None):
-                    continue
+            split_cap = max(1, L.DDP_MAX_TASKS // max(1, len(live)))
+            packs = direct_packs([(m.conv_layers[9 * l + k], max(1, min(m.direct_rows_max_split, split_cap, -(-256 // max(1, -(-csr.n_edges // 128))))))
+                                  for k, csr, _ in live], dev)
+            tasks, nb_d = [], 0.0
+            for k, csr, x_src in direct:
+                P.msgs[k] = (torch.empty((csr.n_edges, spec.d_out), device=dev), csr, m.conv_layers[9 * l + k].packed(dev))
+            for (k, csr, x_src), pks in zip(live, packs):
                 x_recv, _, ek = arr[k]
-                pkc = m.conv_layers[9 * l + k].packed(dev)
-                msg = torch.empty((csr.n_edges, spec.d_out), device=dev)
-                P.msgs[k] = (msg, csr, pkc)
-                if csr.n_edges == 0:
-                    continue
                 if prof_on:
                     nb_d += node_bytes(l, k)
                 segs = [(e[ek], csr.eid, ns, ns), (x_recv, csr.recv, ldx, ns), (x_src, csr.src, ldx, ns)]
-                # (model.direct_rows: through the row-stationary kernel - 128-edge workgroups stream the fc.3 tiles once per 128 edges)
-                # one conv as several tasks of segment ranges where its 128-edge workgroups would leave most of the chip empty (measured: 44
-                # workgroups of 340 tiles - the 5-sample shard - 0.36 -> 0.155 ms per launch as six ranges; 347 workgroups - 40 samples - gain
-                # nothing from two ranges, profiles/r06_direct_rows_ab.txt): ceil(256 / workgroups) ranges, at most direct_rows_max_split
-                nsplit = max(1, min(m.direct_rows_max_split, split_cap, -(-256 // max(1, -(-csr.n_edges // 128)))))
-                pkr = m.conv_layers[9 * l + k].packed_rows_direct(dev, nsplit) if nsplit > 1 else m.conv_layers[9 * l + k].packed_rows_direct(dev)
-                if pkr is not None and all(K.rows_mode(p_) for p_ in (pkr if nsplit > 1 else [pkr])):
-                    for i_, p_ in enumerate(pkr if nsplit > 1 else [pkr]):
-                        t_ = K.make_task(p_, x_src, ldx, csr, sh[ek], segs, msg, rows=True)
-                        if i_:
-                            t_._count = (0, None)      # (the profiler counts a conv's edges once)
-                        tasks.append(t_)
-                else:
-                    tasks.append(K.make_task(pkc, x_src, ldx, csr, sh[ek], segs, msg))
+                for i_, pk in enumerate(pks):
+                    t_ = K.make_task(pk, K.conv_path(pk), x_src, ldx, csr, sh[ek], segs, P.msgs[k][0])
+                    if i_:
+                        t_._count = (0, None)      # (the profiler counts a conv's edges once)
+                    tasks.append(t_)
             P.tasks, P.nb_d = tasks, nb_d
             return tasks
 
@@ -1002,15 +983,14 @@ class ForwardEngine:
                     # rows [E, E + e0): the messages of the complex's own edge list between clean atoms
                     msg = torch.empty((c1.E + c1.e0, spec.d_out), device=dev)
                     P.msgs[k] = (msg, csr, pkc, c1.rowmap)
-                    pkg = conv.packed_g(dev)
-                    rk = K.rows_mode(pkg)
+                    pkg, path = conv.packed_g(dev), self._conv_path(conv, dev)
                     sd_ = c1.so_d
                     if sd_.n_edges > 0:
                         segs = [(e_base, sd_.eid, ns, ns), (x_recv, sd_.recv, ldx, ns), (xa, sd_.src, ldx, ns)]
-                        tasks_g.append(K.make_task(pkg, xa, ldx, sd_, sh_k, segs, msg, g=[P.g_d.get((3, s_)) for s_ in (0, 1)], rows=rk))
+                        tasks_g.append(K.make_task(pkg, path, xa, ldx, sd_, sh_k, segs, msg, g=[P.g_d.get((3, s_)) for s_ in (0, 1)]))
                     sv = c1.so_v
                     segs = [(e_base, sv.eid, ns, ns), (P.x_clean, sv.recv, ldx, ns), (P.x_clean, sv.src, ldx, ns)]
-                    tasks_g.append(K.make_task(pkg, P.x_clean, ldx, sv, sh_k, segs, msg, g=[P.g_v.get((3, s_)) for s_ in (0, 1)], rows=rk))
+                    tasks_g.append(K.make_task(pkg, path, P.x_clean, ldx, sv, sh_k, segs, msg, g=[P.g_v.get((3, s_)) for s_ in (0, 1)]))
                     continue
                 msg = torch.empty((csr.n_edges, spec.d_out), device=dev)
                 P.msgs[k] = (msg, csr, pkc)
@@ -1019,8 +999,8 @@ class ForwardEngine:
                 if prof_on:
                     nb_g += node_bytes(l, k)
                 segs = [(e_base, so_k.eid, ns, ns), (x_recv, so_k.recv, ldx, ns), (x_src, so_k.src, ldx, ns)]
-                pkg = conv.packed_g(dev)
-                tasks_g.append(K.make_task(pkg, x_src, ldx, so_k, sh_k, segs, msg, g=[P.gmap.get((k, s_)) for s_ in (0, 1)], rows=K.rows_mode(pkg)))
+                tasks_g.append(K.make_task(conv.packed_g(dev), self._conv_path(conv, dev), x_src, ldx, so_k, sh_k, segs, msg,
+                                           g=[P.gmap.get((k, s_)) for s_ in (0, 1)]))
             P.tasks_g = getattr(P, "tasks_g", []) + tasks_g
             if tasks_g:
                 K.launch_convs(P.spec_g, tasks_g, flops_spec=spec, node_bytes=nb_g, tag=f"layer{l}")
@@ -1059,14 +1039,14 @@ class ForwardEngine:
                 side.run(1, lambda P=P: launch_direct(P))
             stage_a(P, "lar")
             def atom_g_bytes(Pn):
-                """Bytes of G that stage A writes for the atom-source rows of a layer (host-side capacities)."""
+                """Bytes of G in plane form that stage A writes for the atom-source rows of a layer (host-side capacities; 0 where the model's
+                factorised convs cannot run through the row-stationary kernel)."""
                 tot = 0
-                for (st_, _gid), (_x, rows_, convs_) in Pn.groups.items():
+                for (st_, _gid), (_x, rows_, convs_) in (Pn.groups.items() if m.rows_all_or_none(dev) else ()):
                     if st_ != "a":
                         continue
                     for _k, conv_ in convs_:
-                        pk_ = conv_.packed_g(dev)
-                        tot += rows_[3] * 4 * sum(ld_ for ld_ in (getattr(pk_, "gh_ld", None) or []) if ld_ is not None)
+                        tot += rows_[3] * 4 * sum(ld_ for ld_ in (conv_.packed_g(dev).gh_ld or []) if ld_ is not None)
                 return tot
             for l in range(L_):
                 nxt = plan(l + 1) if l + 1 < L_ else None
@@ -1220,7 +1200,7 @@ class ForwardEngine:
         pkc = m.final_conv.packed(dev)
         msg = torch.empty((Nl, fspec.d_out), device=dev)
         seg_idx = c_c.src if m.fixed_center_conv else c_c.recv
-        K.launch_convs(fspec, [K.make_task(pkc, xl, ldx, c_c, sh_c, [(e_c, c_c.eid, ns, ns), (xl, seg_idx, ldx, ns)], msg)], tag="head")
+        K.launch_convs(fspec, [K.make_task(pkc, K.conv_path(pkc), xl, ldx, c_c, sh_c, [(e_c, c_c.eid, ns, ns), (xl, seg_idx, ldx, ns)], msg)], tag="head")
         gp = torch.empty((B, fspec.d_out), device=dev)      # (every row is written: accumulate = False)
         K.launch_reduce(gp, fspec.d_out, B, fspec.d_out, [(msg, c_c, pkc)], accumulate=False)
         if m.debug_conv_outputs is not None:
@@ -1274,7 +1254,7 @@ class ForwardEngine:
         msg = torch.empty((E, spec.d_out), device=dev)
         segs = [(e_t, csr.eid, ns, ns), (x, csr.src, ldx, ns), (bond_attr, csr.recv, ns, ns)]
         if E > 0:
-            K.launch_convs(spec, [K.make_task(pkc, x, ldx, csr, tor_sh, segs, msg)], tag="head")
+            K.launch_convs(spec, [K.make_task(pkc, K.conv_path(pkc), x, ldx, csr, tor_sh, segs, msg)], tag="head")
         hsum = torch.empty((T, spec.d_out), device=dev)      # (every row is written: accumulate = False)
         K.launch_reduce(hsum, spec.d_out, T, spec.d_out, [(msg, csr, pkc)] if E > 0 else [], accumulate=False)
         if m.debug_conv_outputs is not None:

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 from torch import nn
@@ -238,15 +238,31 @@ def occupancy_shaping(rows_min_lds: int = 0, stage_a_pad: int = 0):
     L.check(L.load().ddp_set_occupancy_shaping(int(rows_min_lds), int(stage_a_pad)), "ddp_set_occupancy_shaping")
 
 
-def rows_mode(pk) -> bool:
-    """Does a factorised conv with these packed weights run through ddp_conv_rows?  (Decided where stage A is planned: it writes G in
-    the layout the conv kernel of the same layer reads.)"""
-    return bool(CONV_H2 and CONV_ROWS and getattr(pk, "wsh", None) is not None)
+class ConvPath(NamedTuple):
+    """How one conv task runs (conv_path): the kernel, the form of its fc products and, for ddp_conv_rows, the ddp_conv_task_t fields
+    that select the kernel's form (include/ddp_hip.h).  Every task of one launch_convs call shares `rows` and `rows_form`."""
+    rows: bool                  # ddp_conv_rows (else ddp_conv_messages); G then comes from stage A in plane form
+    h2: bool                    # the fc products as fp16 hi/lo split products (w1h / w2h), else the exact fp32 MFMA form
+    rows_form: int = 0          # operand images: 0 = v_mfma_f32_32x32x16_f16, 1 = v_mfma_f32_16x16x32_f16
+    gh_fmt: int = 0             # plane form of G (factorised convs)
+    rows_bias_k: int = 0        # the fc.3 bias in the padding k row (direct convs)
+    rows_seg: tuple = (0, 0)    # the output-segment range of a direct conv's task; (0, 0): all
+    rows_nts: int = 0           # stream tiles of that range
 
 
-def make_task(pk, x_src, ldx_src, view: EdgeView, sh, segs, msg, g=None, rows=False) -> L.ConvTask:
-    """segs: [(tensor, idx_int32[E], ld, ncols)], concatenated into edge_attr_ in this order.  rows: a task of ddp_conv_rows - `g` then
-    holds the G arrays in plane form (ddp_stage_a_gh)."""
+def conv_path(pk, rows_ok: bool = True) -> ConvPath:
+    """The one place that decides how a conv task built from the packed weights `pk` runs, from the switches as they are when it is
+    called: CONV_H2, CONV_ROWS and the caller's `rows_ok` (a model's all-or-none verdict, score_model.rows_all_or_none).  ddp_conv_rows
+    where the pack carries its weight stream, ddp_conv_messages otherwise.  Stage A writes G in the layout of the same record."""
+    h2 = CONV_H2 and pk.w1h is not None and pk.w2h is not None
+    if not (CONV_H2 and CONV_ROWS and rows_ok and pk.wsh is not None):
+        return ConvPath(False, h2)
+    return ConvPath(True, h2, pk.rows_form, pk.gh_fmt, pk.rows_bias_k, pk.rows_seg, pk.rows_nts)
+
+
+def make_task(pk, path: ConvPath, x_src, ldx_src, view: EdgeView, sh, segs, msg, g=None) -> L.ConvTask:
+    """segs: [(tensor, idx_int32[E], ld, ncols)], concatenated into edge_attr_ in this order.  path: conv_path of `pk`; for ddp_conv_rows
+    `g` holds the G arrays in plane form (ddp_stage_a_gh)."""
     t = L.ConvTask()
     t.x_src, t.ldx_src, t.n_edges = x_src.data_ptr(), ldx_src, view.n_edges
     t.src, t.eid, t.sh = view.src.data_ptr(), view.eid.data_ptr(), sh.data_ptr()
@@ -257,21 +273,16 @@ def make_task(pk, x_src, ldx_src, view: EdgeView, sh, segs, msg, g=None, rows=Fa
         else:
             t.seg_ptr[k], t.seg_idx[k], t.seg_ld[k], t.seg_n[k] = 0, 0, 0, 0
     t.w1p, t.b1p, t.w2p, t.b2p = pk.w1p.data_ptr(), pk.b1p.data_ptr(), pk.w2p.data_ptr(), pk.b2p.data_ptr()
-    # fp16 hi/lo operand planes of the same weights (None / CONV_H2 off: the exact fp32 MFMA form)
-    use_h2 = CONV_H2 and getattr(pk, "w1h", None) is not None and getattr(pk, "w2h", None) is not None
-    t.w1h, t.w2h = (pk.w1h.data_ptr(), pk.w2h.data_ptr()) if use_h2 else (0, 0)
-    t.h2_range_flag = _p(_RANGE_FLAG) if use_h2 else 0
+    t.w1h, t.w2h = (pk.w1h.data_ptr(), pk.w2h.data_ptr()) if path.h2 else (0, 0)
+    t.h2_range_flag = _p(_RANGE_FLAG) if path.h2 else 0
     t.msg = msg.data_ptr()
-    t.wsh, t.bsp = (pk.wsh.data_ptr(), pk.bsp.data_ptr()) if rows else (0, 0)
+    t.wsh, t.bsp = (pk.wsh.data_ptr(), pk.bsp.data_ptr()) if path.rows else (0, 0)
     for k in range(2):
         gk = g[k].data_ptr() if (g is not None and g[k] is not None) else 0
-        t.g[k], t.gh[k] = (0, gk) if rows else (gk, 0)
-    t.gh_fmt = int(getattr(pk, "gh_fmt", 0)) if rows else 0
-    t.rows_form = int(getattr(pk, "rows_form", 0)) if rows else 0
-    t.rows_bias_k = int(getattr(pk, "rows_bias_k", 0)) if rows else 0
-    t.rows_seg0, t.rows_seg1 = (int(v) for v in getattr(pk, "rows_seg", (0, 0))) if rows else (0, 0)
-    t.rows_nts = int(getattr(pk, "rows_nts", 0)) if rows else 0
-    t._rows = bool(rows)
+        t.g[k], t.gh[k] = (0, gk) if path.rows else (gk, 0)
+    t.gh_fmt, t.rows_form, t.rows_bias_k, t.rows_nts = path.gh_fmt, path.rows_form, path.rows_bias_k, path.rows_nts
+    t.rows_seg0, t.rows_seg1 = path.rows_seg
+    t._path = path
     t.pos = _p(view.pos)
     t.n_edges_dev = _p(view.cnt)
     t._count = (view.n_edges, view.cnt)      # (python-side only: for the profiler)
@@ -279,27 +290,29 @@ def make_task(pk, x_src, ldx_src, view: EdgeView, sh, segs, msg, g=None, rows=Fa
 
 
 def launch_convs(spec: P.ConvSpec, tasks: List[L.ConvTask], flops_spec: Optional[P.ConvSpec] = None, node_bytes: float = 0.0, tag=None):
-    """node_bytes: 4 (N_in D_in + N_out D_out) summed over the launch's conv calls; tag: position in the forward (both only used
-    by the profiler)."""
+    """One launch of the kernel the tasks' common path names (tasks that name different kernels are a caller's error).  node_bytes:
+    4 (N_in D_in + N_out D_out) summed over the launch's conv calls; tag: position in the forward (both only used by the profiler)."""
     lib = L.load()
     if not tasks:
         return
+    path = tasks[0]._path
+    if any((t._path.rows, t._path.rows_form) != (path.rows, path.rows_form) for t in tasks):
+        raise L.DdpError("launch_convs: the tasks of one launch run through different conv kernels")
     arr = (L.ConvTask * len(tasks))(*tasks)
     shape = spec.ctypes_shape()
     prof = _PROFILER
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rows = all(getattr(t, "_rows", False) for t in tasks)
-    if rows:
+    if path.rows:
         L.check(lib.ddp_conv_rows(C.byref(shape), arr, len(tasks), stream()), "ddp_conv_rows")
     else:
         L.check(lib.ddp_conv_messages(C.byref(shape), arr, len(tasks), stream()), "ddp_conv_messages")
     if prof is not None:
         e1.record()
-        h2 = P.h2_steps(spec) > 0 and all(t.w1h and t.w2h for t in tasks)
+        h2 = P.h2_steps(spec) > 0 and all(t._path.h2 for t in tasks)
         prof.record_conv(e0, e1, spec, flops_spec, [t._count for t in tasks], node_bytes, tag, h2,
-                         rows=(2 if all(t.rows_form == 1 for t in tasks) else 1) if rows else 0)
+                         rows=(2 if path.rows_form == 1 else 1) if path.rows else 0)
 
 
 def launch_reduce(x, ldx, n_nodes, d_out, sources, accumulate=True, n_rep=1, rep_stride=0):
@@ -405,31 +418,66 @@ def edge_featurize_jobs(calls):
     return outs
 
 
-def stage_a(x, n_rows, offs, nb, W, out, rows=None, rows_cnt=None, out_rows=None, W3=None, Wh=None, gh=None, gh_fmt=0, ldo=None):
-    """ddp_stage_a: out[b][row] = x[row, offs[b]:offs[b]+k] @ W[b] for the listed rows (all n_rows rows if rows is None).
-    Wh: the weights pre-split for the fp16 hi/lo form (packing.split_h2; ddp_stage_a_h2), W3: for the bf16x3 form
-    (packing.split_bf16x3); neither: exact fp32 MFMA.  gh = the destination table of the plane form (int32 device tensor
-    [nb, ncols / 8, 2], packing.gh_dest_table): the output leaves in the layout ddp_conv_rows reads (ddp_stage_a_gh; needs Wh)."""
+@dataclass
+class StageAStack:
+    """The stacked stage-A right-hand sides of factorised convs that read one source array: ONE launch computes every product
+    (stage_a_stack builds it, stage_a launches it) - G in the plane form ddp_conv_rows reads (path.rows) or as fp32 rows."""
+    W: torch.Tensor             # [nb, K, ncols] fp32
+    meta: list                  # per product: (key, G slot, first input column)
+    offs: object                # the first input columns as a ctypes int32 array
+    path: ConvPath              # of the convs: G leaves in its layout
+    gh: Optional[torch.Tensor]  # destination table of the plane form (packing.gh_dest_table), path.rows only
+    ld: int                     # floats per output row (plane form 1: 3 / 4 of the product's columns)
+    Wh: Optional[torch.Tensor] = None       # W split for the fp16 hi/lo form (packing.split_h2)
+    W3: Optional[torch.Tensor] = None       # W split for the bf16x3 form (packing.split_bf16x3)
+
+    def prepare(self, h2: bool, x3: bool) -> "StageAStack":
+        """Makes the split weights a launch with these options reads (once: the options may change between two forwards)."""
+        if (h2 or self.path.rows) and self.Wh is None:
+            self.Wh = P.split_h2(self.W, unified_scale=P.GH_SW) if self.path.rows else P.split_h2(self.W)
+        if x3 and not self.path.rows and self.W3 is None:
+            self.W3 = P.split_bf16x3(self.W)
+        return self
+
+
+def stage_a_stack(packs, hid: int, path: ConvPath) -> StageAStack:
+    """packs: [(key, packed weights)] of convs that read the same source rows and run by `path` (conv_path): their G arrays in the
+    layout the conv tasks read."""
+    Ws, meta, ghs, lds = [], [], [], set()
+    for key, pk in packs:
+        for slot in (0, 1):
+            if pk.wg[slot] is None:
+                continue
+            meta.append((key, slot, pk.g_in_off[slot]))
+            Ws.append(pk.wgh[slot] if path.rows else pk.wg[slot])
+            if path.rows:
+                ghs.append(pk.gh_groups[slot])
+                lds.add(pk.gh_ld[slot])
+    assert len(lds) <= 1, "the convs of one stage-A launch write G rows of one length"
+    W = torch.stack(Ws).contiguous()
+    gh = torch.stack([P.gh_dest_table(ws, (hid + 7) // 8, W.shape[2], fmt=path.gh_fmt) for ws in ghs]).contiguous().to(W.device) if path.rows else None
+    return StageAStack(W, meta, (C.c_int32 * len(meta))(*[mm[2] for mm in meta]), path, gh, lds.pop() if lds else W.shape[2])
+
+
+def stage_a(x, n_rows, st: StageAStack, out, rows=None, rows_cnt=None, out_rows=None, h2=False, x3=False):
+    """ddp_stage_a: out[b][row] = x[row, offs[b]:offs[b]+k] @ W[b] for the listed rows (all n_rows rows if rows is None) and every
+    product b of the stack.  st.path.rows: the output leaves in the layout ddp_conv_rows reads (ddp_stage_a_gh / _gh3); otherwise h2: the
+    fp16 hi/lo form (ddp_stage_a_h2), x3: the bf16x3 form, neither: exact fp32 MFMA.  (st.prepare(h2, x3) first.)"""
     lib = L.load()
-    n_in, ncols = W.shape[1], W.shape[2]
+    nb, n_in, ncols = st.W.shape
+    if nb > L.DDP_MAX_GEMM_BATCH:
+        raise L.DdpError("more (conv, slot) pairs per source array than DDP_MAX_GEMM_BATCH")
     if n_rows == 0:
         return
-    if gh is not None and gh_fmt == 1:     # plane form 1 (fp16 hi + continuation bytes): rows of `ldo` floats (packing.gh3_ld = 6 ncols / 8)
-        L.check(lib.ddp_stage_a_gh3(x.data_ptr(), x.stride(0), n_rows, ptr(rows), ptr(rows_cnt), out_rows if out_rows is not None else n_rows,
-                                    offs, nb, W.data_ptr(), ptr(Wh), n_in, ncols, out.data_ptr(), int(ldo), ptr(_RANGE_FLAG), gh.data_ptr(),
-                                    stream()), "ddp_stage_a_gh3")
-        return
-    if gh is not None:
-        L.check(lib.ddp_stage_a_gh(x.data_ptr(), x.stride(0), n_rows, ptr(rows), ptr(rows_cnt), out_rows if out_rows is not None else n_rows,
-                                   offs, nb, W.data_ptr(), ptr(Wh), n_in, ncols, out.data_ptr(), ncols, ptr(_RANGE_FLAG), gh.data_ptr(),
-                                   stream()), "ddp_stage_a_gh")
-        return
-    if Wh is not None:
-        L.check(lib.ddp_stage_a_h2(x.data_ptr(), x.stride(0), n_rows, ptr(rows), ptr(rows_cnt), out_rows if out_rows is not None else n_rows,
-                                   offs, nb, W.data_ptr(), ptr(Wh), n_in, ncols, out.data_ptr(), ncols, ptr(_RANGE_FLAG), stream()), "ddp_stage_a_h2")
-        return
-    L.check(lib.ddp_stage_a(x.data_ptr(), x.stride(0), n_rows, ptr(rows), ptr(rows_cnt), out_rows if out_rows is not None else n_rows,
-                            offs, nb, W.data_ptr(), ptr(W3), n_in, ncols, out.data_ptr(), ncols, stream()), "ddp_stage_a")
+    args = (x.data_ptr(), x.stride(0), n_rows, ptr(rows), ptr(rows_cnt), out_rows if out_rows is not None else n_rows, st.offs, nb,
+            st.W.data_ptr())
+    if st.path.rows:
+        fn, name = (lib.ddp_stage_a_gh3, "ddp_stage_a_gh3") if st.path.gh_fmt == 1 else (lib.ddp_stage_a_gh, "ddp_stage_a_gh")
+        L.check(fn(*args, ptr(st.Wh), n_in, ncols, out.data_ptr(), st.ld, ptr(_RANGE_FLAG), st.gh.data_ptr(), stream()), name)
+    elif h2:
+        L.check(lib.ddp_stage_a_h2(*args, ptr(st.Wh), n_in, ncols, out.data_ptr(), ncols, ptr(_RANGE_FLAG), stream()), "ddp_stage_a_h2")
+    else:
+        L.check(lib.ddp_stage_a(*args, ptr(st.W3 if x3 else None), n_in, ncols, out.data_ptr(), ncols, stream()), "ddp_stage_a")
 
 
 # ------------------------------------------------------------------------------------------------ list primitives

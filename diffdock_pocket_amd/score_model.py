@@ -21,7 +21,6 @@ schedules, affinity prediction, parallel > 1) raise NotImplementedError instead 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 from typing import Dict, List, Optional
@@ -145,13 +144,32 @@ def _mlp(n_in, n_hidden, n_out, dropout):
 
 
 class _PackedConv:
+    """A conv's weights in the kernels' layouts (TensorProductConvLayer.packed / packed_g / packed_rows_direct).  What a pack does not
+    carry keeps the defaults below: no fp16 hi/lo planes, no stage-A right-hand sides, no weight stream of ddp_conv_rows.  How a conv
+    runs is not the pack's to say: launch.conv_path decides that per forward."""
     __slots__ = ("w1p", "b1p", "w2p", "b2p", "bn_scale", "bn_shift", "wg", "bg", "g_in_off", "w1h", "w2h",
-                 "wsh", "bsp", "wgh", "gh_groups", "gh_ld", "gh_fmt", "rows_form", "rows_bias_k", "rows_seg", "rows_nts")     # (the last seven: ddp_conv_rows' weight stream and stage-A right-hand sides)
+                 "wsh", "bsp", "wgh", "gh_groups", "gh_ld", "gh_fmt", "rows_form", "rows_bias_k", "rows_seg", "rows_nts")     # (the last ten: ddp_conv_rows' weight stream and stage-A right-hand sides)
+
+    def __init__(self, **fields):
+        self.wg = self.bg = self.g_in_off = self.w1h = self.w2h = None
+        self.wsh = self.bsp = self.wgh = self.gh_groups = self.gh_ld = None
+        self.gh_fmt = self.rows_form = self.rows_bias_k = self.rows_nts = 0
+        self.rows_seg = (0, 0)
+        for k, v in fields.items():
+            setattr(self, k, v)
 
 
 G_PLANES3_DEFAULT = "1"      # model.g_planes3 unless DDP_G_PLANES3 says otherwise (round 6, late: the 19-bit form is the default)
 DIRECT_ROWS_DEFAULT = "1"    # model.direct_rows unless DDP_DIRECT_ROWS says otherwise (round 6, late)
 ROWS_MFMA16_DEFAULT = "1"    # model.rows_mfma16 unless DDP_ROWS_MFMA16 says otherwise (round 6: 15.5 against 16.1 ms per 40-sample step)
+
+
+def rows_defaults():
+    """(rows_mfma16, g_planes3, direct_rows): the row-stationary kernel's options that a model and a stand-alone layer start with
+    (DDP_ROWS_MFMA16 / DDP_G_PLANES3 / DDP_DIRECT_ROWS = 0 / 1 in the environment set them for every model built in the process)."""
+    env = os.environ.get
+    return (env("DDP_ROWS_MFMA16", ROWS_MFMA16_DEFAULT) == "1", env("DDP_G_PLANES3", G_PLANES3_DEFAULT) == "1",
+            env("DDP_DIRECT_ROWS", DIRECT_ROWS_DEFAULT) == "1")
 
 
 class TensorProductConvLayer(nn.Module):
@@ -171,22 +189,20 @@ class TensorProductConvLayer(nn.Module):
         self._packed_d = None           # (packed(), its copy with the direct conv's weight stream): packed_rows_direct
         # which forms of the row-stationary kernel a layer runs through: a model sets these on its layers (rows_mfma16, g_planes3,
         # direct_rows); a stand-alone layer takes the same defaults
-        self.rows_form = 1 if os.environ.get("DDP_ROWS_MFMA16", ROWS_MFMA16_DEFAULT) == "1" else 0
-        self.gh_fmt = 1 if os.environ.get("DDP_G_PLANES3", G_PLANES3_DEFAULT) == "1" else 0
-        self.direct_rows = os.environ.get("DDP_DIRECT_ROWS", DIRECT_ROWS_DEFAULT) == "1"
+        rows16, planes3, self.direct_rows = rows_defaults()
+        self.rows_form, self.gh_fmt = int(rows16), int(planes3)
 
     def packed_g(self, device) -> _PackedConv:
         """Weights for the factorised path: fc.3 tiles of the vector-input features only + the GEMM right-hand sides
         that turn source-node scalars into G / Gb (packing.factor_weights)."""
         if self._packed_g is None or self._packed_g.w1p.device != device:
             base = self.packed(device)
-            pk = _PackedConv()
-            pk.w1p, pk.b1p, pk.bn_scale, pk.bn_shift, pk.w1h = base.w1p, base.b1p, base.bn_scale, base.bn_shift, base.w1h
             w2p, b2p = P.pack_fc2(self.spec_g, self.fc[3].weight, self.fc[3].bias)
             if w2p.numel() == 0:
                 w2p, b2p = torch.zeros(64), torch.zeros(32)
-            pk.w2p, pk.b2p = w2p.to(device), b2p.to(device)
-            pk.w2h = None
+            # (gh_fmt: plane form of G, set by the model: g_planes3; rows_form: operand images of the rows kernel: rows_mfma16)
+            pk = _PackedConv(w1p=base.w1p, b1p=base.b1p, bn_scale=base.bn_scale, bn_shift=base.bn_shift, w1h=base.w1h,
+                             w2p=w2p.to(device), b2p=b2p.to(device), gh_fmt=self.gh_fmt, rows_form=self.rows_form)
             if P.h2_steps(self.spec_g) > 0:
                 w2h = P.pack_fc2_h2(self.spec_g, self.fc[3].weight)
                 pk.w2h = (w2h if w2h.numel() else torch.zeros(64, dtype=torch.float16)).to(device)
@@ -196,18 +212,17 @@ class TensorProductConvLayer(nn.Module):
             pk.g_in_off = offs
             # the 128-edge row-stationary kernel (ddp_conv_rows; size classes ns = 60 / 32): the fc.0 / fc.3 tiles as one stream in the
             # kernel's k order, and stage-A right-hand sides whose product ddp_stage_a_gh writes as fp16 hi/lo planes
-            pk.wsh = pk.bsp = pk.wgh = pk.gh_groups = pk.gh_ld = None
-            pk.rows_bias_k, pk.rows_seg, pk.rows_nts = 0, (0, 0), 0
-            pk.gh_fmt = int(getattr(self, "gh_fmt", 0))     # plane form of G (ddp_conv_task_t::gh_fmt; set by the model: g_planes3)
-            pk.rows_form = int(getattr(self, "rows_form", 0))   # operand images of the rows kernel (ddp_conv_task_t::rows_form: rows_mfma16)
             if P.rows_supported(self.spec_g):
                 try:
                     wsh, bsp = P.rows_stream(self.spec_g, self.fc[0].weight, self.fc[0].bias, self.fc[3].weight, self.fc[3].bias, form=pk.rows_form)
+                    wgh, _, widths = P.factor_weights_gh(self.spec_g, self.fc[3].weight, self.fc[3].bias, fmt=pk.gh_fmt, form=pk.rows_form)
+                    for w in wgh:       # (stage A's planes hold G and, in the Gb columns, the fc.3 bias: the check split_h2 makes there)
+                        if w is not None:
+                            P.split_h2(w.unsqueeze(0), unified_scale=P.GH_SW)
                 except NotImplementedError:
-                    wsh = None      # a weight beyond the unified planes' range (|w| > 255): this conv keeps the 32-edge kernel
+                    wsh = None      # a weight beyond the unified planes' range (|w| > 255), or a bias beyond stage A's: the 32-edge kernel
                 if wsh is not None:
                     pk.wsh, pk.bsp = wsh.to(device), bsp.to(device)
-                    wgh, _, widths = P.factor_weights_gh(self.spec_g, self.fc[3].weight, self.fc[3].bias, fmt=pk.gh_fmt, form=pk.rows_form)
                     pk.wgh = [w.to(device) if w is not None else None for w in wgh]
                     pk.gh_groups = widths          # (per slot: the padded widths of the G array's column parts)
                     # floats per node of the G array stage A writes (plane form 1: shorter than the product's columns)
@@ -216,38 +231,20 @@ class TensorProductConvLayer(nn.Module):
             self._packed_g = pk
         return self._packed_g
 
-    def node_tensors(self, pk: _PackedConv, x_src: torch.Tensor, rows: bool = False):
-        """Stage A of the factorised conv: per-source-node rows [G | Gb | pad] = x_scalar @ Wg (ddp_stage_a); rows: in the plane
-        form ddp_conv_rows reads (ddp_stage_a_gh)."""
-        lib = L.load()
-        g = [None, None]
+    def node_tensors(self, pk: _PackedConv, x_src: torch.Tensor, path: K.ConvPath):
+        """Stage A of the factorised conv alone (a group of one, launch.stage_a_stack): per-source-node rows [G | Gb | pad] = x_scalar @ Wg
+        in the layout of `path` - the plane form ddp_conv_rows reads, or exact fp32 rows."""
         N = x_src.shape[0]
-        if rows:
-            for slot in (0, 1):
-                if pk.wgh[slot] is None:
-                    continue
-                w = pk.wgh[slot]
-                wh = P.split_h2(w.unsqueeze(0), unified_scale=P.GH_SW)
-                g[slot] = torch.empty((N, pk.gh_ld[slot]), device=x_src.device, dtype=torch.float32)
-                offs = (C.c_int32 * 1)(pk.g_in_off[slot])
-                dest = P.gh_dest_table(pk.gh_groups[slot], (self.spec_g.hid + 7) // 8, w.shape[1], fmt=pk.gh_fmt).to(x_src.device)
-                fn = lib.ddp_stage_a_gh3 if pk.gh_fmt == 1 else lib.ddp_stage_a_gh
-                L.check(fn(x_src.data_ptr(), x_src.shape[1], N, None, None, N, offs, 1, w.data_ptr(), wh.data_ptr(), w.shape[0],
-                           w.shape[1], g[slot].data_ptr(), pk.gh_ld[slot], None, dest.data_ptr(), _stream()), "ddp_stage_a_gh")
-            return g
-        for slot in (0, 1):
-            if pk.wg[slot] is None:
-                continue
-            w = pk.wg[slot]
-            g[slot] = torch.empty((N, w.shape[1]), device=x_src.device, dtype=torch.float32)
-            offs = (C.c_int32 * 1)(pk.g_in_off[slot])
-            L.check(lib.ddp_stage_a(x_src.data_ptr(), x_src.shape[1], N, None, None, N, offs, 1, w.data_ptr(), None, w.shape[0], w.shape[1],
-                                    g[slot].data_ptr(), w.shape[1], _stream()), "ddp_stage_a")
+        st = K.stage_a_stack([(0, pk)], self.spec_g.hid, path).prepare(h2=False, x3=False)
+        out = torch.empty((len(st.meta), N, st.ld), device=x_src.device, dtype=torch.float32)
+        K.stage_a(x_src, N, st, out)
+        g = [None, None]
+        for i, (_, slot, _) in enumerate(st.meta):
+            g[slot] = out[i]
         return g
 
     def packed(self, device) -> _PackedConv:
         if self._packed is None or self._packed.w1p.device != device:
-            pk = _PackedConv()
             w1p, b1p = P.pack_fc1(self.spec, self.fc[0].weight, self.fc[0].bias)
             w2p, b2p = P.pack_fc2(self.spec, self.fc[3].weight, self.fc[3].bias)
             if self.batch_norm is not None:
@@ -255,15 +252,12 @@ class TensorProductConvLayer(nn.Module):
                 sc, sh = P.bn_affine(self.out_blocks, bn.running_mean.cpu(), bn.running_var.cpu(), bn.weight.cpu(), bn.bias.cpu())
             else:
                 sc, sh = torch.ones(self.spec.d_out), torch.zeros(self.spec.d_out)
-            pk.w1p, pk.b1p, pk.w2p, pk.b2p = (t.to(device) for t in (w1p, b1p, w2p, b2p))
-            pk.bn_scale, pk.bn_shift = sc.to(device), sh.to(device)
+            pk = _PackedConv(w1p=w1p.to(device), b1p=b1p.to(device), w2p=w2p.to(device), b2p=b2p.to(device),
+                             bn_scale=sc.to(device), bn_shift=sh.to(device))
             # the same weights as fp16 hi/lo operand planes: the fc products then run on the fp16 matrix cores (ddp_conv.hip, h2 form)
-            pk.w1h = pk.w2h = None
             if P.h2_steps(self.spec) > 0:
                 pk.w1h = P.pack_fc1_h2(self.spec, self.fc[0].weight).to(device)
                 pk.w2h = P.pack_fc2_h2(self.spec, self.fc[3].weight).to(device)
-            pk.wsh = pk.bsp = pk.wgh = pk.gh_groups = pk.gh_ld = None
-            pk.gh_fmt, pk.rows_form, pk.rows_bias_k, pk.rows_seg, pk.rows_nts = 0, 0, 0, (0, 0), 0
             self._packed = pk
             self._packed_d = None
         return self._packed
@@ -276,10 +270,9 @@ class TensorProductConvLayer(nn.Module):
         the one pack.  None where the option is off, the shape is not one of the kernel's, or a weight / bias lies beyond the unified planes'
         range (ddp_conv_messages then)."""
         base = self.packed(device)
-        if not (bool(getattr(self, "direct_rows", False)) and int(getattr(self, "rows_form", 0)) == 1 and not self.spec.factorized
-                and P.rows_supported(self.spec)):
+        if not (self.direct_rows and self.rows_form == 1 and not self.spec.factorized and P.rows_supported(self.spec)):
             return None
-        if getattr(self, "_packed_d", None) is None or self._packed_d[0] is not base:
+        if self._packed_d is None or self._packed_d[0] is not base:
             self._packed_d = (base, {})
         cache = self._packed_d[1]
         ranges = P.rows_split_segments(self.spec, nsplit) if nsplit > 1 else [None]
@@ -287,12 +280,10 @@ class TensorProductConvLayer(nn.Module):
         if key not in cache:
             pks = []
             for rg in ranges:
-                pk = _PackedConv()
-                for name in ("w1p", "b1p", "w2p", "b2p", "bn_scale", "bn_shift", "w1h", "w2h"):
-                    setattr(pk, name, getattr(base, name))
-                pk.wsh = pk.bsp = pk.wgh = pk.gh_groups = pk.gh_ld = None
-                pk.gh_fmt, pk.rows_form, pk.rows_bias_k = 0, 1, 1
-                pk.rows_seg, pk.rows_nts = ((rg[0], rg[1]), self.spec.nct1 + rg[2]) if rg is not None else ((0, 0), 0)
+                pk = _PackedConv(**{name: getattr(base, name) for name in ("w1p", "b1p", "w2p", "b2p", "bn_scale", "bn_shift", "w1h", "w2h")},
+                                 rows_form=1, rows_bias_k=1)
+                if rg is not None:
+                    pk.rows_seg, pk.rows_nts = (rg[0], rg[1]), self.spec.nct1 + rg[2]
                 try:
                     wsh, bsp = P.rows_stream(self.spec, self.fc[0].weight, self.fc[0].bias, self.fc[3].weight, self.fc[3].bias, form=1, bias_in_k=True,
                                              seg_range=None if rg is None else (rg[0], rg[1]))
@@ -326,25 +317,21 @@ class TensorProductConvLayer(nn.Module):
         if factorized:
             if self.spec_g is None:
                 raise NotImplementedError("this conv has no factorised variant")
-            pk = self.packed_g(dev)
-            so = G.source_order(csr, x.shape[0])
-            rows = K.rows_mode(pk) and ea.shape[1] % 12 == 0
-            g = self.node_tensors(pk, x, rows=rows)
-            if rows:     # (ddp_conv_rows gathers edge_attr_ as three segments of ns columns: here three column ranges of one array)
-                w3 = ea.shape[1] // 3
-                segs = [(ea[:, i * w3:], so.eid, ea.shape[1], w3) for i in range(3)]
-            else:
-                segs = [(ea, so.eid, ea.shape[1], ea.shape[1])]
-            task = _make_task(pk, x, x.shape[1], so, sh, segs, msg, g=g, rows=rows)
-            _launch_convs(self.spec_g, [task], flops_spec=self.spec)
+            pk, view = self.packed_g(dev), G.source_order(csr, x.shape[0])
+            path = K.conv_path(pk, rows_ok=ea.shape[1] % 12 == 0)
+            g = self.node_tensors(pk, x, path)
         else:
-            pkr = self.packed_rows_direct(dev) if ea.shape[1] % 12 == 0 else None      # (the row-stationary kernel's direct form: direct_rows)
-            if pkr is not None and K.rows_mode(pkr):
-                w3 = ea.shape[1] // 3
-                task = _make_task(pkr, x, x.shape[1], csr, sh, [(ea[:, i * w3:], csr.eid, ea.shape[1], w3) for i in range(3)], msg, rows=True)
-            else:
-                task = _make_task(self.packed(dev), x, x.shape[1], csr, sh, [(ea, csr.eid, ea.shape[1], ea.shape[1])], msg)
-            _launch_convs(self.spec, [task])
+            pk, view, g = self.packed_rows_direct(dev) if ea.shape[1] % 12 == 0 else None, csr, None    # (the rows kernel's direct form: direct_rows)
+            if pk is None or not K.conv_path(pk).rows:
+                pk = self.packed(dev)
+            path = K.conv_path(pk)
+        if path.rows:       # (ddp_conv_rows gathers edge_attr_ as three segments of ns columns: here three column ranges of one array)
+            w3 = ea.shape[1] // 3
+            segs = [(ea[:, i * w3:], view.eid, ea.shape[1], w3) for i in range(3)]
+        else:
+            segs = [(ea, view.eid, ea.shape[1], ea.shape[1])]
+        task = _make_task(pk, path, x, x.shape[1], view, sh, segs, msg, g=g)
+        _launch_convs(self.spec_g if factorized else self.spec, [task], flops_spec=self.spec if factorized else None)
         out = torch.zeros((n_out, self.spec.d_out), device=dev, dtype=torch.float32)
         _launch_reduce(out, self.spec.d_out, n_out, self.spec.d_out, [(msg, csr, self.packed(dev))], accumulate=False)
         return out
@@ -606,14 +593,12 @@ class TensorProductScoreModel(nn.Module):
             self._torus_table = torch.from_numpy(z["torus_score_norm"]).float()
         self._edge_packs: Dict[str, _EdgeMLPPack] = {}
         self.last_stats: Dict[str, float] = {}
-        # plane form of the factorised convs' G (property g_planes3); DDP_G_PLANES3 = 0 / 1 in the environment sets the default of every model
-        # built in the process (the parity suites under the other form: profiles/r06_g3byte_parity.txt)
-        self.rows_mfma16 = os.environ.get("DDP_ROWS_MFMA16", ROWS_MFMA16_DEFAULT) == "1"
-        self.direct_rows = os.environ.get("DDP_DIRECT_ROWS", DIRECT_ROWS_DEFAULT) == "1"
+        # the row-stationary kernel's options (properties below; the environment's defaults: rows_defaults - the parity suites under the
+        # other plane form: profiles/r06_g3byte_parity.txt)
+        self.rows_mfma16, self.g_planes3, self.direct_rows = rows_defaults()
         # a direct conv through the rows kernel as up to this many tasks of segment ranges where its 128-edge workgroups would not fill the chip
-        # (engine.direct_tasks: ceil(512 / workgroups), at most this; 1 = never split)
+        # (engine.direct_tasks: ceil(256 / workgroups), at most this; 1 = never split)
         self.direct_rows_max_split = int(os.environ.get("DDP_DIRECT_SPLIT", "6"))
-        self.g_planes3 = os.environ.get("DDP_G_PLANES3", G_PLANES3_DEFAULT) == "1"
 
     # ---- checkpoint compatibility -------------------------------------------------------------
     _IGNORED_PREFIXES = ("final_tp_tor.", "final_tp_sc_tor.", "tor_bond_conv.tp.", "sc_tor_bond_conv.tp.")
@@ -776,16 +761,7 @@ class TensorProductScoreModel(nn.Module):
 
     @g_planes3.setter
     def g_planes3(self, value):
-        value = bool(value)
-        if value != self.g_planes3:
-            self.__dict__["_g_planes3"] = value
-            self._stage_a_stacks = {}
-            for m_ in self.modules():
-                if isinstance(m_, TensorProductConvLayer):
-                    m_.gh_fmt = 1 if value else 0
-                    m_._packed_g = None
-            self.__dict__["_rows_checked_epoch"] = None
-            self.__dict__["_packed_epoch"] = self.__dict__.get("_packed_epoch", 0) + 1
+        self._set_rows_option("_g_planes3", bool(value), gh_fmt=int(bool(value)))
 
     @property
     def rows_mfma16(self):
@@ -797,17 +773,7 @@ class TensorProductScoreModel(nn.Module):
 
     @rows_mfma16.setter
     def rows_mfma16(self, value):
-        value = bool(value)
-        if value != self.rows_mfma16:
-            self.__dict__["_rows_mfma16"] = value
-            self._stage_a_stacks = {}
-            for m_ in self.modules():
-                if isinstance(m_, TensorProductConvLayer):
-                    m_.rows_form = 1 if value else 0
-                    m_._packed_g = None
-                    m_._packed = None
-            self.__dict__["_rows_checked_epoch"] = None
-            self.__dict__["_packed_epoch"] = self.__dict__.get("_packed_epoch", 0) + 1
+        self._set_rows_option("_rows_mfma16", bool(value), rows_form=int(bool(value)))
 
     @property
     def direct_rows(self):
@@ -819,34 +785,35 @@ class TensorProductScoreModel(nn.Module):
 
     @direct_rows.setter
     def direct_rows(self, value):
-        value = bool(value)
-        if value != self.direct_rows:
-            self.__dict__["_direct_rows"] = value
+        self._set_rows_option("_direct_rows", bool(value), direct_rows=bool(value))
+
+    def _set_rows_option(self, key, value, **layer_attrs):
+        """A row-stationary kernel option changed: its value goes to every conv layer, which packs its weights again."""
+        if value != self.__dict__.get(key, False):
+            self.__dict__[key] = value
+            self._stage_a_stacks = {}
             for m_ in self.modules():
                 if isinstance(m_, TensorProductConvLayer):
-                    m_.direct_rows = value
-                    m_._packed_g = None
-                    m_._packed = None
+                    for name, v in layer_attrs.items():
+                        setattr(m_, name, v)
+                    m_._packed = m_._packed_g = None
             self.__dict__["_packed_epoch"] = self.__dict__.get("_packed_epoch", 0) + 1
 
-    def rows_all_or_none(self, device):
+    def rows_all_or_none(self, device) -> bool:
         """ddp_conv_rows runs either every factorised conv of its size class or none: stage A writes the G of several convs in one
-        launch, in ONE layout.  A conv whose weights the kernel's operand planes cannot hold (|w| > 255, packing.rows_stream) therefore
-        switches the model's factorised convs back to the 32-edge kernel.  Checked once per set of packed weights."""
-        if self.__dict__.get("_rows_checked_epoch") == self.__dict__.get("_packed_epoch", 0):
-            return
-        convs = [m for m in self.modules() if isinstance(m, TensorProductConvLayer) and getattr(m, "spec_g", None) is not None
-                 and P.rows_supported(m.spec_g)]
-        pks = [c.packed_g(device) for c in convs]
-        if any(pk.wsh is None for pk in pks):
-            for pk in pks:
-                pk.wsh = pk.bsp = pk.wgh = pk.gh_groups = pk.gh_ld = None
-        self.__dict__["_rows_checked_epoch"] = self.__dict__.get("_packed_epoch", 0)
+        launch, in ONE layout.  A conv whose weights the kernel's operand planes cannot hold (|w| > 255, packing.rows_stream), or whose
+        fc.3 bias stage A's planes cannot (packed_g), therefore moves the model's factorised convs back to the 32-edge kernel.  The
+        verdict (True: the rows kernel may run them) is made once per set of packed weights; launch.conv_path reads it."""
+        epoch = self.__dict__.get("_packed_epoch", 0)
+        if self.__dict__.get("_rows_ok_epoch") != epoch:
+            convs = [m for m in self.modules() if isinstance(m, TensorProductConvLayer) and m.spec_g is not None and P.rows_supported(m.spec_g)]
+            self.__dict__["_rows_ok"] = all(c.packed_g(device).wsh is not None for c in convs)
+            self.__dict__["_rows_ok_epoch"] = epoch
+        return self.__dict__["_rows_ok"]
 
     def invalidate_packed(self):
         # (a captured step holds the ADDRESSES of what is dropped here: sampler.Sampler compares this counter before a replay)
         self.__dict__["_packed_epoch"] = self.__dict__.get("_packed_epoch", 0) + 1
-        self.__dict__["_rows_checked_epoch"] = None
         self._weights_seen = None
         self._weights_seen_fp = None
         self.__dict__["_weight_tensors_"] = None

@@ -373,7 +373,7 @@ def test_values_outside_the_fp16_range_are_recovered_in_the_same_call(name):
 def test_rows_kernel_range_flag_is_raised_and_recovered():
     """the recovery test above scales fc.0 by 3e5, which puts |w| beyond the row-stationary kernel's weight planes (255) and
     moves the whole model to the 32-edge kernel - ddp_conv_rows' own flag site never ran.  Here the weights stay inside the planes
-    (launch.rows_mode stays on for every factorised conv) and a VALUE leaves the kernel's range: fc.0 (weight and bias) x 3000 and
+    (launch.conv_path keeps every factorised conv on it) and a VALUE leaves the kernel's range: fc.0 (weight and bias) x 3000 and
     fc.3 / 3000 on one conv (and its edge embeddings x 100): |w| <= 3000 x 0.075 < 255, h = relu(fc1) of many edges beyond the h plane's 4094 (65504 / DDP_ROWS_SH) but
     far inside the 65504 of the 32-edge kernel's 2048-scaled planes.  The forward returns the fp32 form's scores (1e-4 of the oracle),
     counts one recovery, and the next forward does the same.  (Stage A's flag - a plane value |32 G| beyond the range - is raised at unit
@@ -670,6 +670,7 @@ def test_single_conv_layer(ns, nv, layer, E, N, factorized, form, fmt):
     (ddp_conv_task_t::rows_form: 1 = v_mfma_f32_16x16x32_f16, the model's default) and both plane forms of G (gh_fmt: 1 = fp16 hi +
     continuation byte, the model's default) where the shape is one of that kernel's - a stand-alone layer has no model to set them; direct
     with form 1: through ddp_conv_rows16_direct_kernel (model.direct_rows: every feature a stream tile, the bias in k, feature chunks)."""
+    from diffdock_pocket_amd import launch as K
     from diffdock_pocket_amd import packing as P
     from diffdock_pocket_amd.score_model import TensorProductConvLayer
     torch.manual_seed(ns + layer + E)
@@ -697,8 +698,8 @@ def test_single_conv_layer(ns, nv, layer, E, N, factorized, form, fmt):
     if conv.direct_rows and ns == 60:
         assert conv.packed_rows_direct(dev) is not None and conv.packed_rows_direct(dev).rows_bias_k == 1
     if factorized and ns in (60, 32) and P.rows_supported(conv.spec_g):
-        pk = conv.packed_g(dev)
-        assert pk.wsh is not None and pk.rows_form == form and pk.gh_fmt == fmt      # (it ran through the kernel form and plane form asked for)
+        path = K.conv_path(conv.packed_g(dev))
+        assert path.rows and path.rows_form == form and path.gh_fmt == fmt      # (it ran through the kernel form and plane form asked for)
     assert got.shape == want.shape
     assert rel_err(got, want) < 2e-5, rel_err(got, want)
     # empty edge set: scalar zero, like the reference (models/score_model.py:109-111)
@@ -734,7 +735,7 @@ def test_rows_kernel_operand_planes_at_small_magnitudes(mag, form, fmt):
     dev = _dev()
     conv = conv.to(dev)
     conv.rows_form, conv.gh_fmt = form, fmt      # (1, 1: the model's defaults - the 16x16x32 kernel, G as fp16 hi + continuation byte: absolute 2^-24 / 32 on G below |32 G| = 2^-14)
-    assert K.CONV_ROWS and conv.packed_g(dev).wsh is not None      # (the row-stationary kernel's weight stream exists: this conv runs through it)
+    assert K.conv_path(conv.packed_g(dev)).rows      # (this conv runs through the row-stationary kernel)
     got = conv(x.to(dev), ei.to(dev), ea.to(dev), sh.to(dev), factorized=True).cpu()
     rows_was = K.CONV_ROWS
     K.CONV_ROWS = False

@@ -41,7 +41,7 @@ def main():
         model = TensorProductScoreModel(**kw)
         model.load_state_dict(sd, strict=True)
         model = model.to(dev).eval()
-        if not any(K.rows_mode(c.packed_g(dev)) for c in model.conv_layers if getattr(c, "spec_g", None) is not None):
+        if not any(K.conv_path(c.packed_g(dev), model.rows_all_or_none(dev)).rows for c in model.conv_layers if getattr(c, "spec_g", None) is not None):
             continue
         want = OracleScoreModel(case.oracle_config(), sd)(case.make_batch())
         keys = ("tr", "rot", "tor", "sc_tor")

@@ -98,15 +98,15 @@ def main():
     real_stage_a, real_launch = K.stage_a, K.launch_convs
     s1, s2 = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
 
-    def stage_a(x, n_rows, offs, nb, W, out, **kw):
-        real_stage_a(x, n_rows, offs, nb, W, out, **kw)
-        if kw.get("gh") is not None and kw.get("rows") is None and n_rows >= 40000:
-            last_sa["call"] = lambda: real_stage_a(x, n_rows, offs, nb, W, out, **kw)
+    def stage_a(x, n_rows, st, out, **kw):
+        real_stage_a(x, n_rows, st, out, **kw)
+        if st.path.rows and kw.get("rows") is None and n_rows >= 40000:
+            last_sa["call"] = lambda: real_stage_a(x, n_rows, st, out, **kw)
             last_sa["gb"] = out.numel() * 4 / 1e9
 
     def launch_convs(spec, tasks, flops_spec=None, node_bytes=0.0, tag=None):
         real_launch(spec, tasks, flops_spec=flops_spec, node_bytes=node_bytes, tag=tag)
-        if tag != "layer3" or not all(getattr(t, "_rows", False) for t in tasks) or "rows2" in res or "call" not in last_sa:
+        if tag != "layer3" or not all(t._path.rows for t in tasks) or "rows2" in res or "call" not in last_sa:
             return
         torch.cuda.synchronize()
         rows = lambda: real_launch(spec, tasks, flops_spec=flops_spec, node_bytes=node_bytes, tag=tag)      # noqa: E731

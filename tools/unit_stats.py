@@ -26,10 +26,10 @@ seen = []
 orig = sm._make_task
 
 
-def hooked(pk, x_src, ldx_src, csr, sh, segs, msg, g=None, pos=None):
+def hooked(pk, path, x_src, ldx_src, csr, sh, segs, msg, g=None):
     if g is not None and csr.n_edges > 0:      # factorised task: `csr` is the source-ordered view
         seen.append(csr)
-    return orig(pk, x_src, ldx_src, csr, sh, segs, msg, g=g, pos=pos)
+    return orig(pk, path, x_src, ldx_src, csr, sh, segs, msg, g=g)
 
 
 sm._make_task = hooked
