@@ -21,6 +21,7 @@ skipped, like the reference's per-complex try / except that returns 0 and goes o
 from __future__ import annotations
 
 import csv
+import dataclasses
 import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
@@ -29,6 +30,7 @@ import numpy as np
 import torch
 
 from . import inputs as I
+from . import outputs as O
 from .diffusion import get_t_schedule
 from .evaluation import PoseEvaluator, PoseMetrics  # noqa: F401
 from .sampler import Sampler, SamplerConfig
@@ -43,6 +45,9 @@ class ComplexResult:
     original_center: Optional[torch.Tensor] = None
     skipped: Optional[str] = None                  # reason, if the row could not be processed
     metrics: Optional["PoseMetrics"] = None        # run_csv(evaluate=True): evaluation.PoseMetrics against the input pose, ranked order
+    files: List[str] = field(default_factory=list)  # run_csv(out_dir=...): the paths written for this row
+    lig_traj: Optional[torch.Tensor] = None        # save_visualisation: [N, steps + 1, n_lig, 3] reverse process, ranked order
+    atom_traj: Optional[torch.Tensor] = None       # save_visualisation, flexible row: [N, steps + 1, n_moving, 3], ranked order
 
 
 def _none(v):
@@ -105,7 +110,8 @@ def build_row_graph(row: Dict, esm_embeddings=None, root: str = "", allow_zero_e
 def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_complex: int = 40, inference_steps: int = 20,
             esm_embeddings=None, root: str = "", seed: int = 0, rank: int = 0, world: int = 1, shard: str = "samples",
             dist=None, sampler_cfg: Optional[SamplerConfig] = None, graph_kwargs: Optional[Dict] = None,
-            allow_zero_esm: bool = False, evaluate: bool = False) -> List[ComplexResult]:
+            allow_zero_esm: bool = False, evaluate: bool = False, out_dir: Optional[str] = None,
+            save_visualisation: bool = False) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -119,14 +125,21 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     against the input ligand pose - the csv's ligand file is then the known pose - in the ranked order of `ligand_pos`), computed
     after the gather so that every rank holds the full set.  Rigid rows are scored against the row's full PDB (the reference's static
     receptor), flexible rows against the graph's atom nodes at each sample's side-chain positions (+ the side-chain RMSD).  A failure
-    of the evaluation skips the row like any other per-row failure."""
+    of the evaluation skips the row like any other per-row failure.
+
+    out_dir: every processed row also gets the files of reference inference.py:240-280 in `{out_dir}/index{i}___{name}`
+    (outputs.write_complex: ranked SDF poses, with flexible side chains the receptors with the moved side chains), listed in
+    `files`; save_visualisation=True records the reverse process on the device (SamplerConfig.record_trajectory) and adds
+    rank{k}_reverseprocess[_protein].pdb; the trajectories are also returned (`lig_traj`, `atom_traj`, ranked order).  With
+    sample sharding the full atom poses and the trajectories are gathered with the ligand poses and rank 0 alone writes (with
+    shard="complexes" each rank writes its own rows); a write failure skips the row on every rank."""
     dev = torch.device(device)
+    args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
+            shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
-            return _run_csv(csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root,
-                            seed, rank, world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate)
-    return _run_csv(csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed,
-                    rank, world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate)
+            return _run_csv(*args)
+    return _run_csv(*args)
 
 
 def _all_ok(dist, ok: bool, device) -> bool:
@@ -138,7 +151,8 @@ def _all_ok(dist, ok: bool, device) -> bool:
 
 
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
-             world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False) -> List[ComplexResult]:
+             world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
+             save_visualisation=False) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if shard not in ("samples", "complexes"):
         raise ValueError(shard)
@@ -165,19 +179,25 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             continue
         flex = bool(getattr(model, "flexible_sidechains", False)) and len(g["flexResidues"]) > 0
         cfg = sampler_cfg or SamplerConfig(inference_steps=inference_steps, flexible_sidechains=flex)
+        if save_visualisation and not cfg.record_trajectory:
+            cfg = dataclasses.replace(cfg, record_trajectory=True)
+        moved = flex and cfg.flexible_sidechains       # side chains sampled (else the written receptor is the input's)
         n = samples_per_complex
         sl = slice(rank * n // world, (rank + 1) * n // world) if split else slice(0, n)
         # Sampling can fail on ONE rank only (each rank holds other poses: a truncated ligand<-atom list - DdpError after the run's
         # final synchronisation -, DDP_ELIMIT, out of memory): like the reference (inference.py:282-287) the complex is then
         # skipped - on EVERY rank, agreed before anyone enters the gathers below
-        lig = conf = smp = apos = None
+        lig = conf = smp = apos = ltraj = atraj = None
         try:
             smp = Sampler(model, g, n, device, cfg, seed=seed + i, sample_slice=sl)
             smp.randomize()
             smp.run(schedule)
             lig = smp.lig_pos
-            if evaluate and flex:
+            if (evaluate and flex) or (out_dir is not None and moved):
                 apos = smp.atom_pos.clone()
+            if save_visualisation:
+                ltraj = smp.lig_traj.clone()
+                atraj = smp.atom_traj.clone() if smp.atom_traj is not None else None
             if confidence_model is not None:
                 conf, _ = smp.confidence(confidence_model)
         except Exception as e:      # noqa: BLE001
@@ -200,6 +220,10 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 conf = _gather_rows(dist, conf, sizes)
             if apos is not None:
                 apos = _gather_rows(dist, apos, sizes)
+            if ltraj is not None:
+                ltraj = _gather_rows(dist, ltraj, sizes)
+            if atraj is not None:
+                atraj = _gather_rows(dist, atraj, sizes)
         if conf is not None:      # reference inference.py:212-219: descending confidence (first column of a multi-output head)
             key = conf[:, 0] if conf.dim() == 2 else conf
             order = torch.argsort(key, descending=True)
@@ -221,7 +245,36 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 res.ligand_pos = res.confidence = res.order = None
                 continue
             res.metrics = metrics
+        if save_visualisation:
+            res.lig_traj = ltraj[order].cpu()
+            res.atom_traj = atraj[order].cpu() if atraj is not None else None
+        if out_dir is not None:
+            ok = True
+            if rank == 0 or not split:
+                try:
+                    res.files = _write_row(out_dir, i, row, root, g, res, apos[order].cpu() if moved else None,
+                                           (graph_kwargs or {}).get("remove_hs", True))
+                except Exception as e:      # noqa: BLE001
+                    res.skipped, ok = f"writing: {type(e).__name__}: {e}", False
+            if split and not _all_ok(dist, ok, device):
+                res.skipped = res.skipped or "skipped: writing failed on rank 0"
+                ok = False
+            if not ok:
+                res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = None
+                res.files = []
     return out
+
+
+def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) -> List[str]:
+    """outputs.write_complex for one processed row (ranked tensors of `res`)."""
+    with open(os.path.join(root, row["ligand"])) as f:
+        sdf_text = f.read()
+    pdb_text = None
+    if apos is not None or res.atom_traj is not None:
+        with open(os.path.join(root, row["experimental_protein"])) as f:
+            pdb_text = f.read()
+    return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
+                           apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs)
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -243,3 +296,130 @@ def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
     parts = [torch.empty_like(buf) for _ in sizes]
     dist.all_gather(parts, buf.contiguous())
     return torch.cat([p[:s] for p, s in zip(parts, sizes)], 0)
+
+
+# ---------------------------------------------------------------------------------------------- command line
+def _parser():
+    """Reference inference.py:49-103: the same flag names and defaults for what this package implements; --esm_embeddings,
+    --allow_zero_esm, --device and --seed are this package's."""
+    import argparse
+    from .sampler import TEMP_PSI, TEMP_SAMPLING, TEMP_SIGMA_DATA
+    p = argparse.ArgumentParser(prog="python -m diffdock_pocket_amd.inference",
+                                description="Dock SDF ligands into PDB pockets and write ranked poses (one process).")
+    p.add_argument("--complex_name", type=str, default="unnamed_complex")
+    p.add_argument("--protein_ligand_csv", type=str, default=None)
+    p.add_argument("--protein_path", "--experimental_protein", type=str, default=None)
+    p.add_argument("--ligand", type=str, default="COc(cc1)ccc1C#N", help="an SDF file (SMILES and other formats need rdkit: not read)")
+    p.add_argument("--flexible_sidechains", type=str, default=None)
+    p.add_argument("--out_dir", type=str, default="results/user_inference")
+    p.add_argument("--save_visualisation", action="store_true", default=False)
+    p.add_argument("--samples_per_complex", type=int, default=10)
+    p.add_argument("--rigid", action="store_true", default=False)
+    for a in "xyz":
+        p.add_argument(f"--pocket_center_{a}", type=float, default=None)
+    p.add_argument("--model_dir", type=str, default=None, help="score model: model_parameters.yml + checkpoint (required: no download)")
+    p.add_argument("--ckpt", type=str, default="best_ema_inference_epoch_model.pt")
+    p.add_argument("--filtering_model_dir", type=str, default=None)
+    p.add_argument("--filtering_ckpt", type=str, default="best_model.pt")
+    p.add_argument("--no_random", action="store_true", default=False)
+    p.add_argument("--no_final_step_noise", action="store_true", default=False)
+    p.add_argument("--ode", action="store_true", default=False)
+    p.add_argument("--inference_steps", type=int, default=30)
+    for k, name in enumerate(("tr", "rot", "tor", "sc_tor")):
+        p.add_argument(f"--temp_sampling_{name}", type=float, default=TEMP_SAMPLING[k])
+        p.add_argument(f"--temp_psi_{name}", type=float, default=TEMP_PSI[k])
+    p.add_argument("--temp_sigma_data", type=float, default=TEMP_SIGMA_DATA)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--esm_embeddings", type=str, default=None,
+                   help="directory of <complex_name>.pt / .npy ESM rows, or one .pt file holding {complex_name: rows}")
+    p.add_argument("--allow_zero_esm", action="store_true", default=False,
+                   help="run complexes without an ESM embedding on a zero block (out of the model's training distribution)")
+    p.add_argument("--device", type=str, default=None, help="default: cuda:0 when a GPU is visible, else cpu")
+    return p
+
+
+def _load_model(model_dir, ckpt, device, confidence_mode=False):
+    """(model, yml namespace): factory.get_model on model_parameters.yml, the checkpoint loaded strictly (inference.py:433-450)."""
+    import argparse
+    import functools
+    import yaml
+    from .diffusion import SigmaRanges, t_to_sigma
+    from .factory import get_model
+    with open(os.path.join(model_dir, "model_parameters.yml")) as f:
+        args = argparse.Namespace(**yaml.full_load(f))
+    sigma = SigmaRanges(**{k: float(getattr(args, k)) for k in SigmaRanges.__dataclass_fields__ if hasattr(args, k)})
+    model = get_model(args, device, functools.partial(t_to_sigma, args=sigma), no_parallel=True, confidence_mode=confidence_mode)
+    model.load_state_dict(torch.load(os.path.join(model_dir, ckpt), map_location="cpu", weights_only=True), strict=True)
+    return model.to(device).eval(), args, sigma
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    """The command line: `python -m diffdock_pocket_amd.inference --protein_path P --ligand L.sdf --model_dir M ...` or
+    `--protein_ligand_csv C`.  Writes `{out_dir}/index{i}___{name}` per complex (run_csv(out_dir=...)); returns 0 when every
+    complex was processed, 1 otherwise."""
+    import tempfile
+    ap = _parser()
+    a = ap.parse_args(argv)
+    if a.protein_ligand_csv is not None and a.protein_path is not None:
+        ap.error("give either --protein_ligand_csv or --protein_path, not both")
+    if a.protein_ligand_csv is None and a.protein_path is None:
+        ap.error("either --protein_ligand_csv or --protein_path has to be given")
+    if a.model_dir is None or not os.path.isfile(os.path.join(a.model_dir, "model_parameters.yml")):
+        ap.error(f"--model_dir {a.model_dir!r}: a directory with model_parameters.yml and the checkpoint is required "
+                 f"(models are not downloaded)")
+    if a.filtering_model_dir is not None and not os.path.isfile(os.path.join(a.filtering_model_dir, "model_parameters.yml")):
+        ap.error(f"--filtering_model_dir {a.filtering_model_dir!r} holds no model_parameters.yml")
+    if a.samples_per_complex < 1 or a.inference_steps < 1:
+        ap.error("--samples_per_complex and --inference_steps must be positive")
+    device = torch.device(a.device or ("cuda:0" if torch.cuda.is_available() else "cpu"))
+    model, margs, sigma = _load_model(a.model_dir, a.ckpt, device)
+    conf_model = _load_model(a.filtering_model_dir, a.filtering_ckpt, device, confidence_mode=True)[0] \
+        if a.filtering_model_dir is not None else None
+    flexible = bool(getattr(margs, "flexible_sidechains", False)) and not a.rigid
+    graph_kwargs = {k: getattr(margs, k) for k in ("receptor_radius", "c_alpha_max_neighbors", "remove_hs", "pocket_reduction",
+                                                   "pocket_buffer", "pocket_cutoff") if hasattr(margs, k)}
+    if flexible and getattr(margs, "flexdist", None) is not None:
+        graph_kwargs["flexdist"] = float(margs.flexdist)
+    cfg = SamplerConfig(inference_steps=a.inference_steps, sigma=sigma,
+                        temp_sampling=[a.temp_sampling_tr, a.temp_sampling_rot, a.temp_sampling_tor, a.temp_sampling_sc_tor],
+                        temp_psi=[a.temp_psi_tr, a.temp_psi_rot, a.temp_psi_tor, a.temp_psi_sc_tor], temp_sigma_data=a.temp_sigma_data,
+                        no_final_step_noise=a.no_final_step_noise, no_random=a.no_random, ode=a.ode, flexible_sidechains=flexible,
+                        no_torsion=bool(getattr(margs, "no_torsion", False)), record_trajectory=a.save_visualisation)
+    esm = a.esm_embeddings
+    if esm is not None and os.path.isfile(esm):
+        esm = torch.load(esm, map_location="cpu", weights_only=False)
+    os.makedirs(a.out_dir, exist_ok=True)
+    with tempfile.TemporaryDirectory() as tmp:
+        csv_path = a.protein_ligand_csv
+        if csv_path is None:      # one complex from the flags: a one-row csv (inference.py:351-361)
+            csv_path = os.path.join(tmp, "input.csv")
+            centre = [a.pocket_center_x, a.pocket_center_y, a.pocket_center_z]
+            with open(csv_path, "w", newline="") as f:
+                w = csv.writer(f)
+                w.writerow(["complex_name", "experimental_protein", "ligand", "pocket_center_x", "pocket_center_y", "pocket_center_z",
+                            "flexible_sidechains"])
+                w.writerow([a.complex_name, a.protein_path, a.ligand] + ["" if c is None else repr(c) for c in centre]
+                           + [a.flexible_sidechains or ""])
+        if a.rigid:       # no flexible residues in the graphs (the csv's flexible_sidechains column is ignored)
+            rows = load_protein_ligand_csv(csv_path)
+            rigid_csv = os.path.join(tmp, "rigid.csv")
+            with open(rigid_csv, "w", newline="") as f:
+                w = csv.writer(f)
+                w.writerow(["complex_name", "experimental_protein", "ligand", "pocket_center_x", "pocket_center_y", "pocket_center_z"])
+                for r in rows:
+                    w.writerow([r["complex_name"], r["experimental_protein"], r["ligand"]]
+                               + (["", "", ""] if r["pocket_center"] is None else [repr(c) for c in r["pocket_center"]]))
+            csv_path = rigid_csv
+        res = run_csv(csv_path, model, device, confidence_model=conf_model, samples_per_complex=a.samples_per_complex,
+                      inference_steps=a.inference_steps, esm_embeddings=esm, seed=a.seed, sampler_cfg=cfg, graph_kwargs=graph_kwargs,
+                      allow_zero_esm=a.allow_zero_esm, out_dir=a.out_dir, save_visualisation=a.save_visualisation)
+    failed = [r for r in res if r.skipped is not None]
+    for r in res:
+        print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)
+    print(f"{len(res) - len(failed)} of {len(res)} complexes written to {a.out_dir}", flush=True)
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

@@ -656,6 +656,23 @@ def sidechain_rotation_masks(rec: Receptor, accept_atom, heavy_mask: Optional[np
     return sub, np.asarray(mapping, dtype=np.int64).reshape(-1, 2), edges, np.asarray(n_bonds, dtype=np.int64), ids
 
 
+def _flex_atom_records(rec: Receptor, ids, heavy_mask: Optional[np.ndarray]) -> Dict[int, Tuple]:
+    """{atom node index: (chain, hetflag, resseq, icode, atom name)} over the atoms of the flexible residues `ids` (flexResidues.pdbIds):
+    the atom nodes are the kept residues' atoms in order, hydrogens dropped under remove_hs (receptor_graph).  A graph-level
+    attribute: `collate` does not carry it into the model's batch; outputs.write_receptor maps moved atoms back to PDB records with it."""
+    want, out, node, k = set(ids), {}, 0, 0
+    for r in rec.residues:
+        for a in r.atoms:
+            keep = heavy_mask is None or bool(heavy_mask[k])
+            k += 1
+            if not keep:
+                continue
+            if (r.chain, r.resseq) in want:
+                out[node] = (r.chain, r.hetflag, r.resseq, r.icode, a.name)
+            node += 1
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- the complex graph
 def build_complex_graph(pdb_text: str, sdf_text: str, *, name: str = "complex", pocket_center: Optional[Sequence[float]] = None,
                         pocket_reduction: bool = True, pocket_cutoff: float = 5.0, pocket_buffer: float = 10.0,
@@ -718,6 +735,7 @@ def build_complex_graph(pdb_text: str, sdf_text: str, *, name: str = "complex", 
                        subcomponentsMapping=torch.from_numpy(mapping), residueNBondsMapping=torch.from_numpy(n_bonds), pdbIds=ids)
             st.num_nodes = edges.shape[0]
             data["flexResidues"] = st
+            data.flex_atom_records = _flex_atom_records(rec, ids, heavy if remove_hs else None)
     data.num_graphs = 1
     data.name = name
     data.original_center = torch.from_numpy(np.asarray(protein_centre, dtype=np.float32)).reshape(1, 3)

@@ -1,0 +1,253 @@
+"""File output of a docking run: ranked ligand poses as SDF, the receptor with moved side chains and reverse-process trajectories as
+PDB (reference inference.py:146-165,212-280, utils/visualise.py).  Host code without rdkit / Biopython; it reads what `inputs`
+parses, and the formats are those of the reference's files:
+
+- `write_sdf`: one V2000 record of the heavy-atom molecule (`inputs.remove_hs`, graph node order = the ligand nodes), name line
+  from the input record, coordinates `%10.4f`, the input's bond orders, `M  CHG` for charged atoms (rdkit's MolToMolBlock layout).
+- `write_ligand_trajectory`: one MODEL / ENDMDL block per frame with HETATM records (residue UNL 1, element symbols) and the
+  CONECT records in the first model only, as the reference's PDBFile.write.
+- `write_receptor`: the ATOM / HETATM records of the input's first model in the input's order, hydrogens dropped under remove_hs,
+  of alternate locations the one `inputs.parse_pdb` keeps, the moving side-chain atoms' coordinates (columns 31-54) rewritten and
+  every other line byte for byte the input's.  Deviation: the reference (SidechainPDBFile on a Bio.PDB structure) also re-sorts the
+  atoms inside each residue by its SORTING_DICT; here the input's order is kept.
+
+Coordinates handed to the writers are pocket-centred (the graph's frame); `original_center` is added on the way out."""
+from __future__ import annotations
+
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import inputs as I
+
+
+def _np(x) -> np.ndarray:
+    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.float64)
+
+
+def _center(original_center) -> np.ndarray:
+    return _np(original_center).reshape(1, 3) if original_center is not None else np.zeros((1, 3))
+
+
+def sdf_name(sdf_text: str) -> str:
+    """Name line of the first record."""
+    return sdf_text.splitlines()[0] if sdf_text else ""
+
+
+def heavy_molecule(sdf_text: str) -> I.Molecule:
+    """The molecule the ligand nodes were built from (inputs.ligand_graph with remove_hs)."""
+    return I.remove_hs(I.parse_sdf(sdf_text))[0]
+
+
+# ---------------------------------------------------------------------------------------------- SDF
+def sdf_block(mol: I.Molecule, pos, name: str = "") -> str:
+    """One V2000 record (ending in `$$$$`) of `mol` at `pos` [n_atoms, 3] (absolute coordinates)."""
+    pos = _np(pos).reshape(-1, 3)
+    if pos.shape[0] != len(mol.elements):
+        raise ValueError(f"{pos.shape[0]} coordinates for {len(mol.elements)} atoms")
+    if len(mol.elements) > 999 or len(mol.bonds) > 999:
+        raise ValueError("V2000 holds at most 999 atoms and bonds")
+    out = [name, "     DDPAMD          3D", "",
+           f"{len(mol.elements):3d}{len(mol.bonds):3d}  0  0  0  0  0  0  0  0999 V2000"]
+    for (x, y, z), e in zip(pos, mol.elements):
+        out.append(f"{x:10.4f}{y:10.4f}{z:10.4f} {e:<3} 0  0  0  0  0  0  0  0  0  0  0  0")
+    for a, b, o in mol.bonds:
+        out.append(f"{a + 1:3d}{b + 1:3d}{o:3d}  0")
+    charged = [(i + 1, c) for i, c in enumerate(mol.charges) if c]
+    for k in range(0, len(charged), 8):
+        part = charged[k:k + 8]
+        out.append(f"M  CHG{len(part):3d}" + "".join(f" {i:3d} {c:3d}" for i, c in part))
+    out += ["M  END", "$$$$"]
+    return "\n".join(out) + "\n"
+
+
+def write_sdf(path: str, mol: I.Molecule, pos, name: str = "", original_center=None) -> str:
+    """`pos` pocket-centred [n_atoms, 3]; the file gets pos + original_center."""
+    with open(path, "w") as f:
+        f.write(sdf_block(mol, _np(pos).reshape(-1, 3) + _center(original_center), name))
+    return path
+
+
+# ---------------------------------------------------------------------------------------------- ligand trajectory
+def _pdb_atom_names(elements: Sequence[str]) -> List[str]:
+    """rdkit's MolToPDBBlock naming: element + running number per element, one-letter elements from column 14."""
+    seen: Dict[str, int] = {}
+    names = []
+    for e in elements:
+        sym = e.upper()
+        seen[sym] = seen.get(sym, 0) + 1
+        nm = f"{sym}{seen[sym]}"
+        names.append((" " + nm if len(sym) == 1 and len(nm) < 4 else nm)[:4].ljust(4))
+    return names
+
+
+def ligand_pdb_model(mol: I.Molecule, pos, conect: bool) -> List[str]:
+    """HETATM records (+ CONECT) of one frame, absolute coordinates."""
+    pos = _np(pos).reshape(-1, 3)
+    names = _pdb_atom_names(mol.elements)
+    out = []
+    for i, ((x, y, z), e) in enumerate(zip(pos, mol.elements)):
+        out.append(f"HETATM{i + 1:5d} {names[i]} UNL     1    {x:8.3f}{y:8.3f}{z:8.3f}  1.00  0.00          {e.upper():>2}  ")
+    if conect:
+        nbr: List[List[int]] = [[] for _ in mol.elements]
+        for a, b, _ in mol.bonds:
+            nbr[a].append(b)
+            nbr[b].append(a)
+        for i, js in enumerate(nbr):
+            for k in range(0, len(js), 4):
+                out.append(f"CONECT{i + 1:5d}" + "".join(f"{j + 1:5d}" for j in sorted(js)[k:k + 4]))
+    return out
+
+
+def write_ligand_trajectory(path: str, mol: I.Molecule, frames, original_center=None) -> str:
+    """One MODEL per frame; `frames` [F, n_atoms, 3] pocket-centred (ligand_frames gives the reference's sequence)."""
+    c = _center(original_center)
+    out = []
+    for k, pos in enumerate(frames):
+        out.append(f"MODEL     {k + 1:4d}")
+        out += ligand_pdb_model(mol, _np(pos).reshape(-1, 3) + c, conect=k == 0)
+        out.append("ENDMDL")
+    out.append("END")
+    with open(path, "w") as f:
+        f.write("\n".join(out) + "\n")
+    return path
+
+
+def ligand_frames(input_pos, traj) -> list:
+    """The reference's frame order (inference.py:153-158, utils/sampling.py): input pose, input pose, then the trajectory
+    (slot 0 = randomised pose, slot t + 1 = after step t): n_slots + 2 frames, pocket-centred."""
+    return [input_pos, input_pos] + list(traj)
+
+
+# ---------------------------------------------------------------------------------------------- receptor
+def _kept_records(pdb_text: str, remove_hs: bool):
+    """(lines, kept line numbers in input order, {(chain, hetflag, resseq, icode, name): line number}) over the ATOM / HETATM
+    records of the first model, alternate locations resolved as inputs.parse_pdb resolves them (highest occupancy, first on ties)."""
+    lines = pdb_text.splitlines()
+    best: Dict[Tuple, Tuple[int, float]] = {}
+    for k, ln in enumerate(lines):
+        rec = ln[:6]
+        if rec.startswith("ENDMDL"):
+            break
+        if rec not in ("ATOM  ", "HETATM"):
+            continue
+        resname, chain, altloc = ln[17:20].strip(), ln[21], ln[16]
+        hetflag = " " if rec == "ATOM  " else ("W" if resname in ("HOH", "WAT") else "H_" + resname)
+        key = (chain, hetflag, int(ln[22:26]), ln[26], ln[12:16].strip())
+        try:
+            occ = float(ln[54:60])
+        except ValueError:
+            occ = 1.0
+        old = best.get(key)
+        if old is None or (altloc != " " and occ > old[1]):
+            best[key] = (k, occ)
+    rows = {key: k for key, (k, _) in best.items()}
+    kept = sorted(rows.values())
+    if remove_hs:
+        def element(ln):
+            e = ln[76:78].strip().upper() if len(ln) >= 78 else ""
+            return e or I._element_from_name(ln[12:16])
+        kept = [k for k in kept if element(lines[k]) != "H"]
+    return lines, kept, rows
+
+
+def receptor_pdb(pdb_text: str, flex_atom_records: Dict[int, Tuple], moving: Sequence[int], frames, original_center=None,
+                 remove_hs: bool = True) -> str:
+    """Text of `write_receptor`.  moving [n_moving] atom node indices (sorted unique flexResidues.subcomponents); frames: a list of
+    [n_moving, 3] pocket-centred positions, or None for a frame at the input coordinates."""
+    lines, kept, rows = _kept_records(pdb_text, remove_hs)
+    moving = [int(m) for m in moving]
+    try:
+        line_of = [rows[flex_atom_records[m]] for m in moving]
+    except KeyError as e:
+        raise ValueError(f"moving atom {e} has no PDB record") from None
+    c = _center(original_center)
+    multi = len(frames) > 1
+    out = []
+    for f, pos in enumerate(frames):
+        new = {}
+        if pos is not None:
+            p = _np(pos).reshape(-1, 3) + c
+            if p.shape[0] != len(moving):
+                raise ValueError(f"{p.shape[0]} positions for {len(moving)} moving atoms")
+            for k, (x, y, z) in zip(line_of, p):
+                ln = lines[k]
+                new[k] = ln[:30] + f"{x:8.3f}{y:8.3f}{z:8.3f}" + ln[54:]
+        if multi:
+            out.append(f"MODEL     {f + 1:4d}")
+        out += [new.get(k, lines[k]) for k in kept]
+        if multi:
+            out.append("ENDMDL")
+    out.append("END")
+    return "\n".join(out) + "\n"
+
+
+def write_receptor(path: str, pdb_text: str, graph, frames, remove_hs: bool = True) -> str:
+    """The input receptor with the moving side-chain atoms of `graph` (inputs.build_complex_graph with flexible side chains) at
+    `frames` (see receptor_pdb; one frame: no MODEL records)."""
+    text = receptor_pdb(pdb_text, graph.flex_atom_records, moving_atoms(graph).tolist(), frames, getattr(graph, "original_center", None), remove_hs)
+    with open(path, "w") as f:
+        f.write(text)
+    return path
+
+
+def moving_atoms(graph) -> torch.Tensor:
+    """Sorted unique flexResidues.subcomponents: the atom nodes side-chain torsions move (Sampler.moving_atoms)."""
+    return torch.unique(torch.as_tensor(graph["flexResidues"].subcomponents).cpu())
+
+
+# ---------------------------------------------------------------------------------------------- one complex
+def complex_dir(out_dir: str, index: int, name: str) -> str:
+    """reference inference.py:136."""
+    return os.path.join(out_dir, f'index{index}___{name.replace("/", "-")}')
+
+
+def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
+                  lig_traj=None, atom_traj=None, remove_hs: bool = True) -> List[str]:
+    """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
+    ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
+    lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
+
+    With a confidence model: rank1.sdf and rank{k}_confidence{c:.2f}.sdf; without one rank{k}.sdf (the reference fails there).
+    Flexible: rank1_protein.pdb and rank{k}_confidence{c:.2f}_protein.pdb (rank{k}_protein.pdb).  Trajectories:
+    rank{k}_reverseprocess.pdb and rank{k}_reverseprocess_protein.pdb, each of the ranked sample itself (the reference indexes the
+    side-chain trajectories by rank instead of by sample, inference.py:276-279)."""
+    os.makedirs(write_dir, exist_ok=True)
+    mol = heavy_molecule(sdf_text)
+    name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
+    conf = None
+    if confidence is not None:
+        conf = _np(confidence)
+        conf = conf[:, 0] if conf.ndim == 2 else conf
+    tag = (lambda k: f"rank{k + 1}_confidence{conf[k]:.2f}") if conf is not None else (lambda k: f"rank{k + 1}")
+    moving = moving_atoms(graph).tolist() if atom_pos is not None or atom_traj is not None else None
+    written = []
+
+    def put(path):
+        written.append(path)
+        return path
+
+    for k in range(ligand_pos.shape[0]):
+        if k == 0 and conf is not None:
+            write_sdf(put(os.path.join(write_dir, "rank1.sdf")), mol, ligand_pos[k], name, oc)
+        write_sdf(put(os.path.join(write_dir, tag(k) + ".sdf")), mol, ligand_pos[k], name, oc)
+    if atom_pos is not None:
+        for k in range(atom_pos.shape[0]):
+            text = receptor_pdb(pdb_text, graph.flex_atom_records, moving, [_np(atom_pos[k])[moving]], oc, remove_hs)
+            for fn in (["rank1_protein.pdb"] if k == 0 and conf is not None else []) + [tag(k) + "_protein.pdb"]:
+                with open(put(os.path.join(write_dir, fn)), "w") as f:
+                    f.write(text)
+    if lig_traj is not None:
+        start = graph["ligand"].pos
+        for k in range(lig_traj.shape[0]):
+            write_ligand_trajectory(put(os.path.join(write_dir, f"rank{k + 1}_reverseprocess.pdb")), mol,
+                                    ligand_frames(start, lig_traj[k]), oc)
+    if atom_traj is not None:
+        for k in range(atom_traj.shape[0]):
+            frames = [None, None] + [f for f in atom_traj[k]]
+            text = receptor_pdb(pdb_text, graph.flex_atom_records, moving, frames, oc, remove_hs)
+            with open(put(os.path.join(write_dir, f"rank{k + 1}_reverseprocess_protein.pdb")), "w") as f:
+                f.write(text)
+    return written

@@ -124,6 +124,31 @@ def modify_conformer_hip(pos, tr, rot, tor, bonds_i32, mask_u8):
     return out
 
 
+def record_trajectory_hip(lig_pos, lig_traj, slot_dev, atom_pos=None, moving_i32=None, atom_traj=None):
+    """One ddp_traj_record launch (csrc/ddp_traj.hip): lig_traj[:, k] = lig_pos and atom_traj[:, k] = atom_pos[:, moving] with
+    k = slot_dev[0], read on the device (a slot outside [0, n_slots) writes nothing).  lig_pos [n, n_lig, 3], lig_traj
+    [n, n_slots, n_lig, 3], atom_pos [n, n_atoms, 3], moving_i32 int32 [n_moving], atom_traj [n, n_slots, n_moving, 3]: fp32
+    contiguous device tensors; shapes are checked here, before the launch."""
+    from . import _lib as L
+    lib = L.load()
+    n, n_l = lig_pos.shape[0], lig_pos.shape[1]
+    ts = [lig_pos, lig_traj, slot_dev] + ([atom_pos, atom_traj] if moving_i32 is not None else [])
+    if any(t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != lig_pos.device for t in ts):
+        raise ValueError("record_trajectory_hip: fp32 contiguous tensors on one HIP device expected")
+    if lig_pos.dim() != 3 or lig_pos.shape[2] != 3 or lig_traj.dim() != 4 or tuple(lig_traj.shape[::2]) != (n, n_l) \
+            or lig_traj.shape[3] != 3 or slot_dev.numel() < 1:
+        raise ValueError(f"record_trajectory_hip: lig_traj {tuple(lig_traj.shape)} does not match lig_pos {tuple(lig_pos.shape)}")
+    n_slots, n_a, n_m = lig_traj.shape[1], 0, 0
+    if moving_i32 is not None:
+        n_a, n_m = atom_pos.shape[1], moving_i32.numel()
+        if moving_i32.dtype != torch.int32 or moving_i32.device != lig_pos.device or tuple(atom_pos.shape[::2]) != (n, 3) \
+                or tuple(atom_traj.shape) != (n, n_slots, n_m, 3):
+            raise ValueError("record_trajectory_hip: atom_pos / moving / atom_traj shapes")
+    L.check(lib.ddp_traj_record(lig_pos.data_ptr(), n, n_l, lig_traj.data_ptr(), atom_pos.data_ptr() if n_m else None, n_a,
+                                moving_i32.data_ptr() if n_m else None, n_m, atom_traj.data_ptr() if n_m else None, n_slots,
+                                slot_dev.data_ptr(), torch._C._cuda_getCurrentRawStream(lig_pos.device.index)), "ddp_traj_record")
+
+
 def modify_conformer(pos, tr, rot, tor, bonds, mask_rotate):
     """Batched modify_conformer (reference utils/diffusion_utils.py:37-60), pivot=None.
     pos [N,n,3]; tr, rot [N,3]; tor [N,T] or None."""
@@ -151,6 +176,7 @@ class SamplerConfig:
     no_torsion: bool = False
     hip_graph: bool = True     # on a HIP device: capture one denoising step (forward + SDE step + pose update) in a hipGraph
                                # after two ordinary steps and replay it from then on (no host work per launch)
+    record_trajectory: bool = False    # keep every step's poses (Sampler.lig_traj / atom_traj: the --save_visualisation frames)
 
 
 class Sampler:
@@ -192,8 +218,44 @@ class Sampler:
         self._graph_epoch, self._graph_stats, self._graph_keep = 0, None, None
         self.graph_enabled = True      # False: the step is launched kernel by kernel even if a graph has been captured
         self._steps_run = 0
+        self.lig_traj = self.atom_traj = None
+        if cfg.record_trajectory:
+            self._init_trajectory()
         if self.on_hip:
             self._init_step_buffers()
+
+    # -- reverse-process trajectory (SamplerConfig.record_trajectory) ----------------------------------------------
+    def _init_trajectory(self):
+        """lig_traj [n, inference_steps + 1, n_lig, 3] and, with flexible side chains, atom_traj [n, inference_steps + 1, n_moving,
+        3] (the moving atoms = the sorted unique side-chain subcomponents, `moving_atoms`), pocket-centred fp32.  Slot 0 holds the
+        poses the first step starts from (written by `randomize` / `restore`), slot t + 1 the poses after step t.  On a HIP device
+        the steps record through ddp_traj_record inside the step (captured with it): its slot is params[1] = t_idx + 1."""
+        n_slots = self.cfg.inference_steps + 1
+        self.lig_traj = torch.zeros(self.n, n_slots, self.n_l, 3, device=self.device)
+        self.moving_atoms = None
+        if self.has_flex:
+            self.moving_atoms = torch.unique(self.sc_sub.cpu())          # (sorted)
+            if self.moving_atoms.numel() and (int(self.moving_atoms[0]) < 0 or int(self.moving_atoms[-1]) >= self.n_a):
+                raise ValueError("flexResidues.subcomponents index outside the atom nodes")
+            self.moving_i32 = self.moving_atoms.to(torch.int32).to(self.device)
+            self.atom_traj = torch.zeros(self.n, n_slots, self.moving_atoms.numel(), 3, device=self.device)
+        if self.on_hip:
+            self._slot0 = torch.zeros(1, device=self.device)      # slot index 0 in device memory (randomize / restore)
+
+    def _check_slot(self, t_idx):
+        if not 0 <= t_idx < self.cfg.inference_steps:
+            raise ValueError(f"step {t_idx} outside the {self.cfg.inference_steps} steps the trajectory was allocated for")
+
+    def _record(self, slot_dev=None, slot=0):
+        """Poses -> trajectory slot: `slot_dev` (device memory, HIP) or `slot` (CPU: plain copies)."""
+        if not self.on_hip:
+            self.lig_traj[:, slot] = self.lig_pos
+            if self.atom_traj is not None:
+                self.atom_traj[:, slot] = self.atom_pos[:, self.moving_atoms]
+            return
+        flex = self.atom_traj is not None
+        record_trajectory_hip(self.lig_pos, self.lig_traj, self._slot0 if slot_dev is None else slot_dev,
+                              self.atom_pos if flex else None, self.moving_i32 if flex else None, self.atom_traj)
 
     # -- device-resident step state (HIP) ------------------------------------------------------------------------
     def _init_step_buffers(self):
@@ -257,6 +319,8 @@ class Sampler:
         self._set_pos("lig_pos", snap[0])
         self._set_pos("atom_pos", snap[1])
         self.gen.set_state(snap[2])
+        if self.lig_traj is not None:      # the run starts again from these poses
+            self._record()
 
     def _step_coefficients(self, t_idx, schedule):
         """(t, [a_tr b_tr a_rot b_rot a_tor b_tor a_sc b_sc], noise on) of a step: update_k = a_k * score_k + b_k * z_k
@@ -292,6 +356,8 @@ class Sampler:
         host = self._pinned_row()
         host[0] = t
         host[1:8] = 0.0
+        if self.lig_traj is not None:
+            host[1] = t_idx + 1            # the trajectory slot of ddp_traj_record (exact as a float)
         host[8:16] = torch.tensor(coef, dtype=torch.float64).float()
         o = self._off
 
@@ -357,6 +423,8 @@ class Sampler:
                                     self.bonds_i32.data_ptr() if use_tor else None, self.mask_u8.data_ptr() if use_tor else None,
                                     self.lig_pos.data_ptr(), st), "ddp_pose_update")
         torch.autograd.graph.increment_version(self.lig_pos)
+        if self.lig_traj is not None:
+            self._record(self.params[1:2])
 
     def _step_hip(self, t_idx, schedule):
         with torch.cuda.device(self.device):
@@ -487,6 +555,8 @@ class Sampler:
             tr = torch.randn((N, 1, 3), generator=self.gen) * cfg.sigma.tr_sigma_max
             new = new + tr[sl].to(self.device)
         self._set_pos("lig_pos", new)
+        if self.lig_traj is not None:
+            self._record()
 
     def _set_pos(self, name, value):
         """Poses are replaced on the CPU path and written IN PLACE on a HIP device (the batch holds views of them and a captured
@@ -498,6 +568,8 @@ class Sampler:
 
     # -- one denoising step (reference utils/sampling.py:93-251) ------------------------------------------------
     def step(self, t_idx: int, schedule: np.ndarray):
+        if self.lig_traj is not None:
+            self._check_slot(t_idx)
         if self.on_hip:
             return self._step_hip(t_idx, schedule)
         cfg, sg, N, sl, dev = self.cfg, self.cfg.sigma, self.n_total, self.slice, self.device
@@ -563,6 +635,8 @@ class Sampler:
             self.lig_pos = modify_conformer_hip(self.lig_pos, tr_p, rot_p, tor_p, self.bonds_i32, self.mask_u8)
         else:
             self.lig_pos = modify_conformer(self.lig_pos, tr_p, rot_p, tor_p, self.bonds, self.rot_idx)
+        if self.lig_traj is not None:
+            self._record(slot=t_idx + 1)
 
     def _call_model(self, model, b):
         """The weights' VALUE fingerprint (score_model._refresh_weight_caches: one host synchronisation) is checked on the
@@ -668,6 +742,8 @@ class PipelinedSampler:
 
     def __init__(self, model, complex_graph: HeteroBatch, n_total: int, device, cfg: SamplerConfig, seed: int = 0,
                  sample_slice: Optional[slice] = None, ways: int = 2):
+        if cfg.record_trajectory:
+            raise NotImplementedError("PipelinedSampler does not record trajectories: use Sampler(record_trajectory=True)")
         self.model, self.device = model, device
         lo, hi, _ = (sample_slice or slice(0, n_total)).indices(n_total)
         ways = max(1, min(ways, hi - lo))

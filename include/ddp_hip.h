@@ -704,6 +704,16 @@ int ddp_pose_rmsd(const float* pred, int n_samples, int pred_stride, const int32
 int ddp_pose_contacts(const float* lig, int n_samples, int n, const float* lig_radii, const float* rec, int m, int rec_stride,
                       const float* rec_radii, float overlap, const float* ref_centroid, float* out, void* stream);
 
+/* ---- reverse-process trajectory recording (csrc/ddp_traj.hip; host side diffdock_pocket_amd/sampler.py).
+ * ddp_traj_record: k = (int)slot[0], read on the device (a captured launch serves every step: the sampler's step parameter block
+ * holds t_idx + 1); a slot outside [0, n_slots) (or NaN) writes nothing.  Exact copies, sample-major:
+ *   lig_traj[s][k]  = lig_pos[s]                  lig_pos [n][n_lig][3], lig_traj [n][n_slots][n_lig][3]
+ *   atom_traj[s][k][m] = atom_pos[s][moving[m]]   atom_pos [n][n_atoms][3], moving [n_moving], atom_traj [n][n_slots][n_moving][3]
+ * n_moving = 0: ligand only (atom_pos, moving, atom_traj may be NULL).  A moving index outside [0, n_atoms) is skipped (no read, no
+ * write); the host checks the list before it is uploaded.  n = 0: no-op. */
+int ddp_traj_record(const float* lig_pos, int n, int n_lig, float* lig_traj, const float* atom_pos, int n_atoms, const int32_t* moving,
+                    int n_moving, float* atom_traj, int n_slots, const float* slot, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
 /* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, csrc/ddp_internal.h, include/ddp_hip.h) the library was built from */
