@@ -480,11 +480,19 @@ __global__ void ddp_torsion_sh_kernel(const float* __restrict__ sh_edge, const f
   const float nx = s[1] * inv3, ny = s[2] * inv3, nz = s[3] * inv3;  // unit edge vector
   const int b = bond_of_edge[e];
   float vx = bond_vec[3 * b], vy = bond_vec[3 * b + 1], vz = bond_vec[3 * b + 2];
-  const float vin = 1.0f / fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), 1e-12f);
+  const float len = sqrtf(vx * vx + vy * vy + vz * vz);
+  const float vin = 1.0f / fmaxf(len, 1e-12f);
   vx *= vin; vy *= vin; vz *= vin;
   const float dot3 = 3.0f * (nx * vx + ny * vy + nz * vz);
   const float k = 1.2247448713915890f;  // sqrt(3/2)
-  reinterpret_cast<f32x4*>(out)[e] = f32x4{0.f, k * (dot3 * vx - nx), k * (dot3 * vy - ny), k * (dot3 * vz - nz)};
+  // Y2 is a homogeneous quadratic of v = bond / max(|bond|, 1e-12) (F.normalize): the general form is 3 (n.v) v - |v|^2 n.  |v| = 1
+  // for every bond longer than the eps; a shorter one (a zero bond: v = 0) gives a zero row, as o3.spherical_harmonics does
+  float sx = nx, sy = ny, sz = nz;
+  if (len < 1e-12f) {
+    const float vv = vx * vx + vy * vy + vz * vz;
+    sx *= vv; sy *= vv; sz *= vv;
+  }
+  reinterpret_cast<f32x4*>(out)[e] = f32x4{0.f, k * (dot3 * vx - sx), k * (dot3 * vy - sy), k * (dot3 * vz - sz)};
 }
 
 extern "C" int ddp_torsion_sh(const float* sh_edge, const float* bond_vec, const int32_t* bond_of_edge, int n_edges,

@@ -224,7 +224,11 @@ def knn_graph(x, k, lx: DenseLayout):
     kk = min(k, max(lx.nmax - 1, 0))
     if kk == 0:
         return torch.zeros((2, 0), dtype=torch.long, device=x.device)
-    val, idx = torch.topk(d2, kk, dim=-1, largest=False, sorted=True)     # [B, n, kk]
+    # Equal distances: the lower node index first.  This is ddp_knn's rule ((distance, index) order, csrc/ddp_graph.hip) adopted as
+    # the definition - torch.topk, used here before, leaves the order of equal distances open, so there was none.  A full stable
+    # sort in place of a top-k, on this CPU path only (tests and the CPU oracle; the device path never comes here)
+    val, idx = torch.sort(d2, dim=-1, stable=True)
+    val, idx = val[..., :kk], idx[..., :kk]                               # [B, n, kk]
     q = lx.index.unsqueeze(-1).expand_as(idx)
     nb = torch.gather(lx.index.unsqueeze(1).expand(-1, d2.shape[1], -1), 2, idx)
     keep = torch.isfinite(val) & (q >= 0)

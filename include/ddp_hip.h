@@ -285,7 +285,8 @@ typedef struct {
 int ddp_edge_featurize_jobs(const ddp_featurize_job_t* jobs, int njobs, void* stream);
 
 /* Torsion-head edge harmonics: the 1o block of FullTensorProduct(sh(edge), Y2(bond)) in closed form,
- *   t[e] = sqrt(3/2) * (3 (n.v) v - n),  n = unit(sh edge vector), v = unit(bond vector of bond ib[e])
+ *   t[e] = sqrt(3/2) * (3 (n.v) v - |v|^2 n),  n = unit(sh edge vector), v = bond vector of bond ib[e] / max(its length, 1e-12)
+ * (|v| = 1 but for a bond shorter than 1e-12: a zero-length bond gives a zero row, as the spherical harmonics of F.normalize's zero vector do)
  * written as [0, t] so the conv kernel reads it like an edge_sh row.
  * Replaces all_atom_score_model.py:394-395,418-419 (o3.spherical_harmonics("2e") + o3.FullTensorProduct). */
 /* The same launch also writes the bonds' node attributes (optional, bond_attr == NULL skips it):
