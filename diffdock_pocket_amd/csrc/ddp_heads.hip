@@ -69,7 +69,7 @@ __global__ __launch_bounds__(DDP_HEAD_THREADS) void ddp_step_prologue_kernel(Pro
       }
       x = wave_sum(x); y = wave_sum(y); z = wave_sum(z);
       if (lane == 0) {
-        const float n = (float)(p1 - p0);
+        const float n = (float)max(p1 - p0, 1);   // an empty graph: 0 / 1, torch_scatter's mean (count clamped to 1)
         A.center[3 * g] = __fdiv_rn(x, n);
         A.center[3 * g + 1] = __fdiv_rn(y, n);
         A.center[3 * g + 2] = __fdiv_rn(z, n);

@@ -249,8 +249,7 @@ int ddp_segment_reduce(float* x, int ldx, int n_nodes, int d_out, const ddp_redu
  * arrays (see "Device-side counts" below).
  * Replaces GaussianSmearing (models/score_model.py:661-671), o3.spherical_harmonics and the *_edge_embedding MLPs
  * (models/all_atom_score_model.py:71-81,164-169,187-192,212-217 and the builders :444-636).
- * w1d: [k_rbf, 64] (zero padded columns), w2: [64, 64] (zero padded), b2: [64]; out: [E, ns]; sh: [E, 4]; vec_out
- * (optional, may be null): [E, 4] = (vec, d). */
+ * w1d: [k_rbf, 64] (zero padded columns), w2: [64, 64] (zero padded), b2: [64]; out: [E, ns]; sh: [E, 4]. */
 int ddp_edge_featurize(const float* pos_a, const int32_t* ia, const float* pos_b, const int32_t* ib, int n_edges,
                        const int32_t* n_edges_dev, const float* offset, int k_rbf, float coeff, const float* pre,
                        const int32_t* pre_idx, int ld_pre, const float* pre2, int n_pre2, int ld_pre2, const float* w1d,
@@ -307,7 +306,8 @@ int ddp_torsion_sh(const float* sh_edge, const float* bond_vec, const int32_t* b
  *   cut[g]                = sigma[0][g] * cut_mul + cut_add     (dynamic cross cutoff 3 sigma_tr + 20, all_atom_score_model.py:548-550)
  *   graph_emb[g, 0..sd)   sinusoidal embedding of t[0][g] (utils/diffusion_utils.py:73-84: [sin | cos] of emb_scale * t * freq[s]);
  *                         the read-out MLPs' input (:371)
- *   center[g]             mean of lig_pos over graph_ptr[g] .. graph_ptr[g+1] (:571-576)
+ *   center[g]             mean of lig_pos over graph_ptr[g] .. graph_ptr[g+1] (:571-576); an empty graph (graph_ptr[g] ==
+ *                         graph_ptr[g+1]) gets the zero centre: torch_scatter's mean divides by the count clamped to 1
  *   bonds[h]              h = 0 ligand torsion head, 1 side-chain head: mid[i] = (pos[b0[i]] + pos[b1[i]]) / 2 (:589-592,613-616),
  *                         vec[i] = pos[b1[i]] - pos[b0[i]] (:392,416)
  *   copy[h]               dst[0..n) = src[0..n) (int32): the bond rows in front of the ligand edge list (:462-468) */

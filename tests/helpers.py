@@ -1,12 +1,38 @@
 """Shared test helpers: load a golden case, rebuild its seeded weights and inputs."""
 import os
 
+import numpy as np
 import torch
 
 from oracle.cases import CASES, input_checksums
 from oracle.weights import synth_state_dict
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+SENTINEL = np.float32(-123456.7890625)     # a value no kernel under test produces; compared bit for bit (the fp64 kernel tests)
+
+
+def _up(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _bits(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+def _assert_within(got, want, tol, what):
+    """|got - want| <= tol element by element (NaN / inf in `got` fail); prints the largest error / bound ratio."""
+    got = np.asarray(got, dtype=np.float64)
+    err = np.abs(got - want)
+    ok = err <= tol
+    ratio = float(np.max(err / np.maximum(tol, 1e-300))) if err.size else 0.0
+    print(f"[fp64] {what}: max err {float(np.nanmax(err)) if err.size else 0.0:.3e}, max err/bound {ratio:.3f}")
+    if not ok.all():
+        i = np.unravel_index(np.argmax(np.where(ok, 0.0, np.where(np.isfinite(err), err - tol, np.inf))), err.shape)
+        raise AssertionError(f"{what}: {int((~ok).sum())} of {ok.size} elements outside the bound; worst at {tuple(int(v) for v in i)}: "
+                             f"got {got[i]!r}, want {want[i]!r}, |diff| {err[i]:.3e}, bound {tol[i]:.3e}")
 
 
 def load_golden(name):

@@ -15,11 +15,12 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import SENTINEL, _assert_within, _bits, _up
+
 pytestmark = pytest.mark.gpu
 
 U23 = 2.0 ** -23
 U24 = 2.0 ** -24
-SENTINEL = np.float32(-123456.7890625)     # a value no kernel under test produces; compared bit for bit
 
 
 def _dev():
@@ -33,30 +34,8 @@ def _api():
     return L, L.load(), K
 
 
-def _up(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a).view(np.int32)
-
-
 def _same_bits(a, b):
     return np.array_equal(_bits(a), _bits(b))
-
-
-def _assert_within(got, want, tol, what):
-    """|got - want| <= tol element by element (NaN / inf in `got` fail); prints the largest error / bound ratio."""
-    got = np.asarray(got, dtype=np.float64)
-    err = np.abs(got - want)
-    ok = err <= tol
-    ratio = float(np.max(err / np.maximum(tol, 1e-300))) if err.size else 0.0
-    print(f"[fp64] {what}: max err {float(np.nanmax(err)) if err.size else 0.0:.3e}, max err/bound {ratio:.3f}")
-    if not ok.all():
-        i = np.unravel_index(np.argmax(np.where(ok, 0.0, np.where(np.isfinite(err), err - tol, np.inf))), err.shape)
-        raise AssertionError(f"{what}: {int((~ok).sum())} of {ok.size} elements outside the bound; worst at {tuple(int(v) for v in i)}: "
-                             f"got {got[i]!r}, want {want[i]!r}, |diff| {err[i]:.3e}, bound {tol[i]:.3e}")
 
 
 # ====================================================================================================== 1. ddp_segment_reduce
