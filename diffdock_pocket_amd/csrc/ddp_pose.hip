@@ -12,6 +12,7 @@
 
 #include "ddp_hip.h"
 #include "ddp_internal.h"
+#include "ddp_horn.h"
 
 #define DDP_POSE_THREADS 128
 
@@ -47,43 +48,6 @@ __device__ __forceinline__ void block_sum3(float& x, float& y, float& z, float* 
   }
   x = red[0]; y = red[DDP_POSE_THREADS]; z = red[2 * DDP_POSE_THREADS];
   __syncthreads();
-}
-
-// largest-eigenvalue eigenvector of the symmetric 4x4 matrix A (cyclic Jacobi, fp64)
-__device__ void max_eigvec4(double A[4][4], double q[4]) {
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0, diag = 0.0;
-    for (int p = 0; p < 4; ++p)
-      for (int r = 0; r < 4; ++r) (p == r ? diag : off) += A[p][r] * A[p][r];
-    if (off <= 1e-30 * diag || off == 0.0) break;
-    for (int p = 0; p < 3; ++p)
-      for (int r = p + 1; r < 4; ++r) {
-        if (fabs(A[p][r]) < 1e-300) continue;
-        const double theta = (A[r][r] - A[p][p]) / (2.0 * A[p][r]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {   // A <- A J
-          const double akp = A[k][p], akr = A[k][r];
-          A[k][p] = c * akp - s * akr;
-          A[k][r] = s * akp + c * akr;
-        }
-        for (int k = 0; k < 4; ++k) {   // A <- J^T A
-          const double apk = A[p][k], ark = A[r][k];
-          A[p][k] = c * apk - s * ark;
-          A[r][k] = s * apk + c * ark;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double vkp = V[k][p], vkr = V[k][r];
-          V[k][p] = c * vkp - s * vkr;
-          V[k][r] = s * vkp + c * vkr;
-        }
-      }
-  }
-  int best = 0;
-  for (int k = 1; k < 4; ++k)
-    if (A[k][k] > A[best][best]) best = k;
-  for (int k = 0; k < 4; ++k) q[k] = V[k][best];
 }
 
 __global__ __launch_bounds__(DDP_POSE_THREADS) void ddp_pose_update_kernel(const float* __restrict__ pos_in, int n_atoms,

@@ -133,6 +133,13 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     rank{k}_reverseprocess[_protein].pdb; the trajectories are also returned (`lig_traj`, `atom_traj`, ranked order).  With
     sample sharding the full atom poses and the trajectories are gathered with the ligand poses and rank 0 alone writes (with
     shard="complexes" each rank writes its own rows); a write failure skips the row on every rank."""
+    if sampler_cfg is not None and sampler_cfg.svgd_weight > 0:
+        # the samples of a complex interact: a row's sampler would raise inside the per-row try and the row would only be skipped
+        if shard == "samples" and world > 1:
+            raise ValueError("svgd_weight > 0 needs all samples of a complex on one device: samples cannot be sharded over ranks "
+                             "(use shard='complexes')")
+        if samples_per_complex < 3:
+            raise ValueError("svgd_weight > 0 needs at least 3 samples per complex")
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
             shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation)
@@ -329,6 +336,11 @@ def _parser():
         p.add_argument(f"--temp_sampling_{name}", type=float, default=TEMP_SAMPLING[k])
         p.add_argument(f"--temp_psi_{name}", type=float, default=TEMP_PSI[k])
     p.add_argument("--temp_sigma_data", type=float, default=TEMP_SIGMA_DATA)
+    p.add_argument("--svgd_weight", type=float, default=0.0, help="> 0: add the SVGD particle-interaction term (rigid receptor, >= 3 samples)")
+    p.add_argument("--svgd_repulsive_weight", type=float, default=1.0)
+    p.add_argument("--svgd_only", action="store_true", default=False, help="the SVGD term replaces the SDE / ODE update")
+    p.add_argument("--svgd_rot_rel_weight", type=float, default=1.0)
+    p.add_argument("--svgd_tor_rel_weight", type=float, default=1.0)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--esm_embeddings", type=str, default=None,
                    help="directory of <complex_name>.pt / .npy ESM rows, or one .pt file holding {complex_name: rows}")
@@ -384,7 +396,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                         temp_sampling=[a.temp_sampling_tr, a.temp_sampling_rot, a.temp_sampling_tor, a.temp_sampling_sc_tor],
                         temp_psi=[a.temp_psi_tr, a.temp_psi_rot, a.temp_psi_tor, a.temp_psi_sc_tor], temp_sigma_data=a.temp_sigma_data,
                         no_final_step_noise=a.no_final_step_noise, no_random=a.no_random, ode=a.ode, flexible_sidechains=flexible,
-                        no_torsion=bool(getattr(margs, "no_torsion", False)), record_trajectory=a.save_visualisation)
+                        no_torsion=bool(getattr(margs, "no_torsion", False)), record_trajectory=a.save_visualisation,
+                        svgd_weight=a.svgd_weight, svgd_repulsive_weight=a.svgd_repulsive_weight, svgd_only=a.svgd_only,
+                        svgd_rot_rel_weight=a.svgd_rot_rel_weight, svgd_tor_rel_weight=a.svgd_tor_rel_weight)
+    if a.svgd_weight > 0 and (flexible or a.samples_per_complex < 3):
+        ap.error("--svgd_weight > 0 needs a rigid receptor (--rigid or a model without flexible side chains) and "
+                 "--samples_per_complex >= 3")
     esm = a.esm_embeddings
     if esm is not None and os.path.isfile(esm):
         esm = torch.load(esm, map_location="cpu", weights_only=False)

@@ -1,7 +1,8 @@
 """Reverse-diffusion sampling loop around the score model: the caller of the hot path.
 
 Counterpart of reference utils/sampling.py:16-60 (`randomize_position`) and :70-286 (`sampling`) for the default
-inference settings (SDE with low-temperature sampling, no SVGD, no confidence model), restructured for the
+inference settings (SDE with low-temperature sampling; the ODE form, the SVGD particle-interaction term of :197-242 - svgd.py,
+csrc/ddp_svgd.hip - and the confidence pass are switched on through SamplerConfig / Sampler.confidence), restructured for the
 MI355X: the N sample graphs of one complex are collated ONCE into a device-resident batch (the reference
 re-collates a python list on the CPU every step, utils/sampling.py:100,112-114) and the pose update
 (utils/diffusion_utils.py:37-70, utils/torsion.py:68-94,251-278, utils/geometry.py:72-86,209-243) is batched over
@@ -177,6 +178,13 @@ class SamplerConfig:
     hip_graph: bool = True     # on a HIP device: capture one denoising step (forward + SDE step + pose update) in a hipGraph
                                # after two ordinary steps and replay it from then on (no host work per launch)
     record_trajectory: bool = False    # keep every step's poses (Sampler.lig_traj / atom_traj: the --save_visualisation frames)
+    # SVGD particle interaction (reference utils/sampling.py:73,197-242; svgd.py): > 0 adds svgd_weight * total_X to every component's
+    # update (svgd_only: replaces the SDE / ODE update by it).  Needs all >= 3 samples of the complex in ONE sampler, rigid receptor.
+    svgd_weight: float = 0.0
+    svgd_repulsive_weight: float = 1.0
+    svgd_only: bool = False
+    svgd_rot_rel_weight: float = 1.0
+    svgd_tor_rel_weight: float = 1.0
 
 
 class Sampler:
@@ -223,6 +231,44 @@ class Sampler:
             self._init_trajectory()
         if self.on_hip:
             self._init_step_buffers()
+        self.svgd = cfg.svgd_weight > 0
+        if self.svgd:
+            self._init_svgd(g)
+
+    # -- SVGD particle interaction (SamplerConfig.svgd_weight > 0; svgd.py) ------------------------------------------
+    def _init_svgd(self, g):
+        """The dihedral table (host, once) and, on a HIP device, the workspace of the three ddp_svgd_* passes.  With no_torsion the
+        torsion angles take no part in the distance (the reference cannot run that combination)."""
+        from . import svgd
+        cfg = self.cfg
+        if self.n != self.n_total:
+            raise ValueError(f"svgd_weight > 0: the samples of a complex interact, so all {self.n_total} of them have to be in one "
+                             f"sampler on one device (this one holds {self.n}: no sample_slice, no PipelinedSampler, no sample sharding)")
+        if self.n_total < 3:
+            raise ValueError("svgd_weight > 0 needs at least 3 samples (the median of a two-sample row is its zero diagonal)")
+        if self.has_flex:
+            raise NotImplementedError("SVGD is not implemented for flexible side chains (reference utils/sampling.py:210-211)")
+        self.svgd_dih = None
+        if not cfg.no_torsion and self.T > 0:
+            self.svgd_dih = svgd.dihedrals(g["ligand", "ligand"].edge_index, g["ligand"].edge_mask)
+        if self.on_hip:
+            self.svgd_ws = svgd.SvgdWorkspace(self.n, self.n_l, self.svgd_dih, self.device, weight=cfg.svgd_weight,
+                                              w_rep=cfg.svgd_repulsive_weight, w_rot=cfg.svgd_rot_rel_weight,
+                                              w_tor=cfg.svgd_tor_rel_weight, svgd_only=cfg.svgd_only)
+
+    def _svgd_gdt(self, t_idx, schedule):
+        """[g_tr^2 dt, g_rot^2 dt, g_tor^2 dt] of a step: the diffusion coefficients of _step_coefficients, without the
+        low-temperature and ODE factors (reference utils/sampling.py:215,219,225)."""
+        sg, steps = self.cfg.sigma, len(schedule)
+        t = float(schedule[t_idx])
+        dt = float(schedule[t_idx] - schedule[t_idx + 1]) if t_idx < steps - 1 else float(schedule[t_idx])
+        out = []
+        for lo, hi, two in ((sg.tr_sigma_min, sg.tr_sigma_max, True), (sg.rot_sigma_min, sg.rot_sigma_max, False),
+                            (sg.tor_sigma_min, sg.tor_sigma_max, True)):
+            sigma = lo ** (1 - t) * hi ** t
+            g = sigma * math.sqrt(2 * math.log(hi / lo)) if two else 2 * sigma * math.sqrt(math.log(hi / lo))
+            out.append(g ** 2 * dt)
+        return out
 
     # -- reverse-process trajectory (SamplerConfig.record_trajectory) ----------------------------------------------
     def _init_trajectory(self):
@@ -358,6 +404,8 @@ class Sampler:
         host[1:8] = 0.0
         if self.lig_traj is not None:
             host[1] = t_idx + 1            # the trajectory slot of ddp_traj_record (exact as a float)
+        if self.svgd:
+            host[2:5] = torch.tensor(self._svgd_gdt(t_idx, schedule), dtype=torch.float64).float()     # read by ddp_svgd_rows
         host[8:16] = torch.tensor(coef, dtype=torch.float64).float()
         o = self._off
 
@@ -413,6 +461,9 @@ class Sampler:
             a.score[k], a.z[k], a.out[k], a.n[k] = sc.data_ptr(), (0 if cfg.ode else zz.data_ptr()), out.data_ptr(), out.numel()
         st = torch._C._cuda_getCurrentRawStream(self.lig_pos.device.index)
         L.check(lib.ddp_sde_update(self.coef.data_ptr(), C.byref(a), st), "ddp_sde_update")
+        if self.svgd:      # on the poses the scores were computed for, into the updates just written
+            self.svgd_ws.launch(self.lig_pos, (keep[0], keep[1], keep[2] if use_tor else None),
+                                (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[2:5])
         if self.has_flex:
             L.check(lib.ddp_sidechain_update(self.atom_pos.data_ptr(), self.n, self.n_a, self.upd["sc"].data_ptr(), self.S,
                                              self.sc_edge_i32.data_ptr(), self.sc_sub_i32.data_ptr(), self.sc_map_i32.data_ptr(),
@@ -631,6 +682,15 @@ class Sampler:
                 self.atom_pos = apply_sidechain_torsions_hip(self.atom_pos, self.sc_edge_i32, self.sc_sub_i32, self.sc_map_i32, sc_p)
             else:
                 self.atom_pos = apply_sidechain_torsions(self.atom_pos, self.sc_edge_idx, self.sc_sub, self.sc_map, sc_p)
+        if self.svgd:
+            from . import svgd
+            gdt = self._svgd_gdt(t_idx, schedule)
+            tot = svgd.totals(self.lig_pos, self.svgd_dih, tr_score, rot_score, tor_score if tor_p is not None else None, gdt,
+                              cfg.svgd_repulsive_weight, cfg.svgd_rot_rel_weight, cfg.svgd_tor_rel_weight)
+            tr_p = cfg.svgd_weight * tot[0] + (0 if cfg.svgd_only else tr_p)
+            rot_p = cfg.svgd_weight * tot[1] + (0 if cfg.svgd_only else rot_p)
+            if tor_p is not None:
+                tor_p = cfg.svgd_weight * tot[2] + (0 if cfg.svgd_only else tor_p)
         if self.lig_pos.is_cuda:   # one HIP launch; the PyTorch form below is the same arithmetic (CPU tests)
             self.lig_pos = modify_conformer_hip(self.lig_pos, tr_p, rot_p, tor_p, self.bonds_i32, self.mask_u8)
         else:
@@ -744,6 +804,9 @@ class PipelinedSampler:
                  sample_slice: Optional[slice] = None, ways: int = 2):
         if cfg.record_trajectory:
             raise NotImplementedError("PipelinedSampler does not record trajectories: use Sampler(record_trajectory=True)")
+        if cfg.svgd_weight > 0:
+            raise ValueError("svgd_weight > 0: the samples of a complex interact, so all of them have to be in one Sampler; a "
+                             "PipelinedSampler splits them into groups")
         self.model, self.device = model, device
         lo, hi, _ = (sample_slice or slice(0, n_total)).indices(n_total)
         ways = max(1, min(ways, hi - lo))

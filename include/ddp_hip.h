@@ -715,9 +715,49 @@ int ddp_pose_contacts(const float* lig, int n_samples, int n, const float* lig_r
 int ddp_traj_record(const float* lig_pos, int n, int n_lig, float* lig_traj, const float* atom_pos, int n_atoms, const int32_t* moving,
                     int n_moving, float* atom_traj, int n_slots, const float* slot, void* stream);
 
+/* ---- SVGD particle-interaction term of the reverse-diffusion step (csrc/ddp_svgd.hip; host side diffdock_pocket_amd/svgd.py and
+ * sampler.py; reference utils/sampling.py:197-242).  One complex, n >= 3 samples with poses pos [n][n_lig][3] BEFORE the step's update,
+ * n_lig >= 4, n_tor >= 0 rotatable bonds with dihedrals [n_tor][4] = (c, a, b, d) atom indices (utils/torsion.py:96-113).
+ *   ddp_svgd_tau:   tau[s][t] = acos(clamp(cos, +-(1 - 1e-5))) sign((u x v) . (b - a)), u / v = the parts of d - a / c - a normal to
+ *                   b - a, cos = u.v / (|u| |v|)                                                                  (torsion.py:120-135)
+ *   ddp_svgd_pairs: for i < j   tr_diff[i][j] = centroid_j - centroid_i,  rot_diff[i][j] = axis-angle vector of the proper Kabsch
+ *                   rotation of pose i onto pose j in the convention of geometry.py:100-206 (the quaternion candidate of the largest
+ *                   component, sign not standardised, angle = 2 atan2(|xyz|, w): the vector may be longer than pi); [j][i] = -[i][j],
+ *                   diagonal 0.  tor_diff[i][j][t] = fmod(tau_i - tau_j + 3 pi, 2 pi) - pi for every ordered pair.
+ *                   dist[i][j] = |tr_diff|^2 + w_rot |rot_diff|^2 + w_tor sum_t tor_diff^2.
+ *   ddp_svgd_rows:  med_i = lower median of dist[i][:] (rank (n - 1) / 2 of the n entries, diagonal included),
+ *                   h_i = w_rep med_i / max(ln n, 1),  k[i][j] = exp(-dist[i][j] / h_i),  and for X in {tr, rot, tor} (w_X = 1, w_rot, w_tor)
+ *                     total_X[i] = gdt[X] ( sum_j k[i][j] score_X[j] + sum_j (2 / h_i) w_X X_diff[i][j] k[i][j] ) / n     (j ascending)
+ *                     upd_X[i]   = (svgd_only ? 0 : upd_X[i]) + weight total_X[i]
+ *                   gdt = [g_tr^2 dt, g_rot^2 dt, g_tor^2 dt] in DEVICE memory (the sampler's step parameter block).  h_i = 0 (half of
+ *                   the poses coincide) is not special-cased.
+ * Called in this order on one stream; tau (double [n][n_tor]), tr_diff / rot_diff (float [n][n][3]), tor_diff (float [n][n][n_tor]) and
+ * dist (double [n][n]) are the workspace the passes hand on.  score / upd: [n][3], [n][3], [n][n_tor].  n_tor = 0: dihedrals, tau,
+ * tor_diff, score[2], upd[2] may be NULL and ddp_svgd_tau launches nothing.  Arithmetic in fp64, no atomics: results do not depend on how
+ * the launches are scheduled.  n < 3, n_lig < 4: DDP_EINVAL; n > 2048: DDP_ELIMIT.  Atom indices of `dihedrals` are not checked on the
+ * device: the host validates them. */
+typedef struct {
+  const float* pos;
+  int32_t n, n_lig, n_tor;
+  const int32_t* dihedrals;
+  const float* score[3];
+  float* upd[3];
+  const float* gdt;
+  float weight, w_rep, w_rot, w_tor;
+  int32_t svgd_only;
+  double* tau;
+  float* tr_diff;
+  float* rot_diff;
+  float* tor_diff;
+  double* dist;
+} ddp_svgd_args_t;
+int ddp_svgd_tau(const ddp_svgd_args_t* args, void* stream);
+int ddp_svgd_pairs(const ddp_svgd_args_t* args, void* stream);
+int ddp_svgd_rows(const ddp_svgd_args_t* args, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
-/* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, csrc/ddp_internal.h, include/ddp_hip.h) the library was built from */
+/* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, the csrc headers, include/ddp_hip.h) the library was built from */
 const char* ddp_source_hash(void);
 
 #ifdef __cplusplus
