@@ -5,7 +5,7 @@ from .batch import HeteroBatch, Store, collate, set_time  # noqa: F401
 from .diffusion import SigmaRanges, get_t_schedule, get_timestep_embedding, sinusoidal_embedding, t_to_sigma  # noqa: F401
 
 __all__ = ["HeteroBatch", "Store", "collate", "set_time", "SigmaRanges", "get_t_schedule", "get_timestep_embedding",
-           "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "summarize"]
+           "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize"]
 
 
 def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ctypes binding
@@ -15,7 +15,7 @@ def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ct
     if name == "get_model":
         from .factory import get_model
         return get_model
-    if name in ("PoseEvaluator", "summarize"):
+    if name in ("PoseEvaluator", "PoseClusters", "summarize"):
         from . import evaluation
         return getattr(evaluation, name)
     raise AttributeError(name)

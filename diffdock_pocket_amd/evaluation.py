@@ -12,7 +12,11 @@
 the crystal ligand is for PDBBind) and scores the [S, n, 3] poses of a Sampler.  Device tensors go through the HIP kernels of
 csrc/ddp_eval.hip (two launches, one workgroup per sample); CPU tensors through `_rmsd_torch` / `_contacts_torch`, the same
 arithmetic in PyTorch (the CPU tests and the csv driver with a stub model).  `summarize` turns the ranked metrics of many complexes
-into the reference's percentages."""
+into the reference's percentages.
+
+Without a known pose: `PoseEvaluator.pairwise_rmsd` is the same symmetry-corrected RMSD between every pair of samples
+(ddp_pose_pairwise_rmsd / `_pairwise_torch`) and `PoseEvaluator.cluster` groups the samples into binding modes by greedy leader
+clustering in ranked order (ddp_pose_cluster / `_cluster_torch`) -> `PoseClusters`."""
 from __future__ import annotations
 
 import json
@@ -159,6 +163,37 @@ def _rmsd_torch(pred, ref, perms_pn, sel=None):
     return torch.sqrt(best_v / n).float(), best_p.to(torch.int32)
 
 
+def _pairwise_torch(pos, perms_pn, sel=None):
+    """[S, S]: for i < j, _rmsd_torch of pose j against ref = the selected rows of pose i (the arithmetic and chunking of
+    _rmsd_torch, one call per i); the lower triangle is a copy of the upper one, the diagonal is 0."""
+    x = pos if sel is None else pos[:, sel]
+    S = x.shape[0]
+    dist = torch.zeros(S, S, dtype=torch.float32)
+    for i in range(S - 1):
+        dist[i, i + 1:] = _rmsd_torch(x[i + 1:], x[i], perms_pn)[0]
+    return torch.triu(dist, 1) + torch.triu(dist, 1).T
+
+
+def _cluster_torch(dist, order=None, cutoff=2.0):
+    """Greedy leader clustering, the rule of ddp_pose_cluster on the host: (labels [S], reps [S], sizes [S], count), int32, reps and
+    sizes -1 past `count`.  Walking `order` (None: 0 .. S-1), a pose without a label opens the next cluster and takes every pose that
+    has no label yet and dist[rep, t] < cutoff (strict; NaN never joins), itself included."""
+    S = dist.shape[0]
+    d = dist.float()
+    cut = torch.tensor(float(cutoff), dtype=torch.float32)
+    labels, reps, sizes = (torch.full((S,), -1, dtype=torch.int32) for _ in range(3))
+    count = 0
+    for o in (range(S) if order is None else [int(v) for v in order]):
+        if o < 0 or o >= S or labels[o] >= 0:
+            continue
+        join = (labels < 0) & (d[o] < cut)
+        join[o] = True
+        labels[join] = count
+        reps[count], sizes[count] = o, int(join.sum())
+        count += 1
+    return labels, reps, sizes, count
+
+
 def _contacts_torch(lig, lig_r, rec, rec_r, ref_c, overlap=OVERLAP_DISTANCE):
     """[S, 4] = clashes, min_cross, min_self, centroid (the arithmetic of ddp_pose_contacts: fp32 squared distances)."""
     S, n = lig.shape[0], lig.shape[1]
@@ -208,6 +243,32 @@ class PoseMetrics:
 
     def index(self, order) -> "PoseMetrics":
         return self._map(lambda t: t[order.to(t.device)])
+
+
+@dataclass
+class PoseClusters:
+    """Binding modes of S poses (PoseEvaluator.cluster), in the order of the poses handed in.  Mode c is led by its representative,
+    the best-ranked pose that no earlier mode took, and holds every later-ranked free pose closer to it than the cutoff: modes are
+    numbered by the rank of their representative, mode 0 holds the top-ranked pose."""
+    dist: torch.Tensor                     # [S, S] symmetry-corrected RMSD of every pair (symmetric bit for bit, zero diagonal)
+    labels: torch.Tensor                   # [S] int32 mode of each pose
+    representatives: torch.Tensor          # [S] int32 pose index leading each mode, -1 past the last mode
+    sizes: torch.Tensor                    # [S] int32 members of each mode, -1 past the last mode
+    rmsd_to_representative: torch.Tensor   # [S] dist[representative of the pose's mode, pose]
+    symmetry_corrected: bool = True
+
+    def cpu(self) -> "PoseClusters":
+        return PoseClusters(**{f.name: (getattr(self, f.name).cpu() if isinstance(getattr(self, f.name), torch.Tensor)
+                                        else getattr(self, f.name)) for f in fields(self)})
+
+    @property
+    def n_modes(self) -> int:
+        return int((self.sizes >= 0).sum())
+
+    def by_size(self) -> List[int]:
+        """Mode indices, the largest first (ties: the lower index, i.e. the better-ranked representative)."""
+        sizes = self.sizes.cpu().tolist()[: self.n_modes]
+        return sorted(range(len(sizes)), key=lambda c: (-sizes[c], c))
 
 
 class PoseEvaluator:
@@ -317,6 +378,46 @@ class PoseEvaluator:
                 sc, _ = LA.pose_rmsd(apos, t["sc_ref"], t["sc_ident"], sel=t["sc_rows"])
             return PoseMetrics(rmsd, plain, best, c[:, 3].contiguous(), c[:, 1].contiguous(), c[:, 2].contiguous(), c[:, 0].to(torch.int32),
                                sc, self.symmetry_corrected)
+
+    def _check_lig(self, lig_pos):
+        if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
+            raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")
+        if lig_pos.is_cuda and (self.device.type != "cuda" or lig_pos.device != self.device):
+            raise ValueError(f"poses on {lig_pos.device}, evaluator built for {self.device}")
+
+    def pairwise_rmsd(self, lig_pos: torch.Tensor) -> torch.Tensor:
+        """lig_pos [S, n, 3] -> [S, S] symmetry-corrected RMSD of every pair of poses (no centring, no alignment, the minimum over
+        the automorphisms - the identity alone when their search overflowed), on the poses' device: ddp_pose_pairwise_rmsd for
+        device tensors, `_pairwise_torch` for CPU tensors."""
+        self._check_lig(lig_pos)
+        if lig_pos.is_cuda:
+            from . import launch as LA
+            with torch.cuda.device(lig_pos.device):
+                return LA.pose_pairwise_rmsd(lig_pos.float().contiguous(), self._dev["perms_t"])
+        return _pairwise_torch(lig_pos.float(), self._cpu["perms"])
+
+    def cluster(self, lig_pos: torch.Tensor, confidence: Optional[torch.Tensor] = None, cutoff: float = 2.0) -> PoseClusters:
+        """Binding modes of the poses: greedy leader clustering on `pairwise_rmsd`, walking the poses by descending confidence ([S],
+        or the first column of [S, k]; None: in the order given).  Results on the poses' device."""
+        dist = self.pairwise_rmsd(lig_pos)
+        S = dist.shape[0]
+        order = None
+        if confidence is not None:
+            key = confidence[:, 0] if confidence.dim() == 2 else confidence
+            if key.shape != (S,):
+                raise ValueError(f"confidence: expected [{S}] or [{S}, k], got {tuple(confidence.shape)}")
+            order = torch.argsort(key.to(dist.device), descending=True).to(torch.int32)
+        if dist.is_cuda:
+            from . import launch as LA
+            with torch.cuda.device(dist.device):
+                labels, reps, sizes, _ = LA.pose_cluster(dist, order, cutoff)
+        else:
+            labels, reps, sizes, _ = _cluster_torch(dist, order, cutoff)
+        has = labels >= 0
+        rep_of = reps.long()[labels.long().clamp(min=0)].clamp(min=0)
+        to_rep = torch.where(has, dist[rep_of, torch.arange(S, device=dist.device)], torch.full_like(dist[:, 0], float("nan"))) \
+            if S else dist.new_empty(0)
+        return PoseClusters(dist, labels, reps, sizes, to_rep, self.symmetry_corrected)
 
 
 # ---------------------------------------------------------------------------------------------- summary over complexes

@@ -32,7 +32,7 @@ import torch
 from . import inputs as I
 from . import outputs as O
 from .diffusion import get_t_schedule
-from .evaluation import PoseEvaluator, PoseMetrics  # noqa: F401
+from .evaluation import PoseClusters, PoseEvaluator, PoseMetrics  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 
 
@@ -48,6 +48,7 @@ class ComplexResult:
     files: List[str] = field(default_factory=list)  # run_csv(out_dir=...): the paths written for this row
     lig_traj: Optional[torch.Tensor] = None        # save_visualisation: [N, steps + 1, n_lig, 3] reverse process, ranked order
     atom_traj: Optional[torch.Tensor] = None       # save_visualisation, flexible row: [N, steps + 1, n_moving, 3], ranked order
+    clusters: Optional["PoseClusters"] = None      # run_csv(cluster_rmsd=X): evaluation.PoseClusters of the ranked poses (binding modes)
 
 
 def _none(v):
@@ -111,7 +112,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             esm_embeddings=None, root: str = "", seed: int = 0, rank: int = 0, world: int = 1, shard: str = "samples",
             dist=None, sampler_cfg: Optional[SamplerConfig] = None, graph_kwargs: Optional[Dict] = None,
             allow_zero_esm: bool = False, evaluate: bool = False, out_dir: Optional[str] = None,
-            save_visualisation: bool = False) -> List[ComplexResult]:
+            save_visualisation: bool = False, cluster_rmsd: Optional[float] = None) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -132,7 +133,12 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     `files`; save_visualisation=True records the reverse process on the device (SamplerConfig.record_trajectory) and adds
     rank{k}_reverseprocess[_protein].pdb; the trajectories are also returned (`lig_traj`, `atom_traj`, ranked order).  With
     sample sharding the full atom poses and the trajectories are gathered with the ligand poses and rank 0 alone writes (with
-    shard="complexes" each rank writes its own rows); a write failure skips the row on every rank."""
+    shard="complexes" each rank writes its own rows); a write failure skips the row on every rank.
+
+    cluster_rmsd=X: every processed row also gets `clusters` (evaluation.PoseEvaluator.cluster: the symmetry-corrected RMSD of every
+    pair of the gathered poses and their greedy grouping into binding modes at cutoff X, in ranked order: mode 0 holds rank 1), and
+    with out_dir the complex directory also gets modes.csv (outputs.write_modes_csv).  Needs no known pose.  A failure skips the row
+    like a failure of the evaluation.  None: nothing is computed or written."""
     if sampler_cfg is not None and sampler_cfg.svgd_weight > 0:
         # the samples of a complex interact: a row's sampler would raise inside the per-row try and the row would only be skipped
         if shard == "samples" and world > 1:
@@ -142,7 +148,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             raise ValueError("svgd_weight > 0 needs at least 3 samples per complex")
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
-            shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation)
+            shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(*args)
@@ -159,7 +165,7 @@ def _all_ok(dist, ok: bool, device) -> bool:
 
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
              world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
-             save_visualisation=False) -> List[ComplexResult]:
+             save_visualisation=False, cluster_rmsd=None) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if shard not in ("samples", "complexes"):
         raise ValueError(shard)
@@ -252,6 +258,18 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 res.ligand_pos = res.confidence = res.order = None
                 continue
             res.metrics = metrics
+        if cluster_rmsd is not None:
+            clusters = None
+            try:
+                clusters = PoseEvaluator(g, device).cluster(lig[order], None, cluster_rmsd).cpu()
+            except Exception as e:      # noqa: BLE001
+                res.skipped = f"clustering: {type(e).__name__}: {e}"
+            if split and not _all_ok(dist, clusters is not None, device):
+                res.skipped = res.skipped or "skipped: clustering failed on another rank"
+            if res.skipped is not None:
+                res.ligand_pos = res.confidence = res.order = res.metrics = None
+                continue
+            res.clusters = clusters
         if save_visualisation:
             res.lig_traj = ltraj[order].cpu()
             res.atom_traj = atraj[order].cpu() if atraj is not None else None
@@ -267,7 +285,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 res.skipped = res.skipped or "skipped: writing failed on rank 0"
                 ok = False
             if not ok:
-                res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = None
+                res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = res.clusters = None
                 res.files = []
     return out
 
@@ -281,7 +299,7 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
         with open(os.path.join(root, row["experimental_protein"])) as f:
             pdb_text = f.read()
     return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
-                           apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs)
+                           apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order)
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -341,6 +359,8 @@ def _parser():
     p.add_argument("--svgd_only", action="store_true", default=False, help="the SVGD term replaces the SDE / ODE update")
     p.add_argument("--svgd_rot_rel_weight", type=float, default=1.0)
     p.add_argument("--svgd_tor_rel_weight", type=float, default=1.0)
+    p.add_argument("--cluster_rmsd", type=float, default=None,
+                   help="group the ranked poses into binding modes at this symmetry-corrected RMSD cutoff and write modes.csv (default: off)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--esm_embeddings", type=str, default=None,
                    help="directory of <complex_name>.pt / .npy ESM rows, or one .pt file holding {complex_name: rows}")
@@ -429,7 +449,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             csv_path = rigid_csv
         res = run_csv(csv_path, model, device, confidence_model=conf_model, samples_per_complex=a.samples_per_complex,
                       inference_steps=a.inference_steps, esm_embeddings=esm, seed=a.seed, sampler_cfg=cfg, graph_kwargs=graph_kwargs,
-                      allow_zero_esm=a.allow_zero_esm, out_dir=a.out_dir, save_visualisation=a.save_visualisation)
+                      allow_zero_esm=a.allow_zero_esm, out_dir=a.out_dir, save_visualisation=a.save_visualisation,
+                      cluster_rmsd=a.cluster_rmsd)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

@@ -651,3 +651,57 @@ def pose_contacts(lig, lig_radii, rec, rec_radii, ref_centroid, overlap=0.4, out
                                        rec_radii.data_ptr(), float(overlap), ref_centroid.data_ptr(), out.data_ptr(), stream()),
             "ddp_pose_contacts")
     return out
+
+
+def pairwise_tile(n: int) -> int:
+    """Poses per tile of ddp_pose_pairwise_rmsd at n atoms (csrc/ddp_eval.hip, pairwise_tile)."""
+    return 8 if n <= 256 else 4 if n <= 512 else 2
+
+
+def pose_pairwise_rmsd(pos, perms_t, sel=None, out=None):
+    """ddp_pose_pairwise_rmsd: pos [S, rows, 3] fp32, perms_t int32 atom-major [n, P], sel int32 [n] rows of pos (None: rows 0 .. n-1).
+    Returns dist [S, S] fp32: for i < j what pose_rmsd(pos[j:j+1], pos[i, sel], perms_t, sel) gives, mirrored, zero diagonal."""
+    dev = pos.device
+    for t, dt, w in ((pos, torch.float32, "pos"), (perms_t, torch.int32, "perms_t")):
+        _eval_arg(t, dt, dev, f"pose_pairwise_rmsd {w}")
+    if pos.dim() != 3 or pos.shape[2] != 3 or perms_t.dim() != 2:
+        raise L.DdpError("pose_pairwise_rmsd: pos [S, rows, 3], perms_t [n, P]")
+    S, n, P = pos.shape[0], perms_t.shape[0], perms_t.shape[1]
+    if sel is not None:
+        _eval_arg(sel, torch.int32, dev, "pose_pairwise_rmsd sel")
+        if sel.shape != (n,):
+            raise L.DdpError("pose_pairwise_rmsd: sel must have one entry per perms_t row")
+    elif n > pos.shape[1]:
+        raise L.DdpError("pose_pairwise_rmsd: more perms_t rows than pos rows")
+    if out is None:
+        out = torch.empty(S, S, dtype=torch.float32, device=dev)
+    else:
+        _eval_arg(out, torch.float32, dev, "pose_pairwise_rmsd out")
+        if out.shape != (S, S):
+            raise L.DdpError("pose_pairwise_rmsd: out [S, S]")
+    if S == 0:
+        return out
+    L.check(L.load().ddp_pose_pairwise_rmsd(pos.data_ptr(), S, pos.shape[1] * 3, _p(sel), n, perms_t.data_ptr(), P, out.data_ptr(),
+                                            stream()), "ddp_pose_pairwise_rmsd")
+    return out
+
+
+def pose_cluster(dist, order=None, cutoff=2.0):
+    """ddp_pose_cluster: dist [S, S] fp32, order int32 [S] pose indices best first (None: 0 .. S-1).  Returns (labels [S], reps [S],
+    sizes [S], n_clusters [1]), int32 on dist's device; reps and sizes are -1 past the n_clusters clusters found."""
+    dev = dist.device
+    _eval_arg(dist, torch.float32, dev, "pose_cluster dist")
+    if dist.dim() != 2 or dist.shape[0] != dist.shape[1]:
+        raise L.DdpError("pose_cluster: dist [S, S]")
+    S = dist.shape[0]
+    if order is not None:
+        _eval_arg(order, torch.int32, dev, "pose_cluster order")
+        if order.shape != (S,):
+            raise L.DdpError("pose_cluster: order must have one entry per pose")
+    labels, reps, sizes = (torch.empty(S, dtype=torch.int32, device=dev) for _ in range(3))
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    if S == 0:
+        return labels, reps, sizes, count
+    L.check(L.load().ddp_pose_cluster(dist.data_ptr(), S, _p(order), float(cutoff), labels.data_ptr(), reps.data_ptr(), sizes.data_ptr(),
+                                      count.data_ptr(), stream()), "ddp_pose_cluster")
+    return labels, reps, sizes, count

@@ -198,6 +198,32 @@ def moving_atoms(graph) -> torch.Tensor:
     return torch.unique(torch.as_tensor(graph["flexResidues"].subcomponents).cpu())
 
 
+# ---------------------------------------------------------------------------------------------- binding modes
+MODES_COLUMNS = ["rank", "sample", "confidence", "mode", "is_representative", "mode_size", "rmsd_to_representative"]
+
+
+def write_modes_csv(path: str, clusters, confidence=None, order=None) -> str:
+    """modes.csv of one complex: one row per pose in RANKED order (evaluation.PoseClusters of the ranked poses).  rank counts from 1,
+    sample is the pose's index before ranking (order [N]; None: rank - 1), confidence is empty without a confidence model; mode counts
+    from 0 in the rank order of the representatives, is_representative is 0 / 1."""
+    import csv
+    c = clusters.cpu()
+    labels, reps, sizes = c.labels.tolist(), c.representatives.tolist(), c.sizes.tolist()
+    to_rep = c.rmsd_to_representative.tolist()
+    conf = None
+    if confidence is not None:
+        conf = _np(confidence)
+        conf = conf[:, 0] if conf.ndim == 2 else conf
+    sample = list(range(len(labels))) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(MODES_COLUMNS)
+        for k, m in enumerate(labels):
+            w.writerow([k + 1, sample[k], "" if conf is None else f"{float(conf[k]):.4f}", m, int(m >= 0 and reps[m] == k),
+                        sizes[m] if m >= 0 else 0, f"{to_rep[k]:.4f}"])
+    return path
+
+
 # ---------------------------------------------------------------------------------------------- one complex
 def complex_dir(out_dir: str, index: int, name: str) -> str:
     """reference inference.py:136."""
@@ -205,7 +231,7 @@ def complex_dir(out_dir: str, index: int, name: str) -> str:
 
 
 def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
-                  lig_traj=None, atom_traj=None, remove_hs: bool = True) -> List[str]:
+                  lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None) -> List[str]:
     """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
     ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
     lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
@@ -213,7 +239,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     With a confidence model: rank1.sdf and rank{k}_confidence{c:.2f}.sdf; without one rank{k}.sdf (the reference fails there).
     Flexible: rank1_protein.pdb and rank{k}_confidence{c:.2f}_protein.pdb (rank{k}_protein.pdb).  Trajectories:
     rank{k}_reverseprocess.pdb and rank{k}_reverseprocess_protein.pdb, each of the ranked sample itself (the reference indexes the
-    side-chain trajectories by rank instead of by sample, inference.py:276-279)."""
+    side-chain trajectories by rank instead of by sample, inference.py:276-279).
+    clusters (evaluation.PoseClusters of the ranked poses; order [N]: the sample index of each rank): also modes.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -250,4 +277,6 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
             text = receptor_pdb(pdb_text, graph.flex_atom_records, moving, frames, oc, remove_hs)
             with open(put(os.path.join(write_dir, f"rank{k + 1}_reverseprocess_protein.pdb")), "w") as f:
                 f.write(text)
+    if clusters is not None:
+        write_modes_csv(put(os.path.join(write_dir, "modes.csv")), clusters, confidence, order)
     return written

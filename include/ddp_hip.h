@@ -705,6 +705,31 @@ int ddp_pose_rmsd(const float* pred, int n_samples, int pred_stride, const int32
 int ddp_pose_contacts(const float* lig, int n_samples, int n, const float* lig_radii, const float* rec, int m, int rec_stride,
                       const float* rec_radii, float overlap, const float* ref_centroid, float* out, void* stream);
 
+/* ---- binding modes of a set of sampled poses (csrc/ddp_eval.hip; host side evaluation.PoseEvaluator.cluster).  No atomics: two
+ * launches give the same bits. */
+#define DDP_PAIRWISE_MAX_SAMPLES 32768   /* poses of one ddp_pose_pairwise_rmsd call (its grid; dist has n_samples^2 entries) */
+
+/* ddp_pose_pairwise_rmsd: the symmetry-corrected RMSD of every pair of poses, dist [n_samples][n_samples].  For i < j
+ *   dist[i][j] = min_p sqrt(sum_a |pos_j[sel[a]] - pos_i[sel[perms[a * n_perms + p]]]|^2 / n)
+ * which is, bit for bit, what ddp_pose_rmsd gives sample j with ref = the n selected rows of pose i (fp32 differences, squares summed
+ * in fp64 in increasing a, ties to the lowest p).  dist[j][i] is a copy of dist[i][j] (the other direction sums in another order and
+ * is not computed), dist[i][i] = 0.  pos, pos_stride, sel, perms as ddp_pose_rmsd.  A permutation with an entry outside [0, n) is not
+ * considered (none left: NaN); a sel row outside the sample's stride is never read and gives NaN for every pair (the stride and sel
+ * are the same for all samples).  A workgroup holds pose i and a tile of T later poses in LDS and reads each permutation entry once
+ * for the tile; T = 8 (n <= 256), 4 (n <= 512) or 2.  n > DDP_EVAL_MAX_ATOMS, n_samples > DDP_PAIRWISE_MAX_SAMPLES: DDP_ELIMIT.
+ * n_samples = 0: no-op. */
+int ddp_pose_pairwise_rmsd(const float* pos, int n_samples, int pos_stride, const int32_t* sel, int n, const int32_t* perms, int n_perms,
+                           float* dist, void* stream);
+
+/* ddp_pose_cluster: greedy leader clustering on dist [n_samples][n_samples] (one workgroup; n_samples > 1024: DDP_ELIMIT).  `order`
+ * [n_samples] lists pose indices best first (NULL: 0 .. n_samples-1).  Walking it, the first pose without a label opens cluster
+ * c = n_clusters++ and becomes reps[c]; it and every pose t that has no label yet and dist[reps[c]][t] < cutoff (strict; NaN never
+ * joins) get labels[t] = c; sizes[c] = the number of members.  Clusters are therefore numbered by the rank of their representative.
+ * labels, reps, sizes: [n_samples], n_clusters: one int; the unused tails of reps and sizes are -1, a pose that `order` never names
+ * keeps label -1, an `order` entry outside [0, n_samples) is skipped without a read. */
+int ddp_pose_cluster(const float* dist, int n_samples, const int32_t* order, float cutoff, int32_t* labels, int32_t* reps, int32_t* sizes,
+                     int32_t* n_clusters, void* stream);
+
 /* ---- reverse-process trajectory recording (csrc/ddp_traj.hip; host side diffdock_pocket_amd/sampler.py).
  * ddp_traj_record: k = (int)slot[0], read on the device (a captured launch serves every step: the sampler's step parameter block
  * holds t_idx + 1); a slot outside [0, n_slots) (or NaN) writes nothing.  Exact copies, sample-major:
