@@ -1,5 +1,5 @@
-// ddp_conv_common.h - what the conv kernels of ddp_conv.hip (32- / 64-edge workgroups) and ddp_conv_rows.hip (256-edge, row-stationary
-// workgroups) share: vector types, size classes, the fp16 hi/lo split of an operand, the launch descriptor, the workgroup -> tile
+// ddp_conv_common.h - what the conv kernels of ddp_conv.hip (32- / 64-edge workgroups) and of ddp_conv_rows.hip / ddp_conv_rows16.hip
+// (128-edge, row-stationary workgroups; what only those two share: ddp_conv_rows_common.h) share: vector types, size classes, the fp16 hi/lo split of an operand, the launch descriptor, the workgroup -> tile
 // map and the basis features of FasterTensorProduct (reference models/layers.py:40-53).
 #ifndef DDP_CONV_COMMON_H
 #define DDP_CONV_COMMON_H

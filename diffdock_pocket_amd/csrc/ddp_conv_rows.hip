@@ -31,43 +31,22 @@
 // Per 32 edges: 0.18 MB of weights + ~0.26 MB of G (whole runs: 2.5 per 32 edges at 3dpf) from L2 instead of 2.0 MB.
 // Summation order of a message element: G runs in edge order, then the stream tiles in feature order, then (blocks with several
 // features per tile) the lane groups in order: fixed, bitwise reproducible; within fp32 rounding of ddp_conv_messages.
+// What does not depend on the MFMA shape - the weight ring, the feature rows, G's byte layout, the host's launch plan - is shared with
+// the 16x16x32 form (ddp_conv_rows16.hip) through ddp_conv_rows_common.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #undef DDP_STAMPS   // (the in-kernel stamps of tools/stamp_conv.py belong to ddp_conv.hip)
-#include "ddp_conv_common.h"
+#include "ddp_conv_rows_common.h"
 
-#define ROWS_NW 4
-#define ROWS_NT 256
-#define ROWS_ET 128
-#define ROWS_FS 36     // floats per feature row F[u * C + c][edge]
 #ifndef DDP_ROWS_GRING1
 #define DDP_ROWS_GRING1 12
 #endif
 #ifndef DDP_ROWS_GRING3
 #define DDP_ROWS_GRING3 8
 #endif
-
-// Operand planes of this kernel ("unified" fp16 hi/lo planes, include/ddp_hip.h DDP_ROWS_S*): V = v * 2^s = hi + lo with hi = fp16(V),
-// lo = fp16(V - hi) at the SAME scale, so that the three split products hh wh + hh wl + hl wh land in ONE accumulator (the common form
-// v = hi + lo / 2048 of ddp_conv_common.h needs two and a multiply-add per element to join them: 32 registers of every tile product
-// here).  22 significant bits while lo is a normal fp16 number (|V| >= 0.125), an absolute 2^-25 / 2^s below; |V| <= 65504 or the
-// range flag is raised.  The accumulators carry 2^(sa + sb); the feature rows / harmonics they are multiplied with carry the inverse.
-#define ROWS_SX ((float)DDP_ROWS_SX)
-#define ROWS_SW ((float)DDP_ROWS_SW)
-#define ROWS_SH ((float)DDP_ROWS_SH)
-#define ROWS_SG ((float)DDP_ROWS_SG)
-__device__ __forceinline__ void rows_split(const f32x4 v, float scale, h4& hi, h4& lo, int32_t* flag) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float V = v[i] * scale;
-    h2_range_check(V, flag);
-    hi[i] = (_Float16)V;
-    lo[i] = (_Float16)(V - (float)hi[i]);
-  }
-}
 
 // Diagnostic build only (-DDDP_ROWS_STAMPS, tools/stamp_rows.py): lane 0 of every wave records s_memtime at the phase boundaries
 #ifdef DDP_ROWS_STAMPS
@@ -93,22 +72,6 @@ extern "C" int ddp_debug_read_rows_stamps(unsigned long long* host_dst, int n_wg
 #define RSTAMP(k) do {} while (0)
 #define RSTAMP_VAL(k, v) do {} while (0)
 #endif
-
-struct RowsLaunch {
-  ConvLaunch L;
-  int nts;         // stream tiles per conv (fc.0 tiles + fc.3 tiles of all segments)
-  int bias_bytes;  // LDS bytes of the bias table behind the ring
-  int priv_bytes;  // LDS bytes of a wave's private area
-  int aux_off;     // byte offset of the per-edge tables inside it
-};
-
-static_assert(sizeof(ConvLaunch) + 16 <= 4096, "the launch descriptor travels as a kernel argument");
-// per-edge tables of a wave (behind its feature rows)
-struct RowsAux {
-  float shT[4][32];   // harmonics, component-major: the "feature rows" of the factorised features
-  float sh[32][4];    // ... edge-major (build_features)
-  int src[32], pos[32], rid[32];
-};
 
 // out[c][i] += F[(u * C + c)][row_i] * acc[i], rows in the MFMA C/D layout: reg i <-> row (i & 3) + 8 (i >> 2) + 4 hh
 // (acc carries the operands' plane scales; the feature rows carry their inverse)
@@ -148,50 +111,6 @@ __device__ __forceinline__ void rows_apply_harmonics(const f32x16& tg, const flo
     }
 }
 
-// The weight stream: a tile travels as ROWS_NP pieces of NS / ROWS_NP k-steps (8 KiB at NS = 12), piece p of every tile through slot p of
-// a three-slot LDS ring.  One stream step j = ROWS_NP t + p: every wave's part of piece j has landed (the wave waits for its own LDS-DMA
-// copies of piece j - those of piece j + 1 stay in flight - then the barrier), nobody reads piece j - 1 any more, so piece j + 2 is
-// requested into its slot (global_load_lds_dwordx4: no staging registers; every wave moves 2 NS / (ROWS_NP ROWS_NW) fragments of 1 KiB,
-// lane-linear in LDS).  A copy has two piece products to land (one was not enough: ~1 k ticks of every 3.4 k-tick tile waited for it).
-#define ROWS_NP 3
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-// (the copies are BUFFER loads to LDS, not global_load_lds: hipcc books a global_load_lds as a flat access to both address spaces, and while
-// one is pending every wait for an ordinary load becomes vmcnt(0))
-typedef __amdgpu_buffer_rsrc_t RowsStream;
-__device__ __forceinline__ RowsStream rows_stream_of(const void* wsh, int nts, int tile_bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wsh), 0, nts * tile_bytes, 0x00020000);
-}
-template <int NS>
-__device__ __forceinline__ void rows_request_piece(f32x4* ring, RowsStream wsh, int jn, int npieces, int slot, int wave, int lane) {
-  constexpr int FPP = 2 * NS / ROWS_NP, FPW = FPP / ROWS_NW, PIECE_Q = FPP * 64;
-  static_assert(NS % ROWS_NP == 0 && FPP % ROWS_NW == 0, "every wave moves the same number of fragments per piece");
-  f32x4* nslot = ring + slot * PIECE_Q;
-  const int piece_off = min(jn, npieces - 1) * (PIECE_Q * 16);
-#pragma unroll
-  for (int f = 0; f < FPW; ++f)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(wsh, (lds_ptr_t)(nslot + (wave + ROWS_NW * f) * 64), 16, ((wave + ROWS_NW * f) * 64 + lane) * 16, piece_off, 0, 0);
-}
-template <int NS, int P>
-__device__ __forceinline__ void rows_stream_step(f32x4* ring, RowsStream wsh, int t, int nts, int wave, int lane) {
-  constexpr int FPW = 2 * NS / ROWS_NP / ROWS_NW;
-  // (hipcc does NOT wait for an LDS-DMA in front of a barrier: without this a wave can pass while its part of the piece is in flight.
-  // vmcnt counts in order: "at most FPW outstanding" = everything older than the copies of piece j + 1 has landed)
-  static_assert(FPW == 2 || FPW == 1, "the literals below");
-  if constexpr (FPW == 2)
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  // the bare barrier, not __syncthreads(): its workgroup fence makes hipcc wait vmcnt(0) whenever an ordinary load is in flight.  What
-  // the barrier orders here is LDS only: this wave's reads of the slot that is requested next (and, once, the bias table's writes) are
-  // complete (lgkmcnt(0)), the copies it waits for are counted above; the asm statements keep the compiler from moving LDS accesses
-  // across it.
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  rows_request_piece<NS>(ring, wsh, ROWS_NP * t + P + 2, ROWS_NP * nts, (P + 2) % ROWS_NP, wave, lane);
-}
-
 // acc += A(regs, k-steps KS0 ..) x B(piece in LDS): 3 split products per 16 k on ONE accumulator (unified planes), B fragments read one
 // k-step ahead (two or four k-steps ahead: the same step time, 18.15 ms)
 template <int NS, int KS0>
@@ -211,52 +130,9 @@ __device__ __forceinline__ void rows_piece_lds(const f32x4* slot, const h8 (&ah)
   }
 }
 
-// The basis features of a block's vector-input segments (DOT, VEC_S0, CROSS; build_features of ddp_conv_common.h restated for one wave):
-// ALL loads of a segment first - clamped, unconditional - then the arithmetic.  build_features issues one load per feature inside a
-// runtime loop, and with the stream's LDS-DMA copies in flight hipcc waits vmcnt(0) at every use: ~700 ticks per feature, 6 - 13 k per block.
-template <int MAXI>
-__device__ __forceinline__ void rows_build_features(const ddp_block_t& B, const ddp_conv_task_t& T, const RowsAux* aux, float* F, int lane) {
-  constexpr int FS = ROWS_FS;
-  const int e = lane & 31, half = lane >> 5;
-  const float* __restrict__ xrow = T.x_src + (size_t)aux->src[e] * T.ldx_src;
-  // (aux->sh carries 1 / (DDP_ROWS_SH DDP_ROWS_SW): the stream tiles' accumulators carry the planes' scales)
-  const float s0 = aux->sh[e][0], sx = aux->sh[e][1], sy = aux->sh[e][2], sz = aux->sh[e][3];
-  const float inv_sqrt3 = 0.57735026918962576f, inv_sqrt2 = 0.70710678118654752f;
-  int ubase = 0;
-  for (int si = 0; si < B.nseg; ++si) {
-    const int kind = B.seg[si].kind, off = B.seg[si].in_off, cnt = B.seg[si].count;
-    float ax[MAXI], ay[MAXI], az[MAXI];
-#pragma unroll
-    for (int i = 0; i < MAXI; ++i) {
-      const int ul = max(min(half + 2 * i, cnt - 1), 0);      // (an empty segment: the load stays inside the row, nothing is stored)
-      ax[i] = xrow[off + 3 * ul];
-      ay[i] = xrow[off + 3 * ul + 1];
-      az[i] = xrow[off + 3 * ul + 2];
-    }
-#pragma unroll
-    for (int i = 0; i < MAXI; ++i) {
-      const int ul = half + 2 * i;
-      if (ul < cnt) {
-        const int u = ubase + ul;
-        if (kind == DDP_F_DOT) {
-          F[u * FS + e] = (ax[i] * sx + ay[i] * sy + az[i] * sz) * inv_sqrt3;
-        } else if (kind == DDP_F_VEC_S0) {
-          F[(u * 3 + 0) * FS + e] = ax[i] * s0;
-          F[(u * 3 + 1) * FS + e] = ay[i] * s0;
-          F[(u * 3 + 2) * FS + e] = az[i] * s0;
-        } else {  // DDP_F_CROSS: a x s1 / sqrt(2)
-          F[(u * 3 + 0) * FS + e] = (ay[i] * sz - az[i] * sy) * inv_sqrt2;
-          F[(u * 3 + 1) * FS + e] = (az[i] * sx - ax[i] * sz) * inv_sqrt2;
-          F[(u * 3 + 2) * FS + e] = (ax[i] * sy - ay[i] * sx) * inv_sqrt2;
-        }
-      }
-    }
-    ubase += cnt;
-  }
-}
-
-// Where the G tile of segment (block bi, part) sits inside a node's row of task.gh[slot]: byte offset of the tile, padded width, padded
-// columns of the slot and in front of the part (include/ddp_hip.h, ddp_conv_task_t::gh).  Returns false if the block has no G part.
+// The walk of rows_gpart_of (ddp_conv_rows_common.h) in this unit's own spelling: a helper with reference results and an early return.
+// hipcc simplifies a function before it inlines it, and this unit's kernels keep their instructions only with this spelling, those of
+// ddp_conv_rows16.hip only with the header's (profiles/rows_common_isa.txt): the walk - and only the walk - exists twice.
 __device__ __forceinline__ bool rows_gpart(const ddp_conv_shape_t& S, int bi, int part, int& wp, int& cumw, int& gcp) {
   const ddp_block_t& B = S.blk[bi];
   wp = cumw = gcp = 0;
@@ -273,47 +149,15 @@ __device__ __forceinline__ bool rows_gpart(const ddp_conv_shape_t& S, int bi, in
   }
   return true;
 }
-
-// The G runs of one segment: per run of edges with one source node ONE tile product h[32 x 16 NS] @ G[node][16 NS x 32], B = the node's G
-// tile (plane form, task.gh) straight from memory through a register ring of GR fragments; every row belongs to exactly one run, so the
-// products are SELECTED into tg[row] (rows_select_run).  Returns tg (0 in the lanes behind the tile's last column).
-// G of a source node and slot: the column parts of the slot's blocks one after the other, each a CONTIGUOUS tile [k8][wp columns][plane]
-// [8 halves] (wp = the part's width rounded up to 4), then Gb per padded column - a run reads one tile as one linear stream, and stage A
-// fills it in whole 128-byte lines.  Fragment q = 2 ks + plane of lane (r, hh): 16-byte unit 2 (k8 wp + column) + plane, k8 = min(2 ks +
-// hh, n8 - 1), addressed as (node base + uniform fragment offset) + a 32-bit per-lane offset (per-fragment 64-bit lane addresses cost ~40
-// registers).
-// MERGE (two vector blocks of the same width n <= 16 with one G part each, e.g. 1o and 1e at nv = 10): lanes [0, n) take block A's
-// columns, lanes [n, 2 n) block B's (another G array, the same node): ONE tile product per run for both - in block B's own tiles lane
-// n + j is feature group 1 of output column j, i.e. where its lane-group sum expects that column.
-struct RowsGPart {
-  const char* base;      // the part's tile inside node 0's row of its G array
-  size_t gldb;           // node stride in bytes
-  int wp, nmine, bias_off;   // padded width, columns, byte offset of Gb[column 0] (plane form 1: of the Gb region) from `base`
-  int cumw;              // padded columns of the slot in front of the part
-};
-// Plane form 1 of a G array (ddp_conv_task_t::gh_fmt = 1, round 6: "G3"; ABI 17): the unit (k8, c) of a part's tile is 24 bytes - 8 fp16 hi
-// words (V truncated), then 8 continuation bytes (19 significant bits; include/ddp_hip.h) - instead of 32; Gb per padded column c of the
-// slot sits behind the units of all parts in 24-byte groups of six fp32: 24 (c / 6) + 4 (c % 6) bytes.
 template <int GF>
-__device__ __forceinline__ RowsGPart rows_gpart_of(const ddp_conv_shape_t& S, const ddp_conv_task_t& T, int bi, int part) {
+__device__ __forceinline__ RowsGPart rows0_gpart_of(const ddp_conv_shape_t& S, const ddp_conv_task_t& T, int bi, int part) {
   RowsGPart P;
   int wp, cumw, gcp;
   rows_gpart(S, bi, part, wp, cumw, gcp);
-  const int n8 = (S.hid + 7) >> 3;
-  if constexpr (GF == 1) {
-    P.base = reinterpret_cast<const char*>(T.gh[S.blk[bi].g_slot]) + (size_t)(n8 * cumw) * 24;
-    P.gldb = (size_t)DDP_GH3_LD(S.hid, gcp) * 4;
-    P.bias_off = n8 * (gcp - cumw) * 24;
-  } else {
-    P.base = reinterpret_cast<const char*>(T.gh[S.blk[bi].g_slot]) + (size_t)(2 * n8 * cumw) * 16;
-    P.gldb = (size_t)DDP_GH_LD(S.hid, gcp) * 4;
-    P.bias_off = (8 * n8 * gcp + cumw) * 4 - (2 * n8 * cumw) * 16;
-  }
-  P.wp = wp;
-  P.nmine = min(32, S.blk[bi].n - 32 * part);
-  P.cumw = cumw;
+  ROWS_GPART_FILL(GF, P, S, T, S.blk[bi], part, wp, cumw, gcp)
   return P;
 }
+
 // per-lane byte offsets of a G part's fragments and of its Gb word (cl = the lane's column of the part)
 template <int GF>
 struct RowsGLane {
@@ -378,6 +222,17 @@ __device__ __forceinline__ h8 rows_lo_operand(const typename RowsLoT<GF>::type v
     return __builtin_bit_cast(h8, v);
   }
 }
+// The G runs of one segment: per run of edges with one source node ONE tile product h[32 x 16 NS] @ G[node][16 NS x 32], B = the node's G
+// tile (plane form, task.gh) straight from memory through a register ring of GR fragments; every row belongs to exactly one run, so the
+// products are SELECTED into tg[row] (rows_select_run).  Returns tg (0 in the lanes behind the tile's last column).
+// G of a source node and slot: the column parts of the slot's blocks one after the other, each a CONTIGUOUS tile [k8][wp columns][plane]
+// [8 halves] (wp = the part's width rounded up to 4), then Gb per padded column - a run reads one tile as one linear stream, and stage A
+// fills it in whole 128-byte lines.  Fragment q = 2 ks + plane of lane (r, hh): 16-byte unit 2 (k8 wp + column) + plane, k8 = min(2 ks +
+// hh, n8 - 1), addressed as (node base + uniform fragment offset) + a 32-bit per-lane offset (per-fragment 64-bit lane addresses cost ~40
+// registers).
+// MERGE (two vector blocks of the same width n <= 16 with one G part each, e.g. 1o and 1e at nv = 10): lanes [0, n) take block A's
+// columns, lanes [n, 2 n) block B's (another G array, the same node): ONE tile product per run for both - in block B's own tiles lane
+// n + j is feature group 1 of output column j, i.e. where its lane-group sum expects that column.
 template <int NS, int GR, bool MERGE, int G3>
 __device__ __forceinline__ f32x16 rows_g_runs(const ddp_conv_shape_t& S, const RowsGPart& PA, const RowsGPart& PB, const h8 (&ah)[NS], const h8 (&al)[NS],
                                               const RowsAux* aux, unsigned rmask, int src_reg, int lane) {
@@ -593,7 +448,7 @@ __device__ __forceinline__ int rows_segment(const RowsLaunch& RL, const ddp_bloc
   if constexpr (C == 1) {
     if (B.g_slot >= 0 && rmask != 0u) {
       constexpr int GK1 = ((DDP_ROWS_GRING1 >= NF) ? NF : GR) / 2;      // k-steps in the ring
-      const RowsGPart PA = rows_gpart_of<G3>(S, T, bi, part);
+      const RowsGPart PA = rows0_gpart_of<G3>(S, T, bi, part);
       RowsGSeq G;
       f32x4 grh[GK1];
       typename RowsLoT<G3>::type grl[GK1];
@@ -641,7 +496,7 @@ __device__ __forceinline__ int rows_segment(const RowsLaunch& RL, const ddp_bloc
       }
       rows_apply_harmonics<C>(tsel, shrow, res);
     } else if (gmode == 1) {
-      const RowsGPart PA = rows_gpart_of<G3>(S, T, bi, part), PB = rows_gpart_of<G3>(S, T, bi + 1, 0);
+      const RowsGPart PA = rows0_gpart_of<G3>(S, T, bi, part), PB = rows0_gpart_of<G3>(S, T, bi + 1, 0);
       const f32x16 tg = rows_g_runs<NS, GR, true, G3>(S, PA, PB, ah, al, aux, rmask, src_reg, lane);
       if (in_b) {
 #pragma unroll
@@ -652,7 +507,7 @@ __device__ __forceinline__ int rows_segment(const RowsLaunch& RL, const ddp_bloc
       for (int i = 0; i < 16; ++i) tsel[i] = (r < B.n) ? tg[i] : 0.f;
       rows_apply_harmonics<C>(tsel, shrow, res);
     } else {
-      const RowsGPart PA = rows_gpart_of<G3>(S, T, bi, part);
+      const RowsGPart PA = rows0_gpart_of<G3>(S, T, bi, part);
       const f32x16 tg = rows_g_runs<NS, GR, false, G3>(S, PA, PA, ah, al, aux, rmask, src_reg, lane);
       rows_apply_harmonics<C>(tg, shrow, res);
     }
@@ -842,8 +697,6 @@ __global__ __launch_bounds__(ROWS_NT, 2) void ddp_conv_rows_kernel(const RowsLau
       const float v = fmaxf(pre, 0.f);
       const _Float16 hi = (_Float16)v;
       const _Float16 lo = (_Float16)(v - (float)hi);
-      constexpr int dummy = 0;
-      (void)dummy;
       if (2 * ct + (j >> 3) < NS) {
         ah[2 * ct + (j >> 3)][j & 7] = hi;
         al[2 * ct + (j >> 3)][j & 7] = lo;
@@ -910,14 +763,16 @@ __global__ __launch_bounds__(ROWS_NT, 2) void ddp_conv_rows_kernel(const RowsLau
 }
 
 // ------------------------------------------------------------------------------------------------ host
-extern "C" int ddp_conv_rows(const ddp_conv_shape_t* shape, const ddp_conv_task_t* tasks, int ntasks, void* stream) {
+// The launch plan of both forms.  They differ in three places, each a condition on `form` below: the parked G products of form 0's
+// private area, form 1's cap on the feature rows, and form 1's bias table of the fc.0 tiles only (rows_bias_k).
+int ddp_conv_rows_plan(const ddp_conv_shape_t* shape, const ddp_conv_task_t* tasks, int ntasks, RowsPlan* plan) {
   if (!shape || !tasks) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: null argument");
   if (ntasks < 0 || ntasks > DDP_MAX_TASKS) return ddp_fail(DDP_ELIMIT, "ddp_conv_rows: ntasks > DDP_MAX_TASKS");
   if (shape->nblocks < 1 || shape->nblocks > DDP_MAX_BLOCKS) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: nblocks");
   const int sc = (shape->f_in != shape->hid) ? 0 : (shape->hid == 180) ? 60 : (shape->hid == 96) ? 32 : 0;
   if (sc == 0) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: shapes of the size classes ns = 60 / 32 (f_in = hid = 180 / 96) only");
-  RowsLaunch RL;
-  ConvLaunch& L = RL.L;
+  RowsPlan& P = *plan;
+  ConvLaunch& L = P.L;
   L.shape = *shape;
   L.r1_floats = 0;
   L.tv_off = 0;
@@ -941,7 +796,8 @@ extern "C" int ddp_conv_rows(const ddp_conv_shape_t* shape, const ddp_conv_task_
       if (B.U * B.C > frows) frows = B.U * B.C;
     }
   }
-  int tiles = 0, gfmt = -1, form = -1;
+  // gh_fmt, rows_form and rows_bias_k of the launch: those of its first task with edges
+  int tiles = 0, gfmt = -1, form = -1, bias_k = -1;
   for (int i = 0; i < ntasks; ++i) {
     const ddp_conv_task_t& T = tasks[i];
     if (T.n_edges <= 0) continue;  // an empty conv sends no message (models/score_model.py:109-111)
@@ -953,6 +809,13 @@ extern "C" int ddp_conv_rows(const ddp_conv_shape_t* shape, const ddp_conv_task_
       return ddp_fail(DDP_EINVAL, "ddp_conv_rows: task.rows_bias_k / rows_seg0 / rows_seg1 / rows_nts need rows_form 1");
     if (form >= 0 && T.rows_form != form) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: the tasks of a launch carry ONE form of operand images");
     form = T.rows_form;
+    // (form 1's fields; all zero in form 0)
+    if (T.rows_seg0 < 0 || T.rows_seg1 < 0 || T.rows_nts < 0 || (T.rows_seg1 > 0 && (T.rows_seg1 <= T.rows_seg0 || T.rows_nts < nct1)) ||
+        (T.rows_nts > nts) || (T.rows_seg1 > 0 && !T.rows_bias_k))      // (a range's bias table is fc.0's: rows_bias_k)
+      return ddp_fail(DDP_EINVAL, "ddp_conv_rows: task.rows_seg0 / rows_seg1 / rows_nts");
+    if ((bias_k >= 0 && T.rows_bias_k != bias_k) || (unsigned)T.rows_bias_k > 1u || (T.rows_bias_k && (shape->hid & 15) == 0))
+      return ddp_fail(DDP_EINVAL, "ddp_conv_rows: rows_bias_k is 0 or 1 for all tasks of a launch and needs hid % 16 != 0");
+    bias_k = T.rows_bias_k;
     if (T.n_edges_dev) L.dev_counts = 1;
     if (!T.wsh || !T.bsp || (reinterpret_cast<size_t>(T.wsh) & 15) || (reinterpret_cast<size_t>(T.bsp) & 15))
       return ddp_fail(DDP_EINVAL, "ddp_conv_rows: task.wsh / bsp missing (or not 16-byte aligned)");
@@ -970,36 +833,54 @@ extern "C" int ddp_conv_rows(const ddp_conv_shape_t* shape, const ddp_conv_task_
     ++L.ntasks;
   }
   L.tile_start[L.ntasks] = tiles;
+  P.sc = sc;
+  P.form = form;
+  P.gh_fmt = gfmt;
+  P.tiles = tiles;
   if (tiles == 0) return 0;
-  if (form == 1) return ddp_conv_rows16_launch(shape, tasks, ntasks, sc, stream);     // operand images of v_mfma_f32_16x16x32_f16
-  RL.nts = nts;
+  // ---- the LDS plan: [ring: one tile's worth of pieces][bias table][per wave: feature rows | per-edge tables (| form 0: parked G products)]
+  P.nts = nts;
+  if (form == 1 && frows > R16_FROWS) frows = R16_FROWS;      // (larger blocks build their features in chunks)
+  P.frows = frows;
   int fbytes = frows * ROWS_FS * 4;
   fbytes = (fbytes + 127) / 128 * 128;
-  RL.aux_off = fbytes;
-  int priv = fbytes + (int)sizeof(RowsAux) + 2048;      // (+ the parked G products of a merged pair of vector blocks)
+  P.aux_off = fbytes;
+  int priv = fbytes + (int)sizeof(RowsAux);
+  if (form == 0) priv += 2048;                     // the parked G products of a merged pair of vector blocks
   if (priv < NS * 1024) priv = NS * 1024;          // the lo plane of edge_attr_ during fc1
   priv = (priv + 127) / 128 * 128;
-  RL.priv_bytes = priv;
-  RL.bias_bytes = (nts * 128 + 127) / 128 * 128;
-  size_t lds_bytes = (size_t)2 * (NS * 1024) + RL.bias_bytes + (size_t)ROWS_NW * priv;
+  P.priv_bytes = priv;
+  P.bias_tiles = (form == 1 && bias_k) ? nct1 : nts;
+  P.bias_bytes = (P.bias_tiles * 128 + 127) / 128 * 128;
+  size_t lds_bytes = (size_t)2 * (NS * 1024) + P.bias_bytes + (size_t)ROWS_NW * priv;
   if (2 * lds_bytes > 160 * 1024) return ddp_fail(DDP_ELIMIT, "ddp_conv_rows: LDS budget of two workgroups per CU exceeded (too many vector features per block)");
   // occupancy shaping (ddp_set_occupancy_shaping): a launch that is to leave one 256-register wave slot per SIMD to another kernel asks
   // for more LDS than two workgroups per CU can have
   if ((size_t)ddp_shape_rows_min_lds > lds_bytes) lds_bytes = (size_t)ddp_shape_rows_min_lds;
+  P.lds_bytes = lds_bytes;
+  return 0;
+}
+
+extern "C" int ddp_conv_rows(const ddp_conv_shape_t* shape, const ddp_conv_task_t* tasks, int ntasks, void* stream) {
+  RowsPlan P;
+  const int rc = ddp_conv_rows_plan(shape, tasks, ntasks, &P);
+  if (rc != 0 || P.tiles == 0) return rc;
+  if (P.form == 1) return ddp_conv_rows16_launch(P, stream);     // operand images of v_mfma_f32_16x16x32_f16
+  RowsLaunch RL;
+  RL.L = P.L;
+  RL.nts = P.nts;
+  RL.bias_bytes = P.bias_bytes;
+  RL.priv_bytes = P.priv_bytes;
+  RL.aux_off = P.aux_off;
   static int lds_have[4] = {0, 0, 0, 0};
   hipError_t err;
-#define ROWS_LAUNCH(SZ_, G3_, I_)                                                                                                       \
-  {                                                                                                                                     \
-    err = ddp_need_lds(reinterpret_cast<const void*>(ddp_conv_rows_kernel<SZ_, G3_>), (int)lds_bytes, &lds_have[I_]);                  \
-    if (err != hipSuccess) return ddp_fail_hip(err, "hipFuncSetAttribute(conv rows)");                                                 \
-    hipLaunchKernelGGL((ddp_conv_rows_kernel<SZ_, G3_>), dim3(tiles), dim3(ROWS_NT), lds_bytes, (hipStream_t)stream, RL);               \
-  }
-  if (sc == 60) {
-    if (gfmt == 1) ROWS_LAUNCH(60, 1, 2) else ROWS_LAUNCH(60, 0, 0)
+  if (P.sc == 60) {
+    if (P.gh_fmt == 1) ROWS_LAUNCH((ddp_conv_rows_kernel<60, 1>), 2, "hipFuncSetAttribute(conv rows)")
+    else ROWS_LAUNCH((ddp_conv_rows_kernel<60, 0>), 0, "hipFuncSetAttribute(conv rows)")
   } else {
-    if (gfmt == 1) ROWS_LAUNCH(32, 1, 3) else ROWS_LAUNCH(32, 0, 1)
+    if (P.gh_fmt == 1) ROWS_LAUNCH((ddp_conv_rows_kernel<32, 1>), 3, "hipFuncSetAttribute(conv rows)")
+    else ROWS_LAUNCH((ddp_conv_rows_kernel<32, 0>), 1, "hipFuncSetAttribute(conv rows)")
   }
-#undef ROWS_LAUNCH
   err = hipGetLastError();
   if (err != hipSuccess) return ddp_fail_hip(err, "ddp_conv_rows launch");
   return 0;

@@ -26,95 +26,27 @@
 //   permuted.
 // Summation order of a message element: G runs in edge order, then the stream tiles in feature order, then (blocks with several
 // features per tile) the lane groups in order: fixed, bitwise reproducible; within fp32 rounding of the other conv kernels.
+// What does not depend on the MFMA shape - the weight ring, the feature rows, G's byte layout, the host's launch plan - is shared with
+// ddp_conv_rows.hip through ddp_conv_rows_common.h (the rows_ / Rows names below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #undef DDP_STAMPS
-#include "ddp_conv_common.h"
-
-#define R16_NW 4
-#define R16_NT 256
-#define R16_ET 128
-#define R16_FS 36     // floats per feature row F[u * C + c][edge]
-#define R16_NP 3      // pieces per stream tile (one ring slot each)
-#define R16_FROWS 72  // feature rows a wave holds at a time (a block with more - the direct convs: 80 features x 3 components - builds them in chunks)
-#define R16_SX ((float)DDP_ROWS_SX)
-#define R16_SW ((float)DDP_ROWS_SW)
-#define R16_SH ((float)DDP_ROWS_SH)
-#define R16_SG ((float)DDP_ROWS_SG)
+#include "ddp_conv_rows_common.h"
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* r16_lds_ptr_t;
-typedef __amdgpu_buffer_rsrc_t R16Stream;
-
-struct R16Launch {
-  ConvLaunch L;
-  int nts;         // stream tiles per conv (fc.0 tiles + fc.3 tiles of all segments)
-  int bias_tiles;  // stream tiles whose bias words sit in the LDS table (all, or fc.0's: ddp_conv_task_t::rows_bias_k)
-  int bias_bytes;  // LDS bytes of the bias table behind the ring
-  int priv_bytes;  // LDS bytes of a wave's private area
-  int aux_off;     // byte offset of the per-edge tables inside it
-  int frows;       // feature rows of the private area (<= R16_FROWS)
-};
-static_assert(sizeof(ConvLaunch) + 16 <= 4096, "the launch descriptor travels as a kernel argument");
-struct R16Aux {
-  float shT[4][32];   // harmonics, component-major (the "feature rows" of the factorised features), x 1 / (SH SG)
-  float sh[32][4];    // ... edge-major, x 1 / (SH SW) (the stream tiles' features)
-  int src[32], pos[32], rid[32];
-};
-
 __device__ __forceinline__ f32x4 r16_splat4(float v) { return f32x4{v, v, v, v}; }
-__device__ __forceinline__ void r16_split(const f32x4 v, float scale, h4& hi, h4& lo, int32_t* flag) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float V = v[i] * scale;
-    h2_range_check(V, flag);
-    hi[i] = (_Float16)V;
-    lo[i] = (_Float16)(V - (float)hi[i]);
-  }
-}
-
-// ---- the weight stream (ddp_conv_rows.hip's: a tile travels as R16_NP pieces through a three-slot LDS ring; one BARE barrier per piece)
-__device__ __forceinline__ R16Stream r16_stream_of(const void* wsh, int nts, int tile_bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wsh), 0, nts * tile_bytes, 0x00020000);
-}
-template <int NS>
-__device__ __forceinline__ void r16_request_piece(f32x4* ring, R16Stream wsh, int jn, int npieces, int slot, int wave, int lane) {
-  constexpr int FPP = 2 * NS / R16_NP, FPW = FPP / R16_NW, PIECE_Q = FPP * 64;
-  static_assert(NS % R16_NP == 0 && FPP % R16_NW == 0, "every wave moves the same number of fragments per piece");
-  f32x4* nslot = ring + slot * PIECE_Q;
-  const int piece_off = min(jn, npieces - 1) * (PIECE_Q * 16);
-#pragma unroll
-  for (int f = 0; f < FPW; ++f)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(wsh, (r16_lds_ptr_t)(nslot + (wave + R16_NW * f) * 64), 16, ((wave + R16_NW * f) * 64 + lane) * 16, piece_off, 0, 0);
-}
-template <int NS, int P>
-__device__ __forceinline__ void r16_stream_step(f32x4* ring, R16Stream wsh, int t, int nts, int wave, int lane) {
-  constexpr int FPW = 2 * NS / R16_NP / R16_NW;
-  static_assert(FPW == 2 || FPW == 1, "the literals below");
-  // (hipcc does not wait for an LDS-DMA in front of a barrier: "at most FPW outstanding" = everything older than the copies of piece j + 1 has landed)
-  if constexpr (FPW == 2)
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  r16_request_piece<NS>(ring, wsh, R16_NP * t + P + 2, R16_NP * nts, (P + 2) % R16_NP, wave, lane);
-}
 
 // acc[2 rt + ct] += A(h of row tile rt, k32 steps of piece P) x B(piece in LDS: fragments [k32 step][ct][plane]); three split products
 // per k-step on ONE accumulator (unified planes)
 template <int NS, int P>
 __device__ __forceinline__ void r16_piece(const f32x4* slot, const h8 (&ah)[NS], const h8 (&al)[NS], int lane, f32x4 (&acc)[4]) {
-  constexpr int KP2 = NS / R16_NP / 2;     // k32 steps per piece
-  static_assert((NS / R16_NP) % 2 == 0, "a piece holds whole k32 steps");
+  constexpr int KP2 = NS / ROWS_NP / 2;     // k32 steps per piece
+  static_assert((NS / ROWS_NP) % 2 == 0, "a piece holds whole k32 steps");
 #pragma unroll
   for (int k = 0; k < KP2; ++k) {
-    constexpr int dummy = 0;
-    (void)dummy;
     const int s = P * KP2 + k;
     h8 b[2][2];
 #pragma unroll
@@ -134,53 +66,11 @@ __device__ __forceinline__ void r16_piece(const f32x4* slot, const h8 (&ah)[NS],
   }
 }
 
-// The basis features of a block's vector-input segments (DOT, VEC_S0, CROSS; ddp_conv_rows.hip's rows_build_features: independent of the
-// MFMA shape - feature rows are indexed by edge)
-template <int MAXI>
-__device__ __forceinline__ void r16_build_features(const ddp_block_t& B, const ddp_conv_task_t& T, const R16Aux* aux, float* F, int lane) {
-  constexpr int FS = R16_FS;
-  const int e = lane & 31, half = lane >> 5;
-  const float* __restrict__ xrow = T.x_src + (size_t)aux->src[e] * T.ldx_src;
-  const float s0 = aux->sh[e][0], sx = aux->sh[e][1], sy = aux->sh[e][2], sz = aux->sh[e][3];
-  const float inv_sqrt3 = 0.57735026918962576f, inv_sqrt2 = 0.70710678118654752f;
-  int ubase = 0;
-  for (int si = 0; si < B.nseg; ++si) {
-    const int kind = B.seg[si].kind, off = B.seg[si].in_off, cnt = B.seg[si].count;
-    float ax[MAXI], ay[MAXI], az[MAXI];
-#pragma unroll
-    for (int i = 0; i < MAXI; ++i) {
-      const int ul = max(min(half + 2 * i, cnt - 1), 0);
-      ax[i] = xrow[off + 3 * ul];
-      ay[i] = xrow[off + 3 * ul + 1];
-      az[i] = xrow[off + 3 * ul + 2];
-    }
-#pragma unroll
-    for (int i = 0; i < MAXI; ++i) {
-      const int ul = half + 2 * i;
-      if (ul < cnt) {
-        const int u = ubase + ul;
-        if (kind == DDP_F_DOT) {
-          F[u * FS + e] = (ax[i] * sx + ay[i] * sy + az[i] * sz) * inv_sqrt3;
-        } else if (kind == DDP_F_VEC_S0) {
-          F[(u * 3 + 0) * FS + e] = ax[i] * s0;
-          F[(u * 3 + 1) * FS + e] = ay[i] * s0;
-          F[(u * 3 + 2) * FS + e] = az[i] * s0;
-        } else {  // DDP_F_CROSS: a x s1 / sqrt(2)
-          F[(u * 3 + 0) * FS + e] = (ay[i] * sz - az[i] * sy) * inv_sqrt2;
-          F[(u * 3 + 1) * FS + e] = (az[i] * sx - ax[i] * sz) * inv_sqrt2;
-          F[(u * 3 + 2) * FS + e] = (ax[i] * sy - ay[i] * sx) * inv_sqrt2;
-        }
-      }
-    }
-    ubase += cnt;
-  }
-}
-
-// ... the features [u0, u1) of a block of ANY kinds, rows (u - u0) C + c: the chunks of a block whose features do not fit the private area at
+// The basis features [u0, u1) of a block of ANY kinds, rows (u - u0) C + c: the chunks of a block whose features do not fit the private area at
 // once (the direct convs; build_features of ddp_conv_common.h over a range, for one wave: lane = (edge, half))
-__device__ __forceinline__ void r16_build_features_range(const ddp_block_t& B, const ddp_conv_task_t& T, const R16Aux* aux, float* F, int lane,
+__device__ __forceinline__ void r16_build_features_range(const ddp_block_t& B, const ddp_conv_task_t& T, const RowsAux* aux, float* F, int lane,
                                                          int u0, int u1) {
-  constexpr int FS = R16_FS;
+  constexpr int FS = ROWS_FS;
   const int e = lane & 31, half = lane >> 5;
   const float* __restrict__ xrow = T.x_src + (size_t)aux->src[e] * T.ldx_src;
   const float s0 = aux->sh[e][0], sx = aux->sh[e][1], sy = aux->sh[e][2], sz = aux->sh[e][3];
@@ -215,47 +105,6 @@ __device__ __forceinline__ void r16_build_features_range(const ddp_block_t& B, c
   }
 }
 
-// Where the G tile of segment (block bi, part) sits inside a node's row of task.gh[slot] (plane form 0: [k8][wp columns][plane][8 halves] per
-// part, then Gb per padded column; include/ddp_hip.h)
-struct R16GPart {
-  const char* base;      // the part's tile inside node 0's row of its G array
-  size_t gldb;           // node stride in bytes
-  int wp, nmine, bias_off;   // padded width, columns, byte offset of Gb[column 0] from `base` (plane form 1: of Gb's first group)
-  int cumw;                  // padded columns of the slot in front of the part
-};
-// Plane form GF (ddp_conv_task_t::gh_fmt): 0 = [k8][c][plane][8 halves], 32 bytes per unit (k8, c); 1 = 24-byte units [8 hi halves | 8
-// continuation bytes], Gb in 24-byte groups of six fp32 behind the units of all parts
-template <int GF>
-__device__ __forceinline__ R16GPart r16_gpart_of(const ddp_conv_shape_t& S, const ddp_conv_task_t& T, int bi, int part) {
-  const ddp_block_t& B = S.blk[bi];
-  int wp = 0, cumw = 0, gcp = 0;
-  for (int bj = 0; bj < S.nblocks; ++bj) {
-    const ddp_block_t& Bj = S.blk[bj];
-    if (Bj.g_slot != B.g_slot) continue;
-    for (int pj = 0; pj < ((Bj.n + 31) >> 5); ++pj) {
-      const int wj = (min(32, Bj.n - 32 * pj) + 3) & ~3;
-      if (bj < bi || (bj == bi && pj < part)) cumw += wj;
-      if (bj == bi && pj == part) wp = wj;
-      gcp += wj;
-    }
-  }
-  const int n8 = (S.hid + 7) >> 3;
-  R16GPart P;
-  if constexpr (GF == 1) {
-    P.base = reinterpret_cast<const char*>(T.gh[B.g_slot]) + (size_t)(n8 * cumw) * 24;
-    P.gldb = (size_t)DDP_GH3_LD(S.hid, gcp) * 4;
-    P.bias_off = 24 * n8 * gcp - 24 * n8 * cumw;
-  } else {
-    P.base = reinterpret_cast<const char*>(T.gh[B.g_slot]) + (size_t)(2 * n8 * cumw) * 16;
-    P.gldb = (size_t)DDP_GH_LD(S.hid, gcp) * 4;
-    P.bias_off = (8 * n8 * gcp + cumw) * 4 - (2 * n8 * cumw) * 16;
-  }
-  P.cumw = cumw;
-  P.wp = wp;
-  P.nmine = min(32, B.n - 32 * part);
-  return P;
-}
-
 // The G runs of one segment, NCT 16-column tiles wide (1: the part has at most 16 columns): per run of edges with one source node the tile
 // product h[32 x 16 NS] @ G[node][16 NS x 16 NCT], B = the node's G tile straight from memory through a register ring of GK k32 steps
 // (buffer loads: descriptor of the node's row + a uniform fragment offset + one lane offset per column tile); while run i is multiplied
@@ -263,7 +112,7 @@ __device__ __forceinline__ R16GPart r16_gpart_of(const ddp_conv_shape_t& S, cons
 // run: the run's rows are selected from its product (rid), times the harmonic(s), into the segment's accumulators.
 template <int NCT>
 struct R16GSeq {
-  R16Stream rs, rsn;     // the current run's node, the next run's (behind the last run: an empty buffer)
+  RowsStream rs, rsn;     // the current run's node, the next run's (behind the last run: an empty buffer)
   const char* base;
   size_t gldb;
   float bias[NCT];       // Gb of the current run's columns
@@ -273,7 +122,7 @@ struct R16GSeq {
   int gc;
 };
 template <int NCT>
-__device__ __forceinline__ R16Stream r16_gseq_node(const R16GSeq<NCT>& G, int src_reg, int row) {
+__device__ __forceinline__ RowsStream r16_gseq_node(const R16GSeq<NCT>& G, int src_reg, int row) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(G.base + (size_t)__builtin_amdgcn_readlane(src_reg, row) * G.gldb), 0, (int)G.gldb, 0x00020000);
 }
 template <int NCT>
@@ -296,13 +145,13 @@ struct R16Lo<1> {
   typedef r16_u32x2 T;
 };
 template <int NCT, int NS2, int GF>
-__device__ __forceinline__ f32x4 r16_gfrag_hi(const R16GSeq<NCT>& G, R16Stream R, int kq, int ct) {
+__device__ __forceinline__ f32x4 r16_gfrag_hi(const R16GSeq<NCT>& G, RowsStream R, int kq, int ct) {
   constexpr int UB = GF == 1 ? 24 : 32;
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R, ((kq == NS2 - 1) ? G.l_last[ct] : G.l_main[ct]),
                                                                           (kq == NS2 - 1) ? 0 : 4 * kq * G.gc * UB, 0));
 }
 template <int NCT, int NS2, int GF>
-__device__ __forceinline__ typename R16Lo<GF>::T r16_gfrag_lo(const R16GSeq<NCT>& G, R16Stream R, int kq, int ct) {
+__device__ __forceinline__ typename R16Lo<GF>::T r16_gfrag_lo(const R16GSeq<NCT>& G, RowsStream R, int kq, int ct) {
   if constexpr (GF == 1)
     return __builtin_bit_cast(r16_u32x2, __builtin_amdgcn_raw_buffer_load_b64(R, ((kq == NS2 - 1) ? G.l_last[ct] : G.l_main[ct]) + 16,
                                                                                (kq == NS2 - 1) ? 0 : 4 * kq * G.gc * 24, 0));
@@ -330,7 +179,7 @@ __device__ __forceinline__ h8 r16_lo_of(const f32x4 hi, const r16_u32x2 by) {
 }
 template <int NS, int NCT, int GK, int GF>
 __device__ __forceinline__ void r16_gseq_init(R16GSeq<NCT>& G, f32x4 (&gh)[GK][NCT], typename R16Lo<GF>::T (&gl)[GK][NCT], f32x4 (&gacc)[4],
-                                              const ddp_conv_shape_t& S, const R16GPart& PA, unsigned rmask, int src_reg, int lane) {
+                                              const ddp_conv_shape_t& S, const RowsGPart& PA, unsigned rmask, int src_reg, int lane) {
   constexpr int NS2 = NS / 2;
   const int n = lane & 15, g = lane >> 4;
   const int n8 = (S.hid + 7) >> 3;
@@ -391,7 +240,7 @@ __device__ __forceinline__ void r16_gseq_step(R16GSeq<NCT>& G, f32x4 (&gh)[GK][N
     }
   }
   __builtin_amdgcn_sched_barrier(0);
-  const R16Stream srcb = (q0 < NS2) ? G.rs : G.rsn;
+  const RowsStream srcb = (q0 < NS2) ? G.rs : G.rsn;
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct) {
     gh[KS % GK][ct] = r16_gfrag_hi<NCT, NS2, GF>(G, srcb, kq, ct);
@@ -401,7 +250,7 @@ __device__ __forceinline__ void r16_gseq_step(R16GSeq<NCT>& G, f32x4 (&gh)[GK][N
 }
 // the run's last k-step is done: res[c][row, column] += harmonic_c[row] * (product + Gb) for the rows of THIS run
 template <int C, int NCT>
-__device__ __forceinline__ void r16_gseq_finish(R16GSeq<NCT>& G, f32x4 (&gacc)[4], const R16Aux* aux, int g, const bool (&mine)[NCT], int src_reg,
+__device__ __forceinline__ void r16_gseq_finish(R16GSeq<NCT>& G, f32x4 (&gacc)[4], const RowsAux* aux, int g, const bool (&mine)[NCT], int src_reg,
                                                 f32x16 (&res)[C]) {
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt) {
@@ -425,7 +274,7 @@ __device__ __forceinline__ void r16_gseq_finish(R16GSeq<NCT>& G, f32x4 (&gacc)[4
   r16_gseq_next(G, src_reg, gacc);
 }
 template <int NS, int C, int NCT, int GF>
-__device__ __forceinline__ void r16_g_runs(const ddp_conv_shape_t& S, const R16GPart& PA, const h8 (&ah)[NS], const h8 (&al)[NS], const R16Aux* aux,
+__device__ __forceinline__ void r16_g_runs(const ddp_conv_shape_t& S, const RowsGPart& PA, const h8 (&ah)[NS], const h8 (&al)[NS], const RowsAux* aux,
                                            unsigned rmask, int src_reg, int lane, f32x16 (&res)[C]) {
   // k32 steps in the ring: half a tile at NS = 12 (the whole tile at NS = 6) for the scalar segments - 12 fragments at two column tiles, like
   // ddp_conv_rows.hip -; a vector segment holds three accumulator sets, so its ring is 6 fragments at one column tile (n <= 16: the shapes
@@ -458,11 +307,11 @@ __device__ __forceinline__ void r16_g_runs(const ddp_conv_shape_t& S, const R16G
 // tiles (vector-input features), then the message columns
 template <int NS, int C, int GF, bool DIRECT>
 __device__ __forceinline__ int r16_segment(const R16Launch& RL, const ddp_block_t& B, int bi, int part, const ddp_conv_task_t& T, const h8 (&ah)[NS],
-                                           const h8 (&al)[NS], f32x4* ring, const float* lbias, int t, float* F, const R16Aux* aux, unsigned rmask,
+                                           const h8 (&al)[NS], f32x4* ring, const float* lbias, int t, float* F, const RowsAux* aux, unsigned rmask,
                                            int src_reg, int nvw, int wave, int lane, int nts) {
   const ddp_conv_shape_t& S = RL.L.shape;
   const int n = lane & 15, g = lane >> 4;
-  const R16Stream wsh = r16_stream_of(T.wsh, nts, 2 * NS * 1024);
+  const RowsStream wsh = rows_stream_of(T.wsh, nts, 2 * NS * 1024);
   // lane -> (output channel, feature slot) of the segment's tiles, per 16-column tile ct: column 16 ct + n of the 32-column tile
   int ncol[2], us[2];
   bool valid[2];
@@ -486,7 +335,7 @@ __device__ __forceinline__ int r16_segment(const R16Launch& RL, const ddp_block_
   // ---- factorised features
   if constexpr (!DIRECT) {
     if (B.g_slot >= 0 && rmask != 0u) {
-      const R16GPart PA = r16_gpart_of<GF>(S, T, bi, part);
+      const RowsGPart PA = rows_gpart_of<GF>(S, T, bi, part);
       if (PA.nmine > 16)
         r16_g_runs<NS, C, 2, GF>(S, PA, ah, al, aux, rmask, src_reg, lane, res);
       else
@@ -502,13 +351,13 @@ __device__ __forceinline__ int r16_segment(const R16Launch& RL, const ddp_block_
   const int tpc = chunked ? max(1, RL.frows / (C * upt)) : cnt;
   int u0 = 0;
   for (int j = 0; j < cnt; ++j, ++t) {
-    constexpr int KPP = NS / R16_NP, PIECE_Q = 2 * KPP * 64;
+    constexpr int KPP = NS / ROWS_NP, PIECE_Q = 2 * KPP * 64;
     if (chunked && j % tpc == 0) {
       u0 = j * upt;
       r16_build_features_range(B, T, aux, F, lane, u0, min(B.U, u0 + tpc * upt));
     }
     f32x4 acc[4];
-    r16_stream_step<NS, 0>(ring, wsh, t, nts, wave, lane);
+    rows_stream_step<NS, 0>(ring, wsh, t, nts, wave, lane);
     {
       // (rows_bias_k: the tile's bias is its k row `hid`, times h[hid] = 1)
       const bool bt = t < RL.bias_tiles;
@@ -519,21 +368,21 @@ __device__ __forceinline__ int r16_segment(const R16Launch& RL, const ddp_block_
       acc[3] = r16_splat4(b1);
     }
     r16_piece<NS, 0>(ring, ah, al, lane, acc);                      // (piece p of every tile sits in slot p)
-    r16_stream_step<NS, 1>(ring, wsh, t, nts, wave, lane);
+    rows_stream_step<NS, 1>(ring, wsh, t, nts, wave, lane);
     r16_piece<NS, 1>(ring + PIECE_Q, ah, al, lane, acc);
-    r16_stream_step<NS, 2>(ring, wsh, t, nts, wave, lane);
+    rows_stream_step<NS, 2>(ring, wsh, t, nts, wave, lane);
     r16_piece<NS, 2>(ring + 2 * PIECE_Q, ah, al, lane, acc);
     // the feature contraction in the D layout: out[c][row, column] += F[(u c)][row] * acc[row, column]
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       int u = (B.nsub > 1) ? j : j * B.ups + us[ct];
       if (!(valid[ct] && u < B.U)) u = 0;
-      const float* frow = F + ((u - u0) * C) * R16_FS + 4 * g;
+      const float* frow = F + ((u - u0) * C) * ROWS_FS + 4 * g;
 #pragma unroll
       for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-          const f32x4 f = *reinterpret_cast<const f32x4*>(frow + c * R16_FS + 16 * rt);
+          const f32x4 f = *reinterpret_cast<const f32x4*>(frow + c * ROWS_FS + 16 * rt);
 #pragma unroll
           for (int q = 0; q < 4; ++q) res[c][4 * (2 * rt + ct) + q] += f[q] * acc[2 * rt + ct][q];
         }
@@ -584,20 +433,20 @@ template <int SZ, int GF, bool DIRECT>
 __device__ __forceinline__ void r16_body(const R16Launch& RL) {
   constexpr int NS = H2Class<SZ>::NS, NS2 = NS / 2, RING_Q = 2 * NS * 64;     // the ring holds one tile's worth of pieces
   constexpr int NQ = SZ / 4;     // 16-byte quads per edge_attr_ segment (ns floats each)
-  static_assert(NS > 0 && NS % (2 * R16_NP) == 0 && SZ % 4 == 0, "size classes whose k16 steps split into R16_NP pieces of whole k32 steps");
+  static_assert(NS > 0 && NS % (2 * ROWS_NP) == 0 && SZ % 4 == 0, "size classes whose k16 steps split into ROWS_NP pieces of whole k32 steps");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const ConvLaunch& L = RL.L;
   const ddp_conv_shape_t& S = L.shape;
   const int tid = threadIdx.x;
   int ti, p0, nvalid;
-  if (!conv_tile<R16_ET>(L, ti, p0, nvalid)) return;
+  if (!conv_tile<ROWS_ET>(L, ti, p0, nvalid)) return;
   const ddp_conv_task_t& T = L.task[ti];
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, n = lane & 15, g = lane >> 4;
   f32x4* ring = reinterpret_cast<f32x4*>(lds);
   float* lbias = lds + RING_Q * 4;                                        // [nts][32] bias words of the stream tiles
   char* priv = reinterpret_cast<char*>(lds) + RING_Q * 16 + RL.bias_bytes + (size_t)wave * RL.priv_bytes;
   const int nts = (T.rows_nts > 0) ? T.rows_nts : RL.nts;      // stream tiles of THIS task (a task of a segment range has a stream of its own)
-  const R16Stream wsh = r16_stream_of(T.wsh, nts, 2 * NS * 1024);
+  const RowsStream wsh = rows_stream_of(T.wsh, nts, 2 * NS * 1024);
   const int nvw = max(0, min(32, nvalid - 32 * wave));      // valid edges of this wave
 
   // ---- the wave's edges (rows behind the last valid one repeat it: every load stays in bounds, nothing of theirs is stored).  Per-edge
@@ -630,9 +479,9 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
   }
 
   // ---- request tiles 0 / 1 of the stream; the tiles' bias words: one table in LDS for the whole kernel
-  r16_request_piece<NS>(ring, wsh, 0, R16_NP * nts, 0, wave, lane);
-  r16_request_piece<NS>(ring, wsh, 1, R16_NP * nts, 1, wave, lane);
-  for (int i = tid; i < RL.bias_tiles * 32; i += R16_NT) lbias[i] = T.bsp[i];
+  rows_request_piece<NS>(ring, wsh, 0, ROWS_NP * nts, 0, wave, lane);
+  rows_request_piece<NS>(ring, wsh, 1, ROWS_NP * nts, 1, wave, lane);
+  for (int i = tid; i < RL.bias_tiles * 32; i += ROWS_NT) lbias[i] = T.bsp[i];
   // ---- edge_attr_ of the wave's edges as B-operand fragments: lane (edge n of tile et, g) holds k = 32 s + 8 g + i.  hi plane in registers,
   // lo plane in the wave's private LDS area (each lane reads back what it wrote); image index 2 s + et
   h8 xh[NS];
@@ -653,8 +502,8 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
 #pragma unroll
       for (int et = 0; et < 2; ++et) {
         h4 h0, l0, h1, l1;
-        r16_split(xv[et][0], R16_SX, h0, l0, T.h2_range_flag);
-        r16_split(xv[et][1], R16_SX, h1, l1, T.h2_range_flag);
+        rows_split(xv[et][0], ROWS_SX, h0, l0, T.h2_range_flag);
+        rows_split(xv[et][1], ROWS_SX, h1, l1, T.h2_range_flag);
         h8 lo;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -677,11 +526,11 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
   for (int ct = 0; ct < NS2; ++ct, ++t) {
     f32x4 acc[4];      // [2 mt + et]
 #pragma unroll
-    for (int pc = 0; pc < R16_NP; ++pc) {
-      constexpr int KPP = NS / R16_NP, KP2 = KPP / 2, PIECE_Q = 2 * KPP * 64;
-      if (pc == 0) r16_stream_step<NS, 0>(ring, wsh, t, nts, wave, lane);
-      else if (pc == 1) r16_stream_step<NS, 1>(ring, wsh, t, nts, wave, lane);
-      else r16_stream_step<NS, 2>(ring, wsh, t, nts, wave, lane);
+    for (int pc = 0; pc < ROWS_NP; ++pc) {
+      constexpr int KPP = NS / ROWS_NP, KP2 = KPP / 2, PIECE_Q = 2 * KPP * 64;
+      if (pc == 0) rows_stream_step<NS, 0>(ring, wsh, t, nts, wave, lane);
+      else if (pc == 1) rows_stream_step<NS, 1>(ring, wsh, t, nts, wave, lane);
+      else rows_stream_step<NS, 2>(ring, wsh, t, nts, wave, lane);
       if (pc == 0) {
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -717,7 +566,7 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
     for (int et = 0; et < 2; ++et)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const float pre = acc[2 * (i >> 2) + et][i & 3] * (R16_SH / (R16_SW * R16_SX));     // the h plane's scale over the accumulator's
+        const float pre = acc[2 * (i >> 2) + et][i & 3] * (ROWS_SH / (ROWS_SW * ROWS_SX));     // the h plane's scale over the accumulator's
         h2_range_check(pre, T.h2_range_flag);     // (before the relu: fmaxf drops a NaN)
         const float v = fmaxf(pre, 0.f);
         const _Float16 hi = (_Float16)v;
@@ -728,7 +577,7 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
 
   // ---- per-edge tables of the wave (the private area is free: the lo plane of edge_attr_ is dead)
   float* F = reinterpret_cast<float*>(priv);
-  R16Aux* aux = reinterpret_cast<R16Aux*>(priv + RL.aux_off);
+  RowsAux* aux = reinterpret_cast<RowsAux*>(priv + RL.aux_off);
   unsigned rmask;
   {
     const int prev = __shfl_up(src, 1);
@@ -741,7 +590,7 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
       aux->pos[r] = pos;
       aux->rid[r] = rowv ? (int)__popc(rmask & upto) - 1 : -1;
       // the harmonics carry the inverse of the accumulators' scales: 1 / (SH SW) for the stream tiles' features, 1 / (SH SG) for G
-      constexpr float fs = 1.f / (R16_SH * R16_SW), gs = 1.f / (R16_SH * R16_SG);
+      constexpr float fs = 1.f / (ROWS_SH * ROWS_SW), gs = 1.f / (ROWS_SH * ROWS_SG);
       aux->sh[r][0] = shv[0] * fs; aux->sh[r][1] = shv[1] * fs; aux->sh[r][2] = shv[2] * fs; aux->sh[r][3] = shv[3] * fs;
       aux->shT[0][r] = shv[0] * gs; aux->shT[1][r] = shv[1] * gs; aux->shT[2][r] = shv[2] * gs; aux->shT[3][r] = shv[3] * gs;
     }
@@ -763,7 +612,7 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
       for (int si = 0; si < B.nseg; ++si)
         fast = fast && B.seg[si].count <= 16 && (B.seg[si].kind == DDP_F_DOT || B.seg[si].kind == DDP_F_VEC_S0 || B.seg[si].kind == DDP_F_CROSS);
       if (fast)
-        r16_build_features<8>(B, T, aux, F, lane);
+        rows_build_features<8>(B, T, aux, F, lane);
       else
         build_features<32, 2>(B, T, aux->src, aux->sh, F, lane);
     }
@@ -778,92 +627,37 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
 }
 
 template <int SZ, int GF>
-__global__ __launch_bounds__(R16_NT, 2) void ddp_conv_rows16_kernel(const R16Launch RL) {
+__global__ __launch_bounds__(ROWS_NT, 2) void ddp_conv_rows16_kernel(const R16Launch RL) {
   r16_body<SZ, GF, false>(RL);
 }
 template <int SZ>
-__global__ __launch_bounds__(R16_NT, 2) void ddp_conv_rows16_direct_kernel(const R16Launch RL) {
+__global__ __launch_bounds__(ROWS_NT, 2) void ddp_conv_rows16_direct_kernel(const R16Launch RL) {
   r16_body<SZ, 0, true>(RL);
 }
 
 // ------------------------------------------------------------------------------------------------ host (called by ddp_conv_rows for rows_form = 1)
-int ddp_conv_rows16_launch(const ddp_conv_shape_t* shape, const ddp_conv_task_t* tasks, int ntasks, int sc, void* stream) {
+int ddp_conv_rows16_launch(const RowsPlan& P, void* stream) {
   R16Launch RL;
-  ConvLaunch& L = RL.L;
-  L.shape = *shape;
-  L.r1_floats = 0;
-  L.tv_off = 0;
-  L.ntasks = 0;
-  L.dev_counts = 0;
-  const int NS = (sc == 60) ? 12 : 6, nct1 = shape->nct1;
-  int nts = nct1, frows = 0;
-  for (int b = 0; b < shape->nblocks; ++b) {
-    const ddp_block_t& B = shape->blk[b];
-    if (B.ntiles > 0 && B.U > 0) {
-      nts += ((B.n + 31) / 32) * (B.nsub > 1 ? B.U : (B.U + B.ups - 1) / B.ups);
-      if (B.U * B.C > frows) frows = B.U * B.C;
-    }
-  }
-  int tiles = 0;
-  const ddp_conv_task_t* ref = nullptr;     // the first non-empty task: the launch's gh_fmt / rows_bias_k
-  for (int i = 0; i < ntasks; ++i) {
-    const ddp_conv_task_t& T = tasks[i];
-    if (T.n_edges <= 0) continue;
-    if (!ref) ref = &T;
-    if (T.gh_fmt != ref->gh_fmt || (unsigned)T.gh_fmt > 1u) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: the tasks of a launch carry one plane form of G (gh_fmt 0 or 1)");
-    if (T.rows_seg0 < 0 || T.rows_seg1 < 0 || T.rows_nts < 0 || (T.rows_seg1 > 0 && (T.rows_seg1 <= T.rows_seg0 || T.rows_nts < nct1)) ||
-        (T.rows_nts > nts) || (T.rows_seg1 > 0 && !T.rows_bias_k))      // (a range's bias table is fc.0's: rows_bias_k)
-      return ddp_fail(DDP_EINVAL, "ddp_conv_rows: task.rows_seg0 / rows_seg1 / rows_nts");
-    if (T.rows_bias_k != ref->rows_bias_k || (unsigned)T.rows_bias_k > 1u || (T.rows_bias_k && (shape->hid & 15) == 0))
-      return ddp_fail(DDP_EINVAL, "ddp_conv_rows: rows_bias_k is 0 or 1 for all tasks of a launch and needs hid % 16 != 0");
-    if (T.n_edges_dev) L.dev_counts = 1;
-    L.tile_start[L.ntasks] = tiles;
-    L.task[L.ntasks] = T;
-    tiles += (T.n_edges + R16_ET - 1) / R16_ET;
-    ++L.ntasks;
-  }
-  L.tile_start[L.ntasks] = tiles;
-  if (tiles == 0) return 0;
-  RL.nts = nts;
-  if (frows > R16_FROWS) frows = R16_FROWS;          // (larger blocks build their features in chunks)
-  RL.frows = frows;
-  int fbytes = frows * R16_FS * 4;
-  fbytes = (fbytes + 127) / 128 * 128;
-  RL.aux_off = fbytes;
-  int priv = fbytes + (int)sizeof(R16Aux);
-  if (priv < NS * 1024) priv = NS * 1024;          // the lo plane of edge_attr_ during fc1
-  priv = (priv + 127) / 128 * 128;
-  RL.priv_bytes = priv;
-  RL.bias_tiles = ref->rows_bias_k ? nct1 : nts;
-  RL.bias_bytes = (RL.bias_tiles * 128 + 127) / 128 * 128;
-  size_t lds_bytes = (size_t)2 * (NS * 1024) + RL.bias_bytes + (size_t)R16_NW * priv;
-  if (2 * lds_bytes > 160 * 1024) return ddp_fail(DDP_ELIMIT, "ddp_conv_rows: LDS budget of two workgroups per CU exceeded (too many vector features per block)");
-  if ((size_t)ddp_shape_rows_min_lds > lds_bytes) lds_bytes = (size_t)ddp_shape_rows_min_lds;
+  RL.L = P.L;
+  RL.nts = P.nts;
+  RL.bias_tiles = P.bias_tiles;
+  RL.bias_bytes = P.bias_bytes;
+  RL.priv_bytes = P.priv_bytes;
+  RL.aux_off = P.aux_off;
+  RL.frows = P.frows;
   static int lds_have[6] = {0, 0, 0, 0, 0, 0};
   hipError_t err;
-  const int gf = ref->gh_fmt;
-  const bool direct = shape->g_cols[0] == 0 && shape->g_cols[1] == 0;
-#define R16_LAUNCH(SZ_, GF_, I_)                                                                                             \
-  {                                                                                                                          \
-    err = ddp_need_lds(reinterpret_cast<const void*>(ddp_conv_rows16_kernel<SZ_, GF_>), (int)lds_bytes, &lds_have[I_]);      \
-    if (err != hipSuccess) return ddp_fail_hip(err, "hipFuncSetAttribute(conv rows16)");                                    \
-    hipLaunchKernelGGL((ddp_conv_rows16_kernel<SZ_, GF_>), dim3(tiles), dim3(R16_NT), lds_bytes, (hipStream_t)stream, RL);   \
-  }
-#define R16_LAUNCH_D(SZ_, I_)                                                                                                \
-  {                                                                                                                          \
-    err = ddp_need_lds(reinterpret_cast<const void*>(ddp_conv_rows16_direct_kernel<SZ_>), (int)lds_bytes, &lds_have[I_]);    \
-    if (err != hipSuccess) return ddp_fail_hip(err, "hipFuncSetAttribute(conv rows16)");                                    \
-    hipLaunchKernelGGL((ddp_conv_rows16_direct_kernel<SZ_>), dim3(tiles), dim3(R16_NT), lds_bytes, (hipStream_t)stream, RL); \
-  }
+  const bool direct = P.L.shape.g_cols[0] == 0 && P.L.shape.g_cols[1] == 0;
   if (direct) {
-    if (sc == 60) R16_LAUNCH_D(60, 4) else R16_LAUNCH_D(32, 5)
-  } else if (sc == 60) {
-    if (gf == 1) R16_LAUNCH(60, 1, 2) else R16_LAUNCH(60, 0, 0)
+    if (P.sc == 60) ROWS_LAUNCH((ddp_conv_rows16_direct_kernel<60>), 4, "hipFuncSetAttribute(conv rows16)")
+    else ROWS_LAUNCH((ddp_conv_rows16_direct_kernel<32>), 5, "hipFuncSetAttribute(conv rows16)")
+  } else if (P.sc == 60) {
+    if (P.gh_fmt == 1) ROWS_LAUNCH((ddp_conv_rows16_kernel<60, 1>), 2, "hipFuncSetAttribute(conv rows16)")
+    else ROWS_LAUNCH((ddp_conv_rows16_kernel<60, 0>), 0, "hipFuncSetAttribute(conv rows16)")
   } else {
-    if (gf == 1) R16_LAUNCH(32, 1, 3) else R16_LAUNCH(32, 0, 1)
+    if (P.gh_fmt == 1) ROWS_LAUNCH((ddp_conv_rows16_kernel<32, 1>), 3, "hipFuncSetAttribute(conv rows16)")
+    else ROWS_LAUNCH((ddp_conv_rows16_kernel<32, 0>), 1, "hipFuncSetAttribute(conv rows16)")
   }
-#undef R16_LAUNCH
-#undef R16_LAUNCH_D
   err = hipGetLastError();
   if (err != hipSuccess) return ddp_fail_hip(err, "ddp_conv_rows (16x16x32 form) launch");
   return 0;

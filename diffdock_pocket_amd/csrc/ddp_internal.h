@@ -18,9 +18,6 @@ static inline hipError_t ddp_need_lds(const void* kernel, int bytes, int* have) 
   return err;
 }
 
-// csrc/ddp_conv_rows16.hip: the launch of ddp_conv_rows for tasks with rows_form = 1 (arguments validated by ddp_conv_rows; sc = size class)
-int ddp_conv_rows16_launch(const ddp_conv_shape_t* shape, const ddp_conv_task_t* tasks, int ntasks, int sc, void* stream);
-
 // Occupancy shaping (ddp_set_occupancy_shaping, include/ddp_hip.h): launch-time LDS floors that decide how many workgroups of a kernel
 // share a CU.  Plain ints read when a launch is enqueued.
 extern int ddp_shape_rows_min_lds;      // ddp_conv_rows: dynamic LDS of a launch is at least this many bytes
