@@ -5,7 +5,8 @@ from .batch import HeteroBatch, Store, collate, set_time  # noqa: F401
 from .diffusion import SigmaRanges, get_t_schedule, get_timestep_embedding, sinusoidal_embedding, t_to_sigma  # noqa: F401
 
 __all__ = ["HeteroBatch", "Store", "collate", "set_time", "SigmaRanges", "get_t_schedule", "get_timestep_embedding",
-           "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize"]
+           "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize", "PoseRefiner",
+           "RefineConfig", "RefineResult"]
 
 
 def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ctypes binding
@@ -18,4 +19,7 @@ def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ct
     if name in ("PoseEvaluator", "PoseClusters", "summarize"):
         from . import evaluation
         return getattr(evaluation, name)
+    if name in ("PoseRefiner", "RefineConfig", "RefineResult"):
+        from . import refine
+        return getattr(refine, name)
     raise AttributeError(name)

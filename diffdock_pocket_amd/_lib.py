@@ -21,7 +21,7 @@ DDP_EVAL_MAX_ATOMS = 1024
 DDP_PAIRWISE_MAX_SAMPLES, DDP_CLUSTER_MAX_SAMPLES = 32768, 1024
 EXPORTS = ["ddp_conv_messages", "ddp_conv_rows", "ddp_stage_a_gh", "ddp_stage_a_gh3", "ddp_segment_reduce", "ddp_edge_featurize", "ddp_edge_featurize_jobs", "ddp_torsion_sh", "ddp_stage_a", "ddp_stage_a_h2",
            "ddp_pose_update", "ddp_sidechain_update", "ddp_sde_update", "ddp_radius_count", "ddp_radius_fill", "ddp_knn", "ddp_group_by_key", "ddp_node_linear", "ddp_scan_jobs", "ddp_mark_jobs", "ddp_rowcopy_jobs", "ddp_select_jobs",
-           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
+           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
 
 
 class Seg(C.Structure):
@@ -101,6 +101,15 @@ class SvgdArgs(C.Structure):
     _fields_ = [("pos", _P), ("n", _I), ("n_lig", _I), ("n_tor", _I), ("dihedrals", _P), ("score", _P * 3), ("upd", _P * 3), ("gdt", _P),
                 ("weight", C.c_float), ("w_rep", C.c_float), ("w_rot", C.c_float), ("w_tor", C.c_float), ("svgd_only", _I),
                 ("tau", _P), ("tr_diff", _P), ("rot_diff", _P), ("tor_diff", _P), ("dist", _P)]
+
+
+class RefineArgs(C.Structure):
+    """ddp_refine_args_t of include/ddp_hip.h."""
+    _fields_ = [("n_samples", _I), ("n", _I), ("m", _I), ("rec_stride", _I), ("n_tor", _I), ("pos", _P), ("anchor", _P), ("lig_radii", _P),
+                ("rec", _P), ("rec_radii", _P), ("self_pairs", _P), ("overlap", C.c_double), ("restraint", C.c_double), ("energy", _P),
+                ("grad", _P), ("bonds", _P), ("mask_rotate", _P), ("step", _P), ("tr", _P), ("rot", _P), ("tor", _P), ("trial", _P),
+                ("trial_energy", _P), ("trial_grad", _P), ("accepted", _P), ("grow", C.c_double), ("shrink", C.c_double),
+                ("step_max", C.c_double)]
 
 
 class GroupJob(C.Structure):
@@ -265,6 +274,9 @@ def load():
     lib.ddp_traj_record.restype = C.c_int
     for name in ("ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows"):
         getattr(lib, name).argtypes = [C.POINTER(SvgdArgs), C.c_void_p]
+        getattr(lib, name).restype = C.c_int
+    for name in ("ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept"):
+        getattr(lib, name).argtypes = [C.POINTER(RefineArgs), C.c_void_p]
         getattr(lib, name).restype = C.c_int
     if lib.ddp_abi_version() != 17:
         raise DdpError("libddp_hip.so ABI version mismatch")

@@ -1,0 +1,268 @@
+// ddp_refine.hip - steric-clash relief of sampled poses in pose space (include/ddp_hip.h, ddp_refine_energy / ddp_refine_direction /
+// ddp_refine_accept; host side diffdock_pocket_amd/refine.py).  This project's own algorithm, not the reference's --relax (an OpenMM
+// minimisation): a clash penalty on the clash rule of ddp_pose_contacts plus a restraint to the sampled pose, descended along the
+// sampler's own degrees of freedom (translation, rotation, torsions) through ddp_pose_update, with a per-sample backtracking line
+// search whose state (energies, step sizes, accept counters) lives in device memory.
+// ddp_pose_update re-aligns the conformer after the torsions, so the torsion component of the search direction is NOT the exact
+// derivative of the map that is applied: the direction is a heuristic, the strict accept rule of ddp_refine_accept (E(trial) < E(x)
+// in fp64) is what guarantees descent.
+// One 256-thread workgroup per sample.  All arithmetic is fp64 on the fp32 inputs (converted first).  Every sum has a fixed order:
+// a wave owns an output (a ligand atom, a rotatable bond), its 64 lanes stride over the summands, a butterfly of __shfl_xor (every
+// stage adds two equal-rank partial sums, fp64 addition is commutative: all lanes end with the same bits), and sums over waves run in
+// wave order.  No atomics: two launches give the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "ddp_hip.h"
+#include "ddp_internal.h"
+
+#define DDP_REFINE_THREADS 256
+#define DDP_REFINE_WAVES (DDP_REFINE_THREADS / 64)
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// max(0, t - d)^2 of one pair and its gradient with respect to the first atom, added to e and (gx, gy, gz).  The square root is
+// taken only where d^2 < t^2 can hold; the comparison is written so that a NaN distance goes through and poisons the sums (a NaN
+// energy is never accepted).  d = 0: the energy term counts, the gradient term is zero.
+__device__ __forceinline__ void pair_term(double dx, double dy, double dz, double t, double& e, double& gx, double& gy, double& gz) {
+  const double d2 = dx * dx + dy * dy + dz * dz;
+  if (d2 >= t * t) return;
+  const double d = sqrt(d2);
+  const double p = t - d;
+  if (p <= 0.0) return;
+  e += p * p;
+  if (d == 0.0) return;
+  const double k = -2.0 * p / d;
+  gx += k * dx; gy += k * dy; gz += k * dz;
+}
+
+// ---- energy[s] = [E_cross, E_self, E_rest, total], grad[s][i] = dE/dx_i.  LDS: the sample's ligand coordinates and radii (fp32, as
+// ddp_pose_contacts stages them), one fp64 gradient accumulator per ligand atom, and a tile of DDP_REFINE_TILE receptor atoms
+// (x, y, z, radius).  The receptor is streamed through that tile, all 256 threads loading one tile with coalesced reads: a wave that
+// read the receptor from global memory inside its pair loop waited one L2 round trip per 64 pairs (measured on 40 poses of 3dpf:
+// 180 us per iteration of the refinement against 125 us with the tile).  Wave w owns the ligand atoms i = w, w + 4, ...: for every tile its lanes stride over the
+// tile's atoms, the butterfly gives the tile's contribution to atom i, and lane 0 adds it to the atom's accumulator (tiles in
+// increasing order: a fixed order).  Then the lanes stride over the ligand atoms j with self_pairs[min(i, j)][max(i, j)] (every self
+// pair is met from both ends and counts half each time: exact) and lane 0 adds the restraint term of atom i.  Per-wave energy
+// partials are summed in that fixed order and over the waves in wave order.
+#define DDP_REFINE_TILE 1024
+__global__ __launch_bounds__(DDP_REFINE_THREADS) void ddp_refine_energy_kernel(const ddp_refine_args_t A) {
+  extern __shared__ float4 tile[];                        // [DDP_REFINE_TILE] (first: 16-byte aligned whatever n is)
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m;
+  double* gacc = (double*)(tile + DDP_REFINE_TILE);       // [n][3]
+  float* x = (float*)(gacc + 3 * n);                      // [n][3]
+  float* rad = x + 3 * n;                                 // [n]
+  __shared__ double we[DDP_REFINE_WAVES][3];
+  const float* __restrict__ ls = A.pos + (size_t)s * n * 3;
+  const float* __restrict__ as = A.anchor + (size_t)s * n * 3;
+  const float* __restrict__ rs = A.rec + (size_t)s * A.rec_stride;
+  for (int i = tid; i < 3 * n; i += DDP_REFINE_THREADS) { x[i] = ls[i]; gacc[i] = 0.0; }
+  for (int i = tid; i < n; i += DDP_REFINE_THREADS) rad[i] = A.lig_radii[i];
+  const double two_ov = 2.0 * A.overlap;
+  const double krest = 2.0 * A.restraint / (double)n;
+  double ec_w = 0.0, es_w = 0.0, er_w = 0.0;     // this wave's atoms, in a fixed order (all lanes hold the same values)
+  for (int j0 = 0; j0 < m; j0 += DDP_REFINE_TILE) {
+    const int mt = min(DDP_REFINE_TILE, m - j0);
+    __syncthreads();                             // the previous tile has been used (first pass: x, rad, gacc are visible)
+    for (int j = tid; j < mt; j += DDP_REFINE_THREADS)
+      tile[j] = make_float4(rs[3 * (j0 + j)], rs[3 * (j0 + j) + 1], rs[3 * (j0 + j) + 2], A.rec_radii[j0 + j]);
+    __syncthreads();
+    for (int i = wave; i < n; i += DDP_REFINE_WAVES) {
+      const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2], ri = rad[i];
+      double ec = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+      for (int j = lane; j < mt; j += 64) {
+        const float4 r = tile[j];
+        if (r.w < 0.f) continue;                 // a receptor hydrogen
+        const double t = ri + (double)r.w - two_ov;
+        if (t <= 0.0) continue;
+        pair_term(xi - (double)r.x, yi - (double)r.y, zi - (double)r.z, t, ec, gx, gy, gz);
+      }
+      ec = wave_sum(ec); gx = wave_sum(gx); gy = wave_sum(gy); gz = wave_sum(gz);
+      ec_w += ec;
+      if (lane == 0) { gacc[3 * i] += gx; gacc[3 * i + 1] += gy; gacc[3 * i + 2] += gz; }   // (atom i is this wave's alone)
+    }
+  }
+  __syncthreads();                               // m = 0: x and rad are visible
+  for (int i = wave; i < n; i += DDP_REFINE_WAVES) {
+    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2], ri = rad[i];
+    double es = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+    if (A.self_pairs) {
+      for (int j = lane; j < n; j += 64) {
+        if (j == i || !A.self_pairs[(size_t)min(i, j) * n + max(i, j)]) continue;
+        const double t = ri + (double)rad[j] - two_ov;
+        if (t <= 0.0) continue;
+        pair_term(xi - (double)x[3 * j], yi - (double)x[3 * j + 1], zi - (double)x[3 * j + 2], t, es, gx, gy, gz);
+      }
+      es = wave_sum(es); gx = wave_sum(gx); gy = wave_sum(gy); gz = wave_sum(gz);
+    }
+    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
+    es_w += 0.5 * es; er_w += ax * ax + ay * ay + az * az;
+    if (lane == 0 && A.grad) {
+      double* g = A.grad + ((size_t)s * n + i) * 3;
+      g[0] = gacc[3 * i] + gx + krest * ax; g[1] = gacc[3 * i + 1] + gy + krest * ay; g[2] = gacc[3 * i + 2] + gz + krest * az;
+    }
+  }
+  if (lane == 0) { we[wave][0] = ec_w; we[wave][1] = es_w; we[wave][2] = er_w; }
+  __syncthreads();
+  if (tid == 0) {
+    double ec = we[0][0], es = we[0][1], er = we[0][2];
+    for (int w = 1; w < DDP_REFINE_WAVES; ++w) { ec += we[w][0]; es += we[w][1]; er += we[w][2]; }
+    er = A.restraint * (er / (double)n);
+    double* e = A.energy + 4 * (size_t)s;
+    e[0] = ec; e[1] = es; e[2] = er; e[3] = ec + es + er;
+  }
+}
+
+static int refine_common(const ddp_refine_args_t* a, const char* who, int* rc) {
+  // shared shape checks; returns 1 when the call is a no-op or failed (*rc holds the result)
+  static thread_local char msg[96];
+  *rc = 0;
+  if (!a) { *rc = ddp_fail(DDP_EINVAL, "ddp_refine: null argument struct"); return 1; }
+  if (a->n_samples == 0) return 1;
+  if (a->n_samples < 0 || a->n <= 0 || a->m < 0 || a->n_tor < 0 || (a->rec_stride != 0 && a->rec_stride < 3 * a->m)) {
+    snprintf(msg, sizeof msg, "%s: shape", who);
+    *rc = ddp_fail(DDP_EINVAL, msg);
+    return 1;
+  }
+  if (a->n > DDP_EVAL_MAX_ATOMS) {
+    snprintf(msg, sizeof msg, "%s: more than DDP_EVAL_MAX_ATOMS ligand atoms", who);
+    *rc = ddp_fail(DDP_ELIMIT, msg);
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int ddp_refine_energy(const ddp_refine_args_t* a, void* stream) {
+  int rc;
+  if (refine_common(a, "ddp_refine_energy", &rc)) return rc;
+  if (!a->pos || !a->anchor || !a->lig_radii || !a->energy || (a->m > 0 && (!a->rec || !a->rec_radii)))
+    return ddp_fail(DDP_EINVAL, "ddp_refine_energy: null argument");
+  if (!(a->restraint >= 0.0)) return ddp_fail(DDP_EINVAL, "ddp_refine_energy: restraint < 0");
+  // the receptor tile + gradient accumulators + ligand coordinates and radii: 16 KiB + 40 n, 56 KiB at the atom limit
+  const size_t lds = DDP_REFINE_TILE * sizeof(float4) + (size_t)3 * a->n * sizeof(double) + (size_t)4 * a->n * sizeof(float);
+  hipLaunchKernelGGL(ddp_refine_energy_kernel, dim3(a->n_samples), dim3(DDP_REFINE_THREADS), lds, (hipStream_t)stream, *a);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_refine_energy launch");
+  return 0;
+}
+
+// ---- search direction of sample s, each degree of freedom scaled by its unit-mass inertia and multiplied by step[s]:
+//   tr = -sum g_i / n,   rot = -sum (x_i - c) x g_i / sum |x_i - c|^2,   tor[b] = -sum g_i . a_i / sum |a_i|^2 over mask_rotate[b],
+//   a_i = u^ x (x_i - x_v), u^ = (x_u - x_v) / |x_u - x_v| (axis and sense of ddp_pose_update; atoms u and v themselves are left out of
+//   the sums: their lever is zero); a zero denominator gives 0.
+// Block sums: lanes stride over the atoms, butterfly, the waves in wave order.  Bonds: wave w owns b = w, w + 4, ...
+__device__ __forceinline__ void block_sum(double* v, int K, double (*red)[8], int lane, int wave) {
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  __syncthreads();                               // red is free again
+  if (lane == 0)
+    for (int k = 0; k < K; ++k) red[wave][k] = v[k];
+  __syncthreads();
+  for (int k = 0; k < K; ++k) {
+    double acc = red[0][k];
+    for (int w = 1; w < DDP_REFINE_WAVES; ++w) acc += red[w][k];
+    v[k] = acc;
+  }
+}
+
+__global__ __launch_bounds__(DDP_REFINE_THREADS) void ddp_refine_direction_kernel(const ddp_refine_args_t A) {
+  __shared__ double red[DDP_REFINE_WAVES][8];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, T = A.n_tor;
+  const float* __restrict__ x = A.pos + (size_t)s * n * 3;
+  const double* __restrict__ g = A.grad + (size_t)s * n * 3;
+  const double step = A.step[s];
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += DDP_REFINE_THREADS) {
+    v[0] += (double)x[3 * i]; v[1] += (double)x[3 * i + 1]; v[2] += (double)x[3 * i + 2];
+    v[3] += g[3 * i]; v[4] += g[3 * i + 1]; v[5] += g[3 * i + 2];
+  }
+  block_sum(v, 6, red, lane, wave);
+  const double cx = v[0] / n, cy = v[1] / n, cz = v[2] / n;
+  if (tid == 0) {
+    A.tr[3 * s] = (float)(step * (-v[3] / n)); A.tr[3 * s + 1] = (float)(step * (-v[4] / n)); A.tr[3 * s + 2] = (float)(step * (-v[5] / n));
+  }
+  double r[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += DDP_REFINE_THREADS) {
+    const double px = (double)x[3 * i] - cx, py = (double)x[3 * i + 1] - cy, pz = (double)x[3 * i + 2] - cz;
+    const double gx = g[3 * i], gy = g[3 * i + 1], gz = g[3 * i + 2];
+    r[0] += py * gz - pz * gy; r[1] += pz * gx - px * gz; r[2] += px * gy - py * gx;
+    r[3] += px * px + py * py + pz * pz;
+  }
+  block_sum(r, 4, red, lane, wave);
+  if (tid == 0) {
+    for (int k = 0; k < 3; ++k) A.rot[3 * s + k] = (float)(step * (r[3] == 0.0 ? 0.0 : -r[k] / r[3]));
+  }
+  for (int b = wave; b < T; b += DDP_REFINE_WAVES) {
+    const int u = A.bonds[2 * b], w = A.bonds[2 * b + 1];
+    double num = 0.0, den = 0.0;
+    if (u >= 0 && u < n && w >= 0 && w < n) {    // an entry outside the ligand: no read, the bond gets 0
+      const double vx = x[3 * w], vy = x[3 * w + 1], vz = x[3 * w + 2];
+      double ux = (double)x[3 * u] - vx, uy = (double)x[3 * u + 1] - vy, uz = (double)x[3 * u + 2] - vz;
+      const double len = sqrt(ux * ux + uy * uy + uz * uz);
+      ux /= len; uy /= len; uz /= len;
+      const uint8_t* __restrict__ mk = A.mask_rotate + (size_t)b * n;
+      for (int i = lane; i < n; i += 64) {
+        if (!mk[i] || i == u || i == w) continue;  // the bond's own atoms lie on the axis: no lever, exactly
+        const double px = (double)x[3 * i] - vx, py = (double)x[3 * i + 1] - vy, pz = (double)x[3 * i + 2] - vz;
+        const double ax = uy * pz - uz * py, ay = uz * px - ux * pz, az = ux * py - uy * px;
+        num += g[3 * i] * ax + g[3 * i + 1] * ay + g[3 * i + 2] * az;
+        den += ax * ax + ay * ay + az * az;
+      }
+    }
+    num = wave_sum(num); den = wave_sum(den);
+    if (lane == 0) A.tor[(size_t)s * T + b] = (float)(step * (den == 0.0 ? 0.0 : -num / den));
+  }
+}
+
+extern "C" int ddp_refine_direction(const ddp_refine_args_t* a, void* stream) {
+  int rc;
+  if (refine_common(a, "ddp_refine_direction", &rc)) return rc;
+  if (!a->pos || !a->grad || !a->step || !a->tr || !a->rot || (a->n_tor > 0 && (!a->tor || !a->bonds || !a->mask_rotate)))
+    return ddp_fail(DDP_EINVAL, "ddp_refine_direction: null argument");
+  hipLaunchKernelGGL(ddp_refine_direction_kernel, dim3(a->n_samples), dim3(DDP_REFINE_THREADS), 0, (hipStream_t)stream, *a);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_refine_direction launch");
+  return 0;
+}
+
+// ---- the line search's decision, per sample: trial_energy[s][3] < energy[s][3] (strict, fp64; false for NaN) takes the trial pose,
+// its energies and its gradient bit for bit, step = min(grow * step, step_max), accepted += 1; otherwise nothing but step *= shrink
+// is written.  Every thread reads the two energies before the barrier, thread 0 overwrites them after it.
+__global__ __launch_bounds__(DDP_REFINE_THREADS) void ddp_refine_accept_kernel(const ddp_refine_args_t A) {
+  const int s = blockIdx.x, tid = threadIdx.x, n = A.n;
+  double* e = A.energy + 4 * (size_t)s;
+  const double* et = A.trial_energy + 4 * (size_t)s;
+  const bool take = et[3] < e[3];
+  __syncthreads();
+  if (tid == 0) {
+    const double st = A.step[s];
+    A.step[s] = take ? fmin(A.grow * st, A.step_max) : A.shrink * st;
+    if (take) A.accepted[s] += 1;
+  }
+  if (!take) return;
+  if (tid < 4) e[tid] = et[tid];
+  float* x = A.pos + (size_t)s * n * 3;
+  const float* xt = A.trial + (size_t)s * n * 3;
+  for (int i = tid; i < 3 * n; i += DDP_REFINE_THREADS) x[i] = xt[i];
+  if (A.grad && A.trial_grad) {
+    double* g = A.grad + (size_t)s * n * 3;
+    const double* gt = A.trial_grad + (size_t)s * n * 3;
+    for (int i = tid; i < 3 * n; i += DDP_REFINE_THREADS) g[i] = gt[i];
+  }
+}
+
+extern "C" int ddp_refine_accept(const ddp_refine_args_t* a, void* stream) {
+  int rc;
+  if (refine_common(a, "ddp_refine_accept", &rc)) return rc;
+  if (!a->pos || !a->trial || !a->energy || !a->trial_energy || !a->step || !a->accepted || (!a->grad) != (!a->trial_grad))
+    return ddp_fail(DDP_EINVAL, "ddp_refine_accept: null argument");
+  hipLaunchKernelGGL(ddp_refine_accept_kernel, dim3(a->n_samples), dim3(DDP_REFINE_THREADS), 0, (hipStream_t)stream, *a);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_refine_accept launch");
+  return 0;
+}

@@ -379,6 +379,27 @@ class PoseEvaluator:
             return PoseMetrics(rmsd, plain, best, c[:, 3].contiguous(), c[:, 1].contiguous(), c[:, 2].contiguous(), c[:, 0].to(torch.int32),
                                sc, self.symmetry_corrected)
 
+    def contact_tables(self, on_device: bool, atom_pos: Optional[torch.Tensor] = None):
+        """(lig_radii [n], receptor coordinates [m, 3] or [S, m, 3], rec_radii [m]) that the contacts pass uses, on the evaluator's
+        device (on_device) or on the host: the van der Waals radii of the ligand, the receptor of `receptor=` - or, for a graph
+        receptor and a given atom_pos [S, n_a, 3], each sample's own atom positions - and its radii (negative: a hydrogen)."""
+        t = self._dev if on_device else self._cpu
+        return t["lig_r"], self._receptor(t, atom_pos), t["rec_r"]
+
+    def contacts(self, lig_pos: torch.Tensor, atom_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[S, 4] fp32 = clashes, min_cross, min_self, centroid of the poses alone (the contacts pass of `evaluate`, without the RMSDs),
+        on the poses' device."""
+        self._check_lig(lig_pos)
+        lig = lig_pos.float().contiguous()
+        apos = None if atom_pos is None else atom_pos.float().contiguous()
+        if lig.is_cuda:
+            from . import launch as LA
+            t = self._dev
+            with torch.cuda.device(lig.device):
+                return LA.pose_contacts(lig, t["lig_r"], self._receptor(t, apos), t["rec_r"], t["ref_centroid"], self.overlap)
+        t = self._cpu
+        return _contacts_torch(lig, t["lig_r"], self._receptor(t, apos), t["rec_r"], t["ref_centroid"], self.overlap)
+
     def _check_lig(self, lig_pos):
         if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
             raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")

@@ -33,6 +33,7 @@ from . import inputs as I
 from . import outputs as O
 from .diffusion import get_t_schedule
 from .evaluation import PoseClusters, PoseEvaluator, PoseMetrics  # noqa: F401
+from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 
 
@@ -49,6 +50,9 @@ class ComplexResult:
     lig_traj: Optional[torch.Tensor] = None        # save_visualisation: [N, steps + 1, n_lig, 3] reverse process, ranked order
     atom_traj: Optional[torch.Tensor] = None       # save_visualisation, flexible row: [N, steps + 1, n_moving, 3], ranked order
     clusters: Optional["PoseClusters"] = None      # run_csv(cluster_rmsd=X): evaluation.PoseClusters of the ranked poses (binding modes)
+    refined_pos: Optional[torch.Tensor] = None     # run_csv(resolve_clashes=cfg): [N, n_lig, 3] the ranked poses after clash relief
+    refine: Optional["RefineResult"] = None        # run_csv(resolve_clashes=cfg): refine.RefineResult of the ranked poses (host tensors)
+    refined_metrics: Optional["PoseMetrics"] = None  # resolve_clashes with evaluate=True: PoseMetrics of refined_pos (`metrics` is untouched)
 
 
 def _none(v):
@@ -112,7 +116,8 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             esm_embeddings=None, root: str = "", seed: int = 0, rank: int = 0, world: int = 1, shard: str = "samples",
             dist=None, sampler_cfg: Optional[SamplerConfig] = None, graph_kwargs: Optional[Dict] = None,
             allow_zero_esm: bool = False, evaluate: bool = False, out_dir: Optional[str] = None,
-            save_visualisation: bool = False, cluster_rmsd: Optional[float] = None) -> List[ComplexResult]:
+            save_visualisation: bool = False, cluster_rmsd: Optional[float] = None,
+            resolve_clashes: Optional[RefineConfig] = None) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -138,7 +143,14 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     cluster_rmsd=X: every processed row also gets `clusters` (evaluation.PoseEvaluator.cluster: the symmetry-corrected RMSD of every
     pair of the gathered poses and their greedy grouping into binding modes at cutoff X, in ranked order: mode 0 holds rank 1), and
     with out_dir the complex directory also gets modes.csv (outputs.write_modes_csv).  Needs no known pose.  A failure skips the row
-    like a failure of the evaluation.  None: nothing is computed or written."""
+    like a failure of the evaluation.  None: nothing is computed or written.
+
+    resolve_clashes=RefineConfig(...): after the ranking, the gathered poses also go through refine.PoseRefiner (this package's own
+    clash relief in pose space, not the reference's --relax): `refined_pos` and `refine` in ranked order, with evaluate=True also
+    `refined_metrics`.  Rigid rows are refined against the row's full PDB, flexible rows against each sample's own atom nodes, as the
+    evaluation chooses.  With out_dir the complex directory also gets rank{k}_resolved.sdf per pose and clashes.csv
+    (outputs.write_clashes_csv).  Nothing that exists without it changes: ligand_pos, confidences, order, metrics and every other
+    file are the same.  A failure skips the row like a failure of the evaluation.  None: nothing is computed or written."""
     if sampler_cfg is not None and sampler_cfg.svgd_weight > 0:
         # the samples of a complex interact: a row's sampler would raise inside the per-row try and the row would only be skipped
         if shard == "samples" and world > 1:
@@ -148,7 +160,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             raise ValueError("svgd_weight > 0 needs at least 3 samples per complex")
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
-            shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd)
+            shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd, resolve_clashes)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(*args)
@@ -165,7 +177,7 @@ def _all_ok(dist, ok: bool, device) -> bool:
 
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
              world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
-             save_visualisation=False, cluster_rmsd=None) -> List[ComplexResult]:
+             save_visualisation=False, cluster_rmsd=None, resolve_clashes=None) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if shard not in ("samples", "complexes"):
         raise ValueError(shard)
@@ -206,7 +218,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             smp.randomize()
             smp.run(schedule)
             lig = smp.lig_pos
-            if (evaluate and flex) or (out_dir is not None and moved):
+            if ((evaluate or resolve_clashes is not None) and flex) or (out_dir is not None and moved):
                 apos = smp.atom_pos.clone()
             if save_visualisation:
                 ltraj = smp.lig_traj.clone()
@@ -270,6 +282,20 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 res.ligand_pos = res.confidence = res.order = res.metrics = None
                 continue
             res.clusters = clusters
+        if resolve_clashes is not None:
+            refined = None
+            try:
+                refined = _refine_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order], resolve_clashes,
+                                      evaluate)
+            except Exception as e:      # noqa: BLE001
+                res.skipped = f"clash relief: {type(e).__name__}: {e}"
+            if split and not _all_ok(dist, refined is not None, device):
+                res.skipped = res.skipped or "skipped: clash relief failed on another rank"
+            if res.skipped is not None:
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = None
+                continue
+            res.refine, res.refined_metrics = refined
+            res.refined_pos = res.refine.lig_pos
         if save_visualisation:
             res.lig_traj = ltraj[order].cpu()
             res.atom_traj = atraj[order].cpu() if atraj is not None else None
@@ -286,6 +312,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 ok = False
             if not ok:
                 res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = res.clusters = None
+                res.refined_pos = res.refine = res.refined_metrics = None
                 res.files = []
     return out
 
@@ -299,7 +326,8 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
         with open(os.path.join(root, row["experimental_protein"])) as f:
             pdb_text = f.read()
     return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
-                           apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order)
+                           apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order,
+                           refine=res.refine)
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -311,6 +339,20 @@ def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
             rec = PoseEvaluator.full_receptor(f.read(), g.original_center)
         ev = PoseEvaluator(g, device, receptor=rec)
     return ev.evaluate(lig, apos).cpu()
+
+
+def _refine_row(row, root, g, device, flex, lig, apos, config, evaluate):
+    """(RefineResult, PoseMetrics or None) of the ranked poses of one row (see run_csv), on the host.  The receptor is the one
+    _evaluate_row scores against."""
+    if flex:
+        rf = PoseRefiner(g, device, config=config)
+    else:
+        with open(os.path.join(root, row["experimental_protein"])) as f:
+            rec = PoseEvaluator.full_receptor(f.read(), g.original_center)
+        rf = PoseRefiner(g, device, receptor=rec, config=config)
+    out = rf.refine(lig, apos if flex else None)
+    metrics = _evaluate_row(row, root, g, device, flex, out.lig_pos, apos) if evaluate else None
+    return out.cpu(), metrics
 
 
 def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
@@ -361,6 +403,12 @@ def _parser():
     p.add_argument("--svgd_tor_rel_weight", type=float, default=1.0)
     p.add_argument("--cluster_rmsd", type=float, default=None,
                    help="group the ranked poses into binding modes at this symmetry-corrected RMSD cutoff and write modes.csv (default: off)")
+    p.add_argument("--resolve_clashes", action="store_true", default=False,
+                   help="push the ranked poses out of steric clashes in pose space (this package's own refinement, no force field) and "
+                        "write rank{k}_resolved.sdf and clashes.csv beside the unchanged poses (default: off)")
+    p.add_argument("--resolve_clashes_iterations", type=int, default=RefineConfig.iterations)
+    p.add_argument("--resolve_clashes_restraint", type=float, default=RefineConfig.restraint,
+                   help="weight of the restraint to the sampled pose")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--esm_embeddings", type=str, default=None,
                    help="directory of <complex_name>.pt / .npy ESM rows, or one .pt file holding {complex_name: rows}")
@@ -401,6 +449,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  f"(models are not downloaded)")
     if a.filtering_model_dir is not None and not os.path.isfile(os.path.join(a.filtering_model_dir, "model_parameters.yml")):
         ap.error(f"--filtering_model_dir {a.filtering_model_dir!r} holds no model_parameters.yml")
+    if a.resolve_clashes_iterations < 0 or a.resolve_clashes_restraint < 0:
+        ap.error("--resolve_clashes_iterations and --resolve_clashes_restraint must not be negative")
     if a.samples_per_complex < 1 or a.inference_steps < 1:
         ap.error("--samples_per_complex and --inference_steps must be positive")
     device = torch.device(a.device or ("cuda:0" if torch.cuda.is_available() else "cpu"))
@@ -450,7 +500,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         res = run_csv(csv_path, model, device, confidence_model=conf_model, samples_per_complex=a.samples_per_complex,
                       inference_steps=a.inference_steps, esm_embeddings=esm, seed=a.seed, sampler_cfg=cfg, graph_kwargs=graph_kwargs,
                       allow_zero_esm=a.allow_zero_esm, out_dir=a.out_dir, save_visualisation=a.save_visualisation,
-                      cluster_rmsd=a.cluster_rmsd)
+                      cluster_rmsd=a.cluster_rmsd,
+                      resolve_clashes=RefineConfig(iterations=a.resolve_clashes_iterations, restraint=a.resolve_clashes_restraint)
+                      if a.resolve_clashes else None)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

@@ -705,3 +705,75 @@ def pose_cluster(dist, order=None, cutoff=2.0):
     L.check(L.load().ddp_pose_cluster(dist.data_ptr(), S, _p(order), float(cutoff), labels.data_ptr(), reps.data_ptr(), sizes.data_ptr(),
                                       count.data_ptr(), stream()), "ddp_pose_cluster")
     return labels, reps, sizes, count
+
+
+# ------------------------------------------------------------------------------------------------ clash relief (csrc/ddp_refine.hip)
+def refine_args(pos, anchor, lig_radii, rec, rec_radii, self_pairs=None, overlap=0.4, restraint=0.0, energy=None, grad=None,
+                bonds=None, mask_rotate=None, step=None, tr=None, rot=None, tor=None, trial=None, trial_energy=None, trial_grad=None,
+                accepted=None, grow=2.0, shrink=0.5, step_max=1024.0) -> L.RefineArgs:
+    """ddp_refine_args_t for the three ddp_refine_* entries, shapes and index tables checked here (the kernels trust them): pos, anchor,
+    trial [S, n, 3] fp32; lig_radii [n], rec [m, 3] or [S, m, 3], rec_radii [m] fp32; self_pairs uint8 [n, n]; energy, trial_energy
+    [S, 4], grad, trial_grad [S, n, 3], step [S] fp64; bonds int32 [T, 2] as refine_bonds returns it (its VALUES are not looked at
+    here: that would be a device-to-host copy, i.e. a synchronisation, per call), mask_rotate uint8 [T, n]; tr, rot
+    [S, 3], tor [S, T] fp32; accepted int32 [S].  Tensors an entry does not use may be None.  The struct holds raw addresses: the
+    caller keeps the tensors alive while it is in use."""
+    dev = pos.device
+    _eval_arg(pos, torch.float32, dev, "refine pos")
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise L.DdpError("refine: pos [S, n, 3]")
+    S, n = pos.shape[0], pos.shape[1]
+    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
+        raise L.DdpError("refine: rec [m, 3] or [S, m, 3]")
+    m = rec.shape[-2]
+    T = 0 if bonds is None else int(bonds.shape[0])
+    want = [(anchor, torch.float32, (S, n, 3), "anchor"), (lig_radii, torch.float32, (n,), "lig_radii"), (rec, torch.float32, None, "rec"),
+            (rec_radii, torch.float32, (m,), "rec_radii"), (self_pairs, torch.uint8, (n, n), "self_pairs"),
+            (energy, torch.float64, (S, 4), "energy"), (grad, torch.float64, (S, n, 3), "grad"), (bonds, torch.int32, (T, 2), "bonds"),
+            (mask_rotate, torch.uint8, (T, n), "mask_rotate"), (step, torch.float64, (S,), "step"), (tr, torch.float32, (S, 3), "tr"),
+            (rot, torch.float32, (S, 3), "rot"), (tor, torch.float32, (S, T), "tor"), (trial, torch.float32, (S, n, 3), "trial"),
+            (trial_energy, torch.float64, (S, 4), "trial_energy"), (trial_grad, torch.float64, (S, n, 3), "trial_grad"),
+            (accepted, torch.int32, (S,), "accepted")]
+    for t, dt, shape, what in want:
+        if t is None:
+            continue
+        _eval_arg(t, dt, dev, f"refine {what}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise L.DdpError(f"refine {what}: expected {shape}, got {tuple(t.shape)}")
+    if T > 0 and mask_rotate is None:
+        raise L.DdpError("refine: bonds without mask_rotate")
+    a = L.RefineArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, n_tor=T, overlap=float(overlap),
+                     restraint=float(restraint), grow=float(grow), shrink=float(shrink), step_max=float(step_max))
+    for name, t in (("pos", pos), ("anchor", anchor), ("lig_radii", lig_radii), ("rec", rec), ("rec_radii", rec_radii),
+                    ("self_pairs", self_pairs), ("energy", energy), ("grad", grad), ("bonds", bonds), ("mask_rotate", mask_rotate),
+                    ("step", step), ("tr", tr), ("rot", rot), ("tor", tor), ("trial", trial), ("trial_energy", trial_energy),
+                    ("trial_grad", trial_grad), ("accepted", accepted)):
+        setattr(a, name, _p(t) or None)
+    return a
+
+
+def refine_bonds(bonds, n: int, device) -> torch.Tensor:
+    """The rotatable-bond table of the ddp_refine_* entries: a HOST tensor [T, 2] of atom indices is checked against [0, n) here, on
+    the host, and then uploaded as int32 (once per complex).  A table with an entry outside the ligand raises; the device skips such
+    an entry without a read, but it is never handed one."""
+    b = torch.as_tensor(bonds)
+    if b.is_cuda:
+        raise L.DdpError("refine bonds: the table is validated on the host - pass the host tensor")
+    b = b.reshape(-1, 2).to(torch.int64)
+    if b.numel() and (int(b.min()) < 0 or int(b.max()) >= n):
+        raise L.DdpError(f"refine bonds: atom index outside [0, {n})")
+    return b.to(torch.int32).contiguous().to(device)
+
+
+def refine_energy(a: L.RefineArgs):
+    """ddp_refine_energy: energy (and grad, when given) of a.pos."""
+    L.check(L.load().ddp_refine_energy(C.byref(a), stream()), "ddp_refine_energy")
+
+
+def refine_direction(a: L.RefineArgs):
+    """ddp_refine_direction: tr / rot / tor = step * the inertia-scaled descent direction of a.grad at a.pos."""
+    L.check(L.load().ddp_refine_direction(C.byref(a), stream()), "ddp_refine_direction")
+
+
+def refine_accept(a: L.RefineArgs):
+    """ddp_refine_accept: the per-sample select between a.pos and a.trial."""
+    L.check(L.load().ddp_refine_accept(C.byref(a), stream()), "ddp_refine_accept")

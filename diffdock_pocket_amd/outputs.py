@@ -224,6 +224,26 @@ def write_modes_csv(path: str, clusters, confidence=None, order=None) -> str:
     return path
 
 
+# ---------------------------------------------------------------------------------------------- clash relief
+CLASHES_COLUMNS = ["rank", "sample", "clashes_before", "clashes_after", "energy_before", "energy_after", "rmsd_moved", "accepted_steps"]
+
+
+def write_clashes_csv(path: str, refine, order=None) -> str:
+    """clashes.csv of one complex: one row per pose in RANKED order (refine.RefineResult of the ranked poses).  rank counts from 1,
+    sample is the pose's index before ranking (order [N]; None: rank - 1); the energies are the total E of refine.py before and after
+    (clash terms + restraint), rmsd_moved in angstrom, accepted_steps the accepted trials of the line search."""
+    import csv
+    r = refine.cpu()
+    sample = list(range(r.lig_pos.shape[0])) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(CLASHES_COLUMNS)
+        for k in range(r.lig_pos.shape[0]):
+            w.writerow([k + 1, sample[k], int(r.clashes_before[k]), int(r.clashes_after[k]), f"{float(r.energy_before[k, 3]):.6g}",
+                        f"{float(r.energy_after[k, 3]):.6g}", f"{float(r.rmsd_moved[k]):.4f}", int(r.accepted[k])])
+    return path
+
+
 # ---------------------------------------------------------------------------------------------- one complex
 def complex_dir(out_dir: str, index: int, name: str) -> str:
     """reference inference.py:136."""
@@ -231,7 +251,7 @@ def complex_dir(out_dir: str, index: int, name: str) -> str:
 
 
 def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
-                  lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None) -> List[str]:
+                  lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None, refine=None) -> List[str]:
     """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
     ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
     lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
@@ -240,7 +260,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     Flexible: rank1_protein.pdb and rank{k}_confidence{c:.2f}_protein.pdb (rank{k}_protein.pdb).  Trajectories:
     rank{k}_reverseprocess.pdb and rank{k}_reverseprocess_protein.pdb, each of the ranked sample itself (the reference indexes the
     side-chain trajectories by rank instead of by sample, inference.py:276-279).
-    clusters (evaluation.PoseClusters of the ranked poses; order [N]: the sample index of each rank): also modes.csv."""
+    clusters (evaluation.PoseClusters of the ranked poses; order [N]: the sample index of each rank): also modes.csv.
+    refine (refine.RefineResult of the ranked poses): also rank{k}_resolved.sdf, the pose after clash relief, and clashes.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -279,4 +300,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
                 f.write(text)
     if clusters is not None:
         write_modes_csv(put(os.path.join(write_dir, "modes.csv")), clusters, confidence, order)
+    if refine is not None:
+        for k in range(refine.lig_pos.shape[0]):
+            write_sdf(put(os.path.join(write_dir, f"rank{k + 1}_resolved.sdf")), mol, refine.lig_pos[k], name, oc)
+        write_clashes_csv(put(os.path.join(write_dir, "clashes.csv")), refine, order)
     return written

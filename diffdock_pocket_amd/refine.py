@@ -1,0 +1,308 @@
+"""Relief of steric clashes of sampled poses, in pose space.  This project's own algorithm - NOT the reference's `--relax` (an OpenMM
+force-field minimisation, which stays out of this tree).  It needs no force field, only what the package already defines: the van
+der Waals table of assets/vdw_radii.json, the clash rule of ddp_pose_contacts (d < r_i + r_j - 2 overlap) and the sampler's own
+degrees of freedom through ddp_pose_update / modify_conformer, so bond lengths, angles and rings cannot change.
+
+Energy of one pose x against the pose x0 it started from, fp64 on the fp32 inputs (converted first), t_ij = r_i + r_j - 2 overlap,
+pairs with t_ij <= 0 never count, receptor hydrogens (negative radius) are ignored:
+
+    E = E_cross + E_self + E_rest
+    E_cross = sum_{i lig, j rec} max(0, t_ij - d_ij)^2
+    E_self  = the same sum over the ligand pairs of `self_pairs` (more than 3 bonds apart AND separated by a rotatable bond)
+    E_rest  = k * mean_i |x_i - x0_i|^2
+
+Search direction from the per-atom gradient g = dE/dx, each degree of freedom scaled by its unit-mass inertia (c the centroid,
+u^ the unit axis x_u - x_v of bond (u, v), a_i = u^ x (x_i - x_v) over the atoms the bond rotates, u and v themselves left out: they
+lie on the axis; a zero denominator gives 0):
+
+    d_tr = -sum g_i / n      d_rot = -sum (x_i - c) x g_i / sum |x_i - c|^2      d_tor[b] = -sum g_i . a_i / sum |a_i|^2
+
+One iteration, per sample with its own step size: trial = pose_update(x, step d_tr, step d_rot, step d_tor); the trial is taken iff
+E(trial) < E(x) strictly in fp64 (a NaN energy is never accepted) and then step = min(2 step, 1024); otherwise x is kept bit for
+bit and step = step / 2.  The pose update re-aligns the conformer after the torsions, so d_tor is not the exact derivative of the
+map that is applied: the direction is a heuristic and the accept rule is what guarantees that the energy never rises.  A fixed
+number of iterations, no convergence test, no host decision inside the loop.
+
+What it does not do: no attraction or electrostatic term (it can only push atoms apart), no side-chain or receptor motion (the
+receptor is static during the refinement), no hydrogens.
+
+Device tensors go through csrc/ddp_refine.hip (ddp_refine_direction, ddp_pose_update, ddp_refine_energy, ddp_refine_accept per
+iteration: energies, step sizes and accept counters stay in device memory, nothing synchronises); CPU tensors through the PyTorch
+fp64 form below with sampler.modify_conformer as the pose update."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from .evaluation import OVERLAP_DISTANCE, PoseEvaluator
+from .sampler import modify_conformer, modify_conformer_hip, rotate_index_lists, torsion_tables
+
+
+@dataclass
+class RefineConfig:
+    """The constants of the line search.  Untuned choices, not fitted to anything."""
+    iterations: int = 50          # fixed number of iterations
+    restraint: float = 0.1        # k of E_rest
+    step_init: float = 1.0        # first step size of every sample
+    step_grow: float = 2.0        # factor after an accepted trial
+    step_shrink: float = 0.5      # factor after a rejected trial
+    step_max: float = 1024.0      # cap of the step size
+
+
+@dataclass
+class RefineResult:
+    """Per-sample results of PoseRefiner.refine, in the order of the poses handed in, on their device."""
+    lig_pos: torch.Tensor          # [S, n, 3] fp32 refined poses
+    energy_before: torch.Tensor    # [S, 4] fp64: E_cross, E_self, E_rest, E
+    energy_after: torch.Tensor     # [S, 4]
+    clashes_before: torch.Tensor   # [S] int32, the clash count of PoseMetrics.clashes
+    clashes_after: torch.Tensor    # [S] int32
+    rmsd_moved: torch.Tensor       # [S] fp32 plain RMSD between the input and the refined pose
+    accepted: torch.Tensor         # [S] int32 accepted trials
+
+    def cpu(self) -> "RefineResult":
+        return RefineResult(**{k: v.cpu() for k, v in self.__dict__.items()})
+
+
+# ---------------------------------------------------------------------------------------------- host tables
+def ligand_torsions(graph):
+    """(bonds [T, 2] int64 (u, v), mask_rotate [T, n] bool) of a complex graph: sampler.torsion_tables, the tables a Sampler hands to
+    ddp_pose_update, checked against the ligand's size on the host."""
+    n = int(graph["ligand"].pos.shape[0])
+    bonds, mask = torsion_tables(graph)
+    bonds, mask = torch.as_tensor(bonds).long().reshape(-1, 2), mask.reshape(-1, n)
+    if mask.shape[0] != bonds.shape[0]:
+        raise ValueError(f"mask_rotate has {mask.shape[0]} rows for {bonds.shape[0]} rotatable bonds")
+    if bonds.numel() and (int(bonds.min()) < 0 or int(bonds.max()) >= n):
+        raise ValueError(f"rotatable bond outside the ligand's {n} atoms")
+    return bonds, mask
+
+
+def build_self_pairs(n: int, edge_index, mask_rotate) -> torch.Tensor:
+    """uint8 [n, n], upper triangle: pair (i, j), i < j, counts iff its topological distance in the ligand bond graph is greater
+    than 3 bonds (or there is no path) and some rotatable bond has mask_rotate[b][i] != mask_rotate[b][j], i.e. some torsion can
+    change the distance."""
+    ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
+    adj = np.zeros((n, n), dtype=bool)
+    ok = (ei >= 0).all(0) & (ei < n).all(0) & (ei[0] != ei[1])
+    adj[ei[0][ok], ei[1][ok]] = adj[ei[1][ok], ei[0][ok]] = True
+    near = np.eye(n, dtype=bool)                     # within 0 bonds
+    for _ in range(3):
+        near = near | ((near.astype(np.int64) @ adj.astype(np.int64)) > 0)
+    mask = np.asarray(mask_rotate, dtype=bool).reshape(-1, n)
+    split = (mask[:, :, None] != mask[:, None, :]).any(0) if mask.shape[0] else np.zeros((n, n), dtype=bool)
+    return torch.from_numpy(np.triu(~near & split, 1).astype(np.uint8))
+
+
+# ---------------------------------------------------------------------------------------------- the PyTorch fp64 form
+def _pair_terms(diff, t, ok):
+    """diff [..., 3] fp64, t thresholds, ok mask (broadcast) -> (sum of max(0, t - d)^2 over the last two pair axes, dE/d(first atom)
+    summed over the second)."""
+    d = diff.pow(2).sum(-1).sqrt()
+    pen = torch.where(ok, (t - d).clamp(min=0.0), torch.zeros_like(d))
+    unit = torch.where((d > 0).unsqueeze(-1), diff / d.unsqueeze(-1), torch.zeros_like(diff))
+    return pen.pow(2).sum((-1, -2)), ((-2.0 * pen).unsqueeze(-1) * unit).sum(-2)
+
+
+def energy_torch(x, anchor, lig_r, rec, rec_r, self_pairs, overlap, restraint):
+    """([S, 4] fp64 energies, [S, n, 3] fp64 gradient) of fp32 poses x against `anchor` - the definition of the module docstring."""
+    S, n = x.shape[0], x.shape[1]
+    x64, r64 = x.double(), lig_r.double()
+    m = rec.shape[-2]
+    e = torch.zeros(S, 4, dtype=torch.float64)
+    g = torch.zeros(S, n, 3, dtype=torch.float64)
+    t = r64[:, None] + rec_r.double()[None, :] - 2.0 * overlap
+    ok = (rec_r[None, :] >= 0) & (t > 0)
+    sp = None
+    if self_pairs is not None and n > 1:
+        sp = self_pairs.bool() | self_pairs.bool().T
+        ts = r64[:, None] + r64[None, :] - 2.0 * overlap
+        sp = sp & (ts > 0)
+    chunk = max(1, (1 << 23) // max(1, n * max(m, n) * 3))
+    for s0 in range(0, S, chunk):
+        xs = x64[s0:s0 + chunk]
+        if m > 0:
+            r = (rec[None] if rec.dim() == 2 else rec[s0:s0 + chunk]).double()
+            ec, gc = _pair_terms(xs[:, :, None, :] - r[:, None, :, :], t, ok)
+            e[s0:s0 + chunk, 0] = ec
+            g[s0:s0 + chunk] += gc
+        if sp is not None:
+            es, gs = _pair_terms(xs[:, :, None, :] - xs[:, None, :, :], ts, sp)
+            e[s0:s0 + chunk, 1] = 0.5 * es               # every pair is met from both ends
+            g[s0:s0 + chunk] += gs
+    dx = x64 - anchor.double()
+    e[:, 2] = restraint * dx.pow(2).sum(-1).mean(-1)
+    g += (2.0 * restraint / n) * dx
+    e[:, 3] = e[:, 0] + e[:, 1] + e[:, 2]
+    return e, g
+
+
+def direction_torch(x, g, bonds, mask_rotate):
+    """fp64 (d_tr [S, 3], d_rot [S, 3], d_tor [S, T]) of the module docstring (not yet multiplied by the step)."""
+    x = x.double()
+    n = x.shape[1]
+    zero = torch.zeros((), dtype=torch.float64)
+    d_tr = -g.sum(1) / n
+    p = x - x.mean(1, keepdim=True)
+    den = p.pow(2).sum((1, 2))
+    d_rot = torch.where(den[:, None] == 0, zero, -torch.cross(p, g, dim=-1).sum(1) / den[:, None])
+    d_tor = torch.zeros(x.shape[0], bonds.shape[0], dtype=torch.float64)
+    for b in range(bonds.shape[0]):
+        u, v = int(bonds[b, 0]), int(bonds[b, 1])
+        axis = x[:, u] - x[:, v]
+        axis = axis / axis.norm(dim=-1, keepdim=True)
+        mk = mask_rotate[b].bool().clone()
+        mk[u] = mk[v] = False                              # the bond's own atoms lie on the axis: no lever, exactly
+        a = torch.cross(axis[:, None, :].expand(-1, int(mk.sum()), -1), x[:, mk] - x[:, v:v + 1], dim=-1)
+        num, dn = (g[:, mk] * a).sum((1, 2)), a.pow(2).sum((1, 2))
+        d_tor[:, b] = torch.where(dn == 0, zero, -num / dn)
+    return d_tr, d_rot, d_tor
+
+
+# ---------------------------------------------------------------------------------------------- refiner
+class PoseRefiner:
+    """Clash relief for the poses of one complex (see the module docstring).
+
+    graph, device, receptor, overlap: as PoseEvaluator - receptor "graph" (the graph's atom nodes; each sample's own atom_pos when
+    one is handed in: flexible runs) or (coords, elements), e.g. PoseEvaluator.full_receptor(pdb_text, graph.original_center).  Radii
+    and the hydrogen convention are the evaluator's own tables; clash counts go through its contacts path."""
+
+    def __init__(self, graph, device="cpu", receptor="graph", overlap: float = OVERLAP_DISTANCE, config: Optional[RefineConfig] = None):
+        self.config = config or RefineConfig()
+        if self.config.restraint < 0 or self.config.iterations < 0:
+            raise ValueError("RefineConfig: restraint and iterations must not be negative")
+        self.device = torch.device(device)
+        self.overlap = float(overlap)
+        self.evaluator = PoseEvaluator(graph, device, receptor=receptor, max_automorphisms=1, overlap=overlap)
+        self.n, self.n_a = self.evaluator.n, self.evaluator.n_a
+        self.bonds, self.mask_rotate = ligand_torsions(graph)
+        self.T = int(self.bonds.shape[0])
+        self.rot_idx = rotate_index_lists(self.mask_rotate)
+        self.self_pairs = build_self_pairs(self.n, torch.as_tensor(graph["ligand", "ligand"].edge_index).numpy(), self.mask_rotate.numpy())
+        self._ref_lig = torch.as_tensor(graph["ligand"].pos).float().reshape(-1, 3)
+        if self.device.type != "cpu":
+            from . import launch as LA
+            self._bonds_i32 = LA.refine_bonds(self.bonds, self.n, self.device)      # checked on the host, uploaded once
+            self._mask_u8 = self.mask_rotate.to(torch.uint8).contiguous().to(self.device)
+            self._pairs_dev = self.self_pairs.contiguous().to(self.device)
+
+    # ---- checks
+    def _check(self, lig_pos, atom_pos):
+        if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
+            raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")
+        if atom_pos is not None and (atom_pos.dim() != 3 or atom_pos.shape[1:] != (self.n_a, 3) or atom_pos.shape[0] != lig_pos.shape[0]):
+            raise ValueError(f"atom_pos: expected [S, {self.n_a}, 3], got {tuple(atom_pos.shape)}")
+        if lig_pos.is_cuda and (self.device.type != "cuda" or lig_pos.device != self.device):
+            raise ValueError(f"poses on {lig_pos.device}, refiner built for {self.device}")
+        if atom_pos is not None and atom_pos.device != lig_pos.device:
+            raise ValueError("lig_pos and atom_pos on different devices")
+
+    def _tables(self, lig_pos, atom_pos):
+        apos = None if atom_pos is None else atom_pos.float().contiguous()
+        return self.evaluator.contact_tables(lig_pos.is_cuda, apos)
+
+    def clashes(self, lig_pos, atom_pos=None) -> torch.Tensor:
+        """[S] int32 clash counts of the poses (PoseEvaluator.contacts: the count behind PoseMetrics.clashes)."""
+        return self.evaluator.contacts(lig_pos, atom_pos)[:, 0].to(torch.int32)
+
+    # ---- energy
+    def energy(self, lig_pos, anchor=None, atom_pos=None):
+        """([S, 4] fp64 = E_cross, E_self, E_rest, E; [S, n, 3] fp64 gradient) of the poses; anchor None: the poses themselves."""
+        self._check(lig_pos, atom_pos)
+        x = lig_pos.float().contiguous()
+        a = x if anchor is None else anchor.float().contiguous()
+        if a.shape != x.shape or a.device != x.device:
+            raise ValueError("anchor: the shape and device of lig_pos")
+        lig_r, rec, rec_r = self._tables(x, atom_pos)
+        if not x.is_cuda:
+            return energy_torch(x, a, lig_r, rec, rec_r, self.self_pairs, self.overlap, self.config.restraint)
+        from . import launch as LA
+        with torch.cuda.device(x.device):
+            e = torch.empty(x.shape[0], 4, dtype=torch.float64, device=x.device)
+            g = torch.empty(x.shape[0], self.n, 3, dtype=torch.float64, device=x.device)
+            LA.refine_energy(LA.refine_args(x, a, lig_r, rec, rec_r, self._pairs_dev, self.overlap, self.config.restraint, e, g))
+        return e, g
+
+    # ---- refinement
+    def refine(self, lig_pos, atom_pos=None, history: Optional[List[torch.Tensor]] = None) -> RefineResult:
+        """Runs config.iterations iterations on lig_pos [S, n, 3] (flexible runs: atom_pos [S, n_a, 3], each sample's own static
+        receptor) and returns a RefineResult on the poses' device.  The input tensor is not modified.  history: a list that receives
+        the [S] total energies before the first and after every iteration (a debug hook; device tensors, no synchronisation)."""
+        self._check(lig_pos, atom_pos)
+        x0 = lig_pos.float().contiguous()
+        lig_r, rec, rec_r = self._tables(x0, atom_pos)
+        if x0.is_cuda:
+            with torch.cuda.device(x0.device):
+                x, e0, e1, acc = self._refine_hip(x0, lig_r, rec, rec_r, history)
+        else:
+            x, e0, e1, acc = self._refine_torch(x0, lig_r, rec, rec_r, history)
+        moved = (x.double() - x0.double()).pow(2).sum(-1).mean(-1).sqrt().float()
+        return RefineResult(x, e0, e1, self.clashes(x0, atom_pos), self.clashes(x, atom_pos), moved, acc)
+
+    def _refine_torch(self, x0, lig_r, rec, rec_r, history):
+        c = self.config
+        S = x0.shape[0]
+
+        def E(p):
+            return energy_torch(p, x0, lig_r, rec, rec_r, self.self_pairs, self.overlap, c.restraint)
+
+        x = x0.clone()
+        e, g = E(x)
+        e0 = e.clone()
+        step = torch.full((S,), float(c.step_init), dtype=torch.float64)
+        acc = torch.zeros(S, dtype=torch.int32)
+        if history is not None:
+            history.append(e[:, 3].clone())
+        for _ in range(c.iterations):
+            d_tr, d_rot, d_tor = direction_torch(x, g, self.bonds, self.mask_rotate)
+            # a sample without a finite energy can never accept (NaN compares false): the graph's own pose goes through the update in
+            # its place with a zero move, so that its NaNs do not reach the batched SVD of the alignment
+            fin = torch.isfinite(e[:, 3])
+            tr, rot, tor = (torch.where(fin[:, None], step[:, None] * d, torch.zeros_like(d)).float() for d in (d_tr, d_rot, d_tor))
+            trial = modify_conformer(torch.where(fin[:, None, None], x, self._ref_lig[None]), tr, rot,
+                                     tor if self.T else None, self.bonds, self.rot_idx)
+            et, gt = E(trial)
+            take = et[:, 3] < e[:, 3]                      # strict, fp64; False for NaN
+            x = torch.where(take[:, None, None], trial, x)
+            g = torch.where(take[:, None, None], gt, g)
+            e = torch.where(take[:, None], et, e)
+            step = torch.where(take, (c.step_grow * step).clamp(max=c.step_max), c.step_shrink * step)
+            acc += take.to(torch.int32)
+            if history is not None:
+                history.append(e[:, 3].clone())
+        return x, e0, e, acc
+
+    def _refine_hip(self, x0, lig_r, rec, rec_r, history):
+        from . import launch as LA
+        c = self.config
+        dev, S, n, T = x0.device, x0.shape[0], self.n, self.T
+        f64 = dict(dtype=torch.float64, device=dev)
+        x, trial = x0.clone(), torch.empty_like(x0)
+        e, et = torch.empty(S, 4, **f64), torch.empty(S, 4, **f64)
+        g, gt = torch.empty(S, n, 3, **f64), torch.empty(S, n, 3, **f64)
+        step = torch.full((S,), float(c.step_init), **f64)
+        acc = torch.zeros(S, dtype=torch.int32, device=dev)
+        tr, rot = torch.empty(S, 3, device=dev), torch.empty(S, 3, device=dev)
+        tor = torch.empty(S, T, device=dev)
+        common = dict(lig_radii=lig_r, rec=rec, rec_radii=rec_r, self_pairs=self._pairs_dev, overlap=self.overlap, restraint=c.restraint)
+        cur = LA.refine_args(x, x0, energy=e, grad=g, bonds=self._bonds_i32, mask_rotate=self._mask_u8, step=step, tr=tr, rot=rot,
+                             tor=tor, trial=trial, trial_energy=et, trial_grad=gt, accepted=acc, grow=c.step_grow,
+                             shrink=c.step_shrink, step_max=c.step_max, **common)
+        tri = LA.refine_args(trial, x0, energy=et, grad=gt, **common)
+        LA.refine_energy(cur)
+        e0 = e.clone()
+        if history is not None:
+            history.append(e[:, 3].clone())
+        for _ in range(c.iterations if S else 0):
+            LA.refine_direction(cur)
+            # ddp_pose_update, the existing kernel: x -> trial (never in place: the accept kernel may have to keep x)
+            modify_conformer_hip(x, tr, rot, tor if T else None, self._bonds_i32, self._mask_u8, out=trial)
+            LA.refine_energy(tri)
+            LA.refine_accept(cur)
+            if history is not None:
+                history.append(e[:, 3].clone())
+        return x, e0, e, acc
+

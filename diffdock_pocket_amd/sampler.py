@@ -107,13 +107,17 @@ def apply_sidechain_torsions_hip(pos, edge_idx_i32, sub_i32, map_i32, angles):
     return out
 
 
-def modify_conformer_hip(pos, tr, rot, tor, bonds_i32, mask_u8):
+def modify_conformer_hip(pos, tr, rot, tor, bonds_i32, mask_u8, out=None):
     """modify_conformer for a device-resident batch in ONE launch (ddp_pose_update, csrc/ddp_pose.hip); same arguments
-    as modify_conformer with bonds as int32 [T,2] and mask_rotate as uint8 [T,n] device tensors."""
+    as modify_conformer with bonds as int32 [T,2] and mask_rotate as uint8 [T,n] device tensors.  out: a contiguous tensor like pos
+    that receives the result (None: a new one)."""
     from . import _lib as L
     lib = L.load()
     pos = pos.contiguous()
-    out = torch.empty_like(pos)
+    if out is None:
+        out = torch.empty_like(pos)
+    elif out.shape != pos.shape or out.dtype != pos.dtype or out.device != pos.device or not out.is_contiguous():
+        raise ValueError("modify_conformer_hip: out must be a contiguous tensor like pos")
     tr, rot = tr.contiguous().float(), rot.contiguous().float()
     has_tor = tor is not None and tor.shape[1] > 0
     if has_tor:
@@ -148,6 +152,16 @@ def record_trajectory_hip(lig_pos, lig_traj, slot_dev, atom_pos=None, moving_i32
     L.check(lib.ddp_traj_record(lig_pos.data_ptr(), n, n_l, lig_traj.data_ptr(), atom_pos.data_ptr() if n_m else None, n_a,
                                 moving_i32.data_ptr() if n_m else None, n_m, atom_traj.data_ptr() if n_m else None, n_slots,
                                 slot_dev.data_ptr(), torch._C._cuda_getCurrentRawStream(lig_pos.device.index)), "ddp_traj_record")
+
+
+def torsion_tables(g):
+    """(bonds [T,2] (u,v), mask_rotate [T,n] bool) of a complex graph's ligand, on the host: the rotatable bonds are the ligand edges
+    flagged by edge_mask, in edge order: the statements of Sampler.__init__ below, for callers without a sampler
+    (refine.PoseRefiner)."""
+    em = g["ligand"].edge_mask.bool()
+    bonds = g["ligand", "ligand"].edge_index.t()[em].clone()
+    mr = g["ligand"].mask_rotate
+    return bonds, torch.as_tensor(np.asarray(mr if isinstance(mr, np.ndarray) else mr[0])).bool()
 
 
 def modify_conformer(pos, tr, rot, tor, bonds, mask_rotate):

@@ -780,6 +780,59 @@ int ddp_svgd_tau(const ddp_svgd_args_t* args, void* stream);
 int ddp_svgd_pairs(const ddp_svgd_args_t* args, void* stream);
 int ddp_svgd_rows(const ddp_svgd_args_t* args, void* stream);
 
+/* ---- steric-clash relief of sampled poses in pose space (csrc/ddp_refine.hip; host side diffdock_pocket_amd/refine.py).  This
+ * project's own algorithm, not the reference's --relax.  n_samples poses of one complex, pos [n_samples][n][3] fp32 in the pocket frame,
+ * anchor [n_samples][n][3] the poses the refinement started from; lig_radii, rec, m, rec_stride, rec_radii as ddp_pose_contacts (a
+ * negative receptor radius = a hydrogen, ignored); self_pairs uint8 [n][n], upper triangle (NULL: no ligand-ligand term).  All
+ * arithmetic is fp64 on the fp32 inputs.  With t_ij = r_i + r_j - 2 overlap (a pair with t_ij <= 0 never counts) and d_ij the distance,
+ *   E_cross = sum_{i lig, j rec, r_j >= 0} max(0, t_ij - d_ij)^2        E_self = the same sum over the pairs of self_pairs
+ *   E_rest  = restraint * mean_i |x_i - anchor_i|^2                      E = E_cross + E_self + E_rest
+ *   ddp_refine_energy:    energy[s] = [E_cross, E_self, E_rest, E], grad[s][i] = dE/dx_i (NULL: not computed).  d_ij = 0 counts for E
+ *                         and adds nothing to the gradient.  A NaN coordinate gives a NaN energy.
+ *   ddp_refine_direction: with c the centroid, u^ = (x_u - x_v) / |x_u - x_v| and a_i = u^ x (x_i - x_v) for bond b = (u, v) = bonds[b]
+ *                           tr[s]     = step[s] * -sum_i g_i / n
+ *                           rot[s]    = step[s] * -sum_i (x_i - c) x g_i / sum_i |x_i - c|^2
+ *                           tor[s][b] = step[s] * -sum_{i: mask_rotate[b][i]} g_i . a_i / sum_{i: mask_rotate[b][i]} |a_i|^2
+ *                         rounded to fp32: the tr / rot / tor arguments of ddp_pose_update (same bonds [n_tor][2], mask_rotate
+ *                         [n_tor][n], axis and sense).  Atoms u and v lie on the axis and are left out of the torsion sums (their lever
+ *                         is zero, so a bond that turns a single on-axis atom gets exactly 0).  A zero denominator gives 0; a bonds
+ *                         entry outside [0, n) gives 0 without a read (the host validates the table before it is uploaded).
+ *                         ddp_pose_update re-aligns after the torsions, so tor is not the exact derivative of that map: the accept
+ *                         rule is what guarantees descent.
+ *   ddp_refine_accept:    per sample, trial_energy[s][3] < energy[s][3] (strict, fp64, false for NaN): pos[s], energy[s], grad[s] take
+ *                         trial[s], trial_energy[s], trial_grad[s] bit for bit, step[s] = min(grow * step[s], step_max), accepted[s] += 1;
+ *                         otherwise only step[s] = shrink * step[s] is written.  grad and trial_grad: both given or both NULL.
+ * One iteration = ddp_refine_direction, ddp_pose_update (pos -> trial), ddp_refine_energy (on trial), ddp_refine_accept, on one stream,
+ * no host decision in between.  One workgroup per sample, the ligand staged in LDS (n > DDP_EVAL_MAX_ATOMS: DDP_ELIMIT), every sum in a
+ * fixed order, no atomics: two launches give the same bits.  n_samples = 0: no-op; m = 0: no cross term; n_tor = 0: rigid only (bonds,
+ * mask_rotate, tor may be NULL); n = 1: rot = 0.  Each entry reads only the fields its description names. */
+typedef struct {
+  int32_t n_samples, n, m, rec_stride, n_tor;
+  float* pos;                   /* [n_samples][n][3]; written by ddp_refine_accept only */
+  const float* anchor;
+  const float* lig_radii;
+  const float* rec;
+  const float* rec_radii;
+  const uint8_t* self_pairs;
+  double overlap, restraint;
+  double* energy;               /* [n_samples][4] */
+  double* grad;                 /* [n_samples][n][3] */
+  const int32_t* bonds;
+  const uint8_t* mask_rotate;
+  double* step;                 /* [n_samples] */
+  float* tr;                    /* [n_samples][3] */
+  float* rot;                   /* [n_samples][3] */
+  float* tor;                   /* [n_samples][n_tor] */
+  const float* trial;
+  const double* trial_energy;
+  const double* trial_grad;
+  int32_t* accepted;            /* [n_samples] */
+  double grow, shrink, step_max;
+} ddp_refine_args_t;
+int ddp_refine_energy(const ddp_refine_args_t* args, void* stream);
+int ddp_refine_direction(const ddp_refine_args_t* args, void* stream);
+int ddp_refine_accept(const ddp_refine_args_t* args, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
 /* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, the csrc headers, include/ddp_hip.h) the library was built from */
