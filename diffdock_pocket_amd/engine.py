@@ -1251,7 +1251,8 @@ class ForwardEngine:
         if m.smooth_edges and E > 0:      # (:614,634 -> :401,426) the bond-centre graphs' edges are weighted too
             tor_sh.mul_(self._smooth_weight(h.bond_pos, csr.recv, pos, csr.src, m.lig_max_radius).unsqueeze(1))
         spec, pkc = conv.spec, conv.packed(dev)
-        msg = torch.empty((E, spec.d_out), device=dev)
+        # (a one-layer model has no 1e features: no block writes the 0o half of the message rows, which the reference leaves zero)
+        msg = (torch.empty if spec.covers_output() else torch.zeros)((E, spec.d_out), device=dev)
         segs = [(e_t, csr.eid, ns, ns), (x, csr.src, ldx, ns), (bond_attr, csr.recv, ns, ns)]
         if E > 0:
             K.launch_convs(spec, [K.make_task(pkc, K.conv_path(pkc), x, ldx, csr, tor_sh, segs, msg)], tag="head")

@@ -101,6 +101,10 @@ class ConvSpec:
             self.fbuf_floats += (64 * max(self.g_cols) + 3) // 4 * 4   # + the tv[64][g_cols] region of the factorised part
         if any(b.n > 64 or (b.C == 3 and b.n > 32) for b in self.blocks):
             raise NotImplementedError("HIP conv supports ns <= 64 and nv <= 32")
+        hit = [False] * self.d_out
+        for b in self.blocks:
+            hit[b.out_off:b.out_off + b.n * b.C] = [True] * (b.n * b.C)
+        self._covers = all(hit)          # (covers_output)
         self.roles, self.nrounds = (conv32_roles(self.blocks) if self.factorized else ([[] for _ in range(CONV32_WAVES)], 0))
 
     def ctypes_shape(self) -> L.ConvShape:
@@ -122,6 +126,11 @@ class ConvSpec:
             for k, (kind, off, cnt) in enumerate(b.segs):
                 cb.seg[k].kind, cb.seg[k].in_off, cb.seg[k].count = kind, off, cnt
         return s
+
+    def covers_output(self) -> bool:
+        """Every column of a message row belongs to a block.  False for the torsion conv of a ONE-layer model (no 1e inputs: no path to its 0o
+        outputs, which the reference leaves zero): the kernels write only the columns of the shape's blocks, so the caller zeroes msg then."""
+        return self._covers
 
     def flops_per_edge(self):
         """Algorithmic FLOPs per edge of the reference formulation."""

@@ -298,12 +298,9 @@ class TensorProductConvLayer(nn.Module):
             return None
         return pks if nsplit > 1 else pks[0]
 
-    def forward(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce="mean", edge_weight=1.0,
-                factorized=False):
-        if reduce != "mean" or not (isinstance(edge_weight, (int, float)) and edge_weight == 1.0):
-            raise NotImplementedError("HIP conv implements reduce='mean', edge_weight=1")
-        if edge_index.numel() == 0:
-            return torch.tensor(0, dtype=node_attr.dtype, device=node_attr.device)
+    def messages(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, factorized=False):
+        """The per-edge messages of `forward`, before the segmented mean: (msg [E, d_out] in CSR order of the receiving node, the CSR view,
+        the ConvPath the launch ran by).  row p of msg belongs to edge csr.eid[p] of the arguments."""
         _require_hip(node_attr)
         dev = node_attr.device
         n_out = int(out_nodes) if out_nodes is not None else node_attr.shape[0]
@@ -313,7 +310,7 @@ class TensorProductConvLayer(nn.Module):
         sh = edge_sh.float().contiguous()
         if sh.shape[1] != 4:
             raise NotImplementedError("edge_sh must be [E,4] (lmax=1) or pre-contracted torsion harmonics [0,t]")
-        msg = torch.empty((csr.n_edges, self.spec.d_out), device=dev, dtype=torch.float32)
+        msg = (torch.empty if self.spec.covers_output() else torch.zeros)((csr.n_edges, self.spec.d_out), device=dev, dtype=torch.float32)
         if factorized:
             if self.spec_g is None:
                 raise NotImplementedError("this conv has no factorised variant")
@@ -332,6 +329,17 @@ class TensorProductConvLayer(nn.Module):
             segs = [(ea, view.eid, ea.shape[1], ea.shape[1])]
         task = _make_task(pk, path, x, x.shape[1], view, sh, segs, msg, g=g)
         _launch_convs(self.spec_g if factorized else self.spec, [task], flops_spec=self.spec if factorized else None)
+        return msg, csr, path
+
+    def forward(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce="mean", edge_weight=1.0,
+                factorized=False):
+        if reduce != "mean" or not (isinstance(edge_weight, (int, float)) and edge_weight == 1.0):
+            raise NotImplementedError("HIP conv implements reduce='mean', edge_weight=1")
+        if edge_index.numel() == 0:
+            return torch.tensor(0, dtype=node_attr.dtype, device=node_attr.device)
+        msg, csr, _ = self.messages(node_attr, edge_index, edge_attr, edge_sh, out_nodes=out_nodes, factorized=factorized)
+        dev = node_attr.device
+        n_out = int(out_nodes) if out_nodes is not None else node_attr.shape[0]
         out = torch.zeros((n_out, self.spec.d_out), device=dev, dtype=torch.float32)
         _launch_reduce(out, self.spec.d_out, n_out, self.spec.d_out, [(msg, csr, self.packed(dev))], accumulate=False)
         return out

@@ -112,7 +112,9 @@ typedef struct {
   const float* b1p;
   const float* w2p;     /* fc.3 weight, packed, 1/sqrt(U) folded in */
   const float* b2p;
-  float* msg;           /* per-edge messages, CSR order                       [E, d_out] */
+  float* msg;           /* per-edge messages, CSR order                       [E, d_out].  Only the columns of the shape's blocks are written: where
+                           the blocks do not cover d_out (the torsion conv of a one-layer model: no 1e inputs, no path to its 0o outputs) the
+                           caller zeroes the array, as the reference's tensor product leaves those outputs zero */
   /* factorised convs only (shape.g_cols != 0): edges are then listed in SOURCE-node order (so that a workgroup streams
    * each G[j] once) and `pos` gives the message row (= position in the receiver-CSR order) of every listed edge */
   const float* g[2];    /* G[s]: [n_src, DDP_G_LD(hid, g_cols[s])] floats per node: first [hg/4, g_cols[s], 4] (hg = hid rounded

@@ -13,7 +13,8 @@ from oracle import thirdparty as tp
 from oracle.cases import CASES
 from oracle.ref_model import OracleConfig, OracleScoreModel, gaussian_smearing
 
-from helpers import case_inputs, conv_stats_excess, elementwise_excess, rel_err, rowwise_excess
+import conv_ref64 as R64
+from helpers import _assert_within, case_inputs, conv_stats_excess, elementwise_excess, rel_err, rowwise_excess
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -702,6 +703,13 @@ def test_single_conv_layer(ns, nv, layer, E, N, factorized, form, fmt):
         assert path.rows and path.rows_form == form and path.gh_fmt == fmt      # (it ran through the kernel form and plane form asked for)
     assert got.shape == want.shape
     assert rel_err(got, want) < 2e-5, rel_err(got, want)
+    # ... and the messages before the mean, every element against the fp64 definition within the composed bound (tests/conv_ref64.py)
+    msg, csr, mpath = conv.messages(x.to(dev), ei.to(dev), ea.to(dev), sh.to(dev), factorized=factorized)
+    form64 = R64.Form("rows" if mpath.rows else "h2" if mpath.h2 else "fp32", factorized, mpath.gh_fmt if (factorized and mpath.rows) else 0)
+    ref = R64.reference(spec, *(t.detach().cpu() for t in (conv.fc[0].weight, conv.fc[0].bias, conv.fc[3].weight, conv.fc[3].bias)),
+                        ea, x[ei[1]], sh, form64)
+    eid = csr.eid.cpu().long().numpy()
+    _assert_within(msg.cpu().numpy(), ref.msg[eid], ref.bound[eid], f"single conv layer ({ns}, {nv}, {layer}) E={E} {form64}")
     # empty edge set: scalar zero, like the reference (models/score_model.py:109-111)
     z = conv(x.to(dev), ei[:, :0].to(dev), ea[:0].to(dev), sh[:0].to(dev))
     assert z.dim() == 0 and float(z) == 0.0
