@@ -33,6 +33,7 @@ from . import inputs as I
 from . import outputs as O
 from .diffusion import get_t_schedule
 from .evaluation import PoseClusters, PoseEvaluator, PoseMetrics  # noqa: F401
+from .pockets import Pocket, PocketConfig, find_pockets as _find_pockets  # noqa: F401
 from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 
@@ -53,6 +54,7 @@ class ComplexResult:
     refined_pos: Optional[torch.Tensor] = None     # run_csv(resolve_clashes=cfg): [N, n_lig, 3] the ranked poses after clash relief
     refine: Optional["RefineResult"] = None        # run_csv(resolve_clashes=cfg): refine.RefineResult of the ranked poses (host tensors)
     refined_metrics: Optional["PoseMetrics"] = None  # resolve_clashes with evaluate=True: PoseMetrics of refined_pos (`metrics` is untouched)
+    pockets: Optional[List["Pocket"]] = None       # run_csv(find_pockets=cfg), row without a centre: every pocket found, best first
 
 
 def _none(v):
@@ -98,7 +100,7 @@ def build_row_graph(row: Dict, esm_embeddings=None, root: str = "", allow_zero_e
         pdb_text = f.read()
     with open(os.path.join(root, lig)) as f:
         sdf_text = f.read()
-    e = _esm_rows(esm_embeddings, row["complex_name"])
+    e = _esm_rows(esm_embeddings, row.get("esm_name", row["complex_name"]))
     if e is None and not allow_zero_esm:
         raise ValueError(f"{row['complex_name']}: no ESM embedding found (pass allow_zero_esm=True to run on a zero block)")
     g = I.build_complex_graph(pdb_text, sdf_text, name=row["complex_name"], pocket_center=row.get("pocket_center"),
@@ -117,7 +119,8 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             dist=None, sampler_cfg: Optional[SamplerConfig] = None, graph_kwargs: Optional[Dict] = None,
             allow_zero_esm: bool = False, evaluate: bool = False, out_dir: Optional[str] = None,
             save_visualisation: bool = False, cluster_rmsd: Optional[float] = None,
-            resolve_clashes: Optional[RefineConfig] = None) -> List[ComplexResult]:
+            resolve_clashes: Optional[RefineConfig] = None, find_pockets: Optional[PocketConfig] = None,
+            pockets_top_k: int = 1) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -150,7 +153,18 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     `refined_metrics`.  Rigid rows are refined against the row's full PDB, flexible rows against each sample's own atom nodes, as the
     evaluation chooses.  With out_dir the complex directory also gets rank{k}_resolved.sdf per pose and clashes.csv
     (outputs.write_clashes_csv).  Nothing that exists without it changes: ligand_pos, confidences, order, metrics and every other
-    file are the same.  A failure skips the row like a failure of the evaluation.  None: nothing is computed or written."""
+    file are the same.  A failure skips the row like a failure of the evaluation.  None: nothing is computed or written.
+
+    find_pockets=PocketConfig(...): a row WITHOUT pocket_center_* gets its centre from pockets.find_pockets on the row's protein (this
+    package's geometric finder, on `device`): it is docked at the `ca_center` of pocket 1, and with pockets_top_k = K > 1 it is expanded
+    into the rows `{name}_pocket{k}`, k = 1 ... min(K, found), each docked, ranked and written like any other row (one ComplexResult
+    each, seeds and directory indices counting the expanded rows; the ESM embedding is looked up under the row's own name).  Such a
+    result carries `pockets` (all pockets found), and with out_dir its directory gets pockets.csv (outputs.write_pockets_csv: one line
+    per pocket found, `docked` = 1 for the pockets this run docked).  A protein on which no pocket survives, or that cannot be read,
+    fails the row like any other per-row failure.  A row with an explicit centre keeps it and gets none of this.  None: nothing is
+    computed or written, and a row without a centre takes it from the ligand's pose as before."""
+    if pockets_top_k < 1:
+        raise ValueError("pockets_top_k must be at least 1")
     if sampler_cfg is not None and sampler_cfg.svgd_weight > 0:
         # the samples of a complex interact: a row's sampler would raise inside the per-row try and the row would only be skipped
         if shard == "samples" and world > 1:
@@ -160,7 +174,8 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             raise ValueError("svgd_weight > 0 needs at least 3 samples per complex")
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
-            shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd, resolve_clashes)
+            shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd, resolve_clashes,
+            find_pockets, pockets_top_k)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(*args)
@@ -177,8 +192,10 @@ def _all_ok(dist, ok: bool, device) -> bool:
 
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
              world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
-             save_visualisation=False, cluster_rmsd=None, resolve_clashes=None) -> List[ComplexResult]:
+             save_visualisation=False, cluster_rmsd=None, resolve_clashes=None, find_pockets=None, pockets_top_k=1) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
+    if find_pockets is not None:
+        rows = expand_pocket_rows(rows, root, device, find_pockets, pockets_top_k)
     if shard not in ("samples", "complexes"):
         raise ValueError(shard)
     mine = range(len(rows))
@@ -187,13 +204,15 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
     out: List[ComplexResult] = []
     schedule = get_t_schedule(inference_steps)
     for i, row in enumerate(rows):
-        res = ComplexResult(name=row["complex_name"])
+        res = ComplexResult(name=row["complex_name"], pockets=row.get("pockets"))
         out.append(res)
         if i not in mine:
             continue
         split = shard == "samples" and world > 1
         g = None
         try:
+            if row.get("pocket_error") is not None:
+                raise ValueError(row["pocket_error"])
             g = build_row_graph(row, esm_embeddings, root, allow_zero_esm=allow_zero_esm, **(graph_kwargs or {}))
         except Exception as e:      # noqa: BLE001 - the reference skips a failing complex and goes on (inference.py:282-287)
             res.skipped = f"{type(e).__name__}: {e}"
@@ -317,6 +336,32 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
     return out
 
 
+def expand_pocket_rows(rows: List[Dict], root: str, device, config: PocketConfig, top_k: int = 1) -> List[Dict]:
+    """run_csv(find_pockets=config): every row without an explicit centre gets `pocket_center` = ca_center of a pocket found on its
+    protein, `pockets` (all found) and `pockets_docked` (how many this run docks); with top_k > 1 it becomes the rows
+    `{name}_pocket{k}`.  A protein that cannot be read or on which nothing survives leaves ONE row that carries `pocket_error`."""
+    out = []
+    for row in rows:
+        if row.get("pocket_center") is not None:
+            out.append(row)
+            continue
+        try:
+            with open(os.path.join(root, row["experimental_protein"])) as f:
+                found = _find_pockets(f.read(), device, config)
+            if not found:
+                raise ValueError(f"{row['complex_name']}: no pocket found on {row['experimental_protein']} (find_pockets: no component of "
+                                 f"at least {config.min_points} buried points; give pocket_center_x/y/z, or relax PocketConfig)")
+        except Exception as e:      # noqa: BLE001 - reported through the row's own failure path
+            out.append(dict(row, pocket_error=f"{type(e).__name__}: {e}" if not isinstance(e, ValueError) else str(e)))
+            continue
+        k_max = min(top_k, len(found))
+        for k in range(k_max):
+            name = row["complex_name"] if top_k == 1 else f"{row['complex_name']}_pocket{k + 1}"
+            out.append(dict(row, complex_name=name, esm_name=row.get("esm_name", row["complex_name"]),
+                            pocket_center=[float(v) for v in found[k].ca_center], pockets=found, pockets_docked=k_max))
+    return out
+
+
 def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) -> List[str]:
     """outputs.write_complex for one processed row (ranked tensors of `res`)."""
     with open(os.path.join(root, row["ligand"])) as f:
@@ -327,7 +372,7 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
             pdb_text = f.read()
     return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
                            apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order,
-                           refine=res.refine)
+                           refine=res.refine, pockets=res.pockets, pockets_docked=row.get("pockets_docked", 0))
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -409,6 +454,13 @@ def _parser():
     p.add_argument("--resolve_clashes_iterations", type=int, default=RefineConfig.iterations)
     p.add_argument("--resolve_clashes_restraint", type=float, default=RefineConfig.restraint,
                    help="weight of the restraint to the sampled pose")
+    p.add_argument("--find_pockets", action="store_true", default=False,
+                   help="complexes without --pocket_center_* / pocket_center columns: find the pocket on the protein's geometry (this "
+                        "package's grid buriedness finder, no learned predictor) and dock there; writes pockets.csv (default: off)")
+    p.add_argument("--pockets_top_k", type=int, default=1, help="with --find_pockets: dock into the best K pockets, as complexes {name}_pocket{k}")
+    p.add_argument("--pocket_spacing", type=float, default=PocketConfig.spacing, help="grid spacing of the pocket finder, angstrom")
+    p.add_argument("--pocket_min_lines", type=int, default=PocketConfig.min_lines, help="lines (of 7) that must be blocked on both sides")
+    p.add_argument("--pocket_probe", type=float, default=PocketConfig.probe, help="probe radius added to the van der Waals radii")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--esm_embeddings", type=str, default=None,
                    help="directory of <complex_name>.pt / .npy ESM rows, or one .pt file holding {complex_name: rows}")
@@ -416,6 +468,13 @@ def _parser():
                    help="run complexes without an ESM embedding on a zero block (out of the model's training distribution)")
     p.add_argument("--device", type=str, default=None, help="default: cuda:0 when a GPU is visible, else cpu")
     return p
+
+
+def pocket_config_from_args(a) -> Optional[PocketConfig]:
+    """The PocketConfig the command line asks for (None without --find_pockets)."""
+    if not a.find_pockets:
+        return None
+    return PocketConfig(spacing=a.pocket_spacing, min_lines=a.pocket_min_lines, probe=a.pocket_probe)
 
 
 def _load_model(model_dir, ckpt, device, confidence_mode=False):
@@ -451,6 +510,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error(f"--filtering_model_dir {a.filtering_model_dir!r} holds no model_parameters.yml")
     if a.resolve_clashes_iterations < 0 or a.resolve_clashes_restraint < 0:
         ap.error("--resolve_clashes_iterations and --resolve_clashes_restraint must not be negative")
+    if a.pockets_top_k < 1 or not a.pocket_spacing > 0 or not 0 <= a.pocket_min_lines <= 7 or a.pocket_probe < 0:
+        ap.error("--pockets_top_k must be at least 1, --pocket_spacing positive, --pocket_min_lines in 0..7, --pocket_probe not negative")
     if a.samples_per_complex < 1 or a.inference_steps < 1:
         ap.error("--samples_per_complex and --inference_steps must be positive")
     device = torch.device(a.device or ("cuda:0" if torch.cuda.is_available() else "cpu"))
@@ -502,7 +563,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       allow_zero_esm=a.allow_zero_esm, out_dir=a.out_dir, save_visualisation=a.save_visualisation,
                       cluster_rmsd=a.cluster_rmsd,
                       resolve_clashes=RefineConfig(iterations=a.resolve_clashes_iterations, restraint=a.resolve_clashes_restraint)
-                      if a.resolve_clashes else None)
+                      if a.resolve_clashes else None,
+                      find_pockets=pocket_config_from_args(a), pockets_top_k=a.pockets_top_k)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

@@ -777,3 +777,65 @@ def refine_direction(a: L.RefineArgs):
 def refine_accept(a: L.RefineArgs):
     """ddp_refine_accept: the per-sample select between a.pos and a.trial."""
     L.check(L.load().ddp_refine_accept(C.byref(a), stream()), "ddp_refine_accept")
+
+
+# ------------------------------------------------------------------------------------------------ pocket finder (csrc/ddp_pockets.hip)
+def _grid_n(dims) -> int:
+    nx, ny, nz = (int(d) for d in dims)
+    return nx * ny * nz if min(nx, ny, nz) > 0 else 0
+
+
+def pocket_occupancy(pos, r2, lo, spacing, dims, occ=None):
+    """ddp_pocket_occupancy: pos [N, 3] fp32, r2 [N] fp32 = fp32((radius + probe)^2), lo (3 floats, already fp32 values), dims (nx, ny, nz)
+    -> occ uint8 [nx, ny, nz]."""
+    dev = pos.device
+    _eval_arg(pos, torch.float32, dev, "pocket pos")
+    _eval_arg(r2, torch.float32, dev, "pocket r2")
+    if pos.dim() != 2 or pos.shape[1] != 3 or r2.shape != pos.shape[:1]:
+        raise L.DdpError("pocket_occupancy: pos [N, 3] and r2 [N]")
+    nx, ny, nz = (int(d) for d in dims)
+    if occ is None:
+        occ = torch.empty((max(nx, 0), max(ny, 0), max(nz, 0)), dtype=torch.uint8, device=dev)
+    _eval_arg(occ, torch.uint8, dev, "pocket occ")
+    if occ.numel() != _grid_n(dims):
+        raise L.DdpError("pocket_occupancy: occ does not have the grid's size")
+    L.check(L.load().ddp_pocket_occupancy(ptr(pos if pos.numel() else None), ptr(r2 if r2.numel() else None), int(pos.shape[0]), float(lo[0]),
+                                          float(lo[1]), float(lo[2]), float(spacing), nx, ny, nz, ptr(occ if occ.numel() else None), stream()),
+            "ddp_pocket_occupancy")
+    return occ
+
+
+def pocket_buriedness(occ, spacing, ray_length, min_lines, bur=None, mask=None):
+    """ddp_pocket_buriedness: occ uint8 [nx, ny, nz] -> (bur uint8, mask int32: bur + 1 at the pocket points, else 0), same shape."""
+    dev = occ.device
+    _eval_arg(occ, torch.uint8, dev, "pocket occ")
+    if occ.dim() != 3:
+        raise L.DdpError("pocket_buriedness: occ [nx, ny, nz]")
+    bur = torch.empty_like(occ) if bur is None else bur
+    mask = torch.empty(occ.shape, dtype=torch.int32, device=dev) if mask is None else mask
+    _eval_arg(bur, torch.uint8, dev, "pocket bur")
+    _eval_arg(mask, torch.int32, dev, "pocket mask")
+    if bur.shape != occ.shape or mask.shape != occ.shape:
+        raise L.DdpError("pocket_buriedness: bur and mask have the grid's shape")
+    nx, ny, nz = occ.shape
+    some = occ.numel() > 0
+    L.check(L.load().ddp_pocket_buriedness(ptr(occ if some else None), nx, ny, nz, float(spacing), float(ray_length), int(min_lines),
+                                           ptr(bur if some else None), ptr(mask if some else None), stream()), "ddp_pocket_buriedness")
+    return bur, mask
+
+
+def pocket_label(mask, labels=None):
+    """ddp_pocket_label: mask int32 [nx, ny, nz] (non-zero = in the mask) -> labels int32, the smallest flat index of each point's
+    6-connected component, -1 outside the mask."""
+    dev = mask.device
+    _eval_arg(mask, torch.int32, dev, "pocket mask")
+    if mask.dim() != 3:
+        raise L.DdpError("pocket_label: mask [nx, ny, nz]")
+    labels = torch.empty_like(mask) if labels is None else labels
+    _eval_arg(labels, torch.int32, dev, "pocket labels")
+    if labels.shape != mask.shape:
+        raise L.DdpError("pocket_label: labels has the grid's shape")
+    nx, ny, nz = mask.shape
+    some = mask.numel() > 0
+    L.check(L.load().ddp_pocket_label(ptr(mask if some else None), nx, ny, nz, ptr(labels if some else None), stream()), "ddp_pocket_label")
+    return labels

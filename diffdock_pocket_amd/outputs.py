@@ -244,6 +244,23 @@ def write_clashes_csv(path: str, refine, order=None) -> str:
     return path
 
 
+# ---------------------------------------------------------------------------------------------- pockets
+POCKETS_COLUMNS = ["pocket", "score", "size", "center_x", "center_y", "center_z", "ca_center_x", "ca_center_y", "ca_center_z", "docked"]
+
+
+def write_pockets_csv(path: str, pockets, docked: int = 1) -> str:
+    """pockets.csv of one complex docked without a given centre (pockets.find_pockets, best first): one line per pocket FOUND, pocket
+    counts from 1, the centres in the input frame, docked = 1 for the first `docked` pockets (the ones the run docked into)."""
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(POCKETS_COLUMNS)
+        for k, p in enumerate(pockets):
+            w.writerow([k + 1, int(p.score), int(p.size)] + [f"{float(v):.4f}" for v in p.center] + [f"{float(v):.4f}" for v in p.ca_center]
+                       + [int(k < docked)])
+    return path
+
+
 # ---------------------------------------------------------------------------------------------- one complex
 def complex_dir(out_dir: str, index: int, name: str) -> str:
     """reference inference.py:136."""
@@ -251,7 +268,8 @@ def complex_dir(out_dir: str, index: int, name: str) -> str:
 
 
 def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
-                  lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None, refine=None) -> List[str]:
+                  lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None, refine=None, pockets=None,
+                  pockets_docked: int = 1) -> List[str]:
     """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
     ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
     lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
@@ -261,7 +279,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     rank{k}_reverseprocess.pdb and rank{k}_reverseprocess_protein.pdb, each of the ranked sample itself (the reference indexes the
     side-chain trajectories by rank instead of by sample, inference.py:276-279).
     clusters (evaluation.PoseClusters of the ranked poses; order [N]: the sample index of each rank): also modes.csv.
-    refine (refine.RefineResult of the ranked poses): also rank{k}_resolved.sdf, the pose after clash relief, and clashes.csv."""
+    refine (refine.RefineResult of the ranked poses): also rank{k}_resolved.sdf, the pose after clash relief, and clashes.csv.
+    pockets (pockets.find_pockets of the protein, when the centre came from there): also pockets.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -304,4 +323,6 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
         for k in range(refine.lig_pos.shape[0]):
             write_sdf(put(os.path.join(write_dir, f"rank{k + 1}_resolved.sdf")), mol, refine.lig_pos[k], name, oc)
         write_clashes_csv(put(os.path.join(write_dir, "clashes.csv")), refine, order)
+    if pockets is not None:
+        write_pockets_csv(put(os.path.join(write_dir, "pockets.csv")), pockets, pockets_docked)
     return written

@@ -835,6 +835,31 @@ int ddp_refine_energy(const ddp_refine_args_t* args, void* stream);
 int ddp_refine_direction(const ddp_refine_args_t* args, void* stream);
 int ddp_refine_accept(const ddp_refine_args_t* args, void* stream);
 
+/* ---- geometric pocket finder: LIGSITE-style buriedness on a grid (csrc/ddp_pockets.hip; host side diffdock_pocket_amd/pockets.py, which
+ * states the whole definition).  This project's own method, no learned predictor.  Grid point (i, j, k), 0 <= i < nx ..., has the flat
+ * index g = (i ny + j) nz + k and sits at lo + (i, j, k) spacing; everything outside the grid is free space.  nx ny nz < 2^31.
+ *   ddp_pocket_occupancy:  occ[g] = 1 iff some atom a has |x_g - pos[a]|^2 < r2[a] (strict), else 0; r2[a] = fp32((radius_a + probe)^2)
+ *                          is formed by the caller.  fp32 with separate roundings, no contraction: x_g = lo + fp32(i) * spacing per axis,
+ *                          the three differences, (dx dx + dy dy) + dz dz.  One wave per atom over the atom's bounding cube clipped to
+ *                          the grid (an atom outside the grid marks what its sphere reaches, or nothing), plain byte stores of 1 after a
+ *                          memset: the result does not depend on the order of the stores.
+ *   ddp_pocket_buriedness: 7 lines (3 axes, 4 cube diagonals), each two opposite rays.  A ray from a free point takes t = 1 ... n_d grid
+ *                          steps along d in {-1, 0, 1}^3, n_d = floor(ray_length / (spacing |d|)) in double, and hits if it meets an
+ *                          occupied point before it leaves the grid.  bur[g] = number of lines whose two rays both hit (0 at occupied
+ *                          points); mask[g] = bur[g] + 1 at the pocket points (free, bur >= min_lines), 0 elsewhere.  Integers only.
+ *   ddp_pocket_label:      labels[g] = the smallest flat index of the 6-connected component of g among the points with mask[g] != 0,
+ *                          -1 where mask[g] == 0.  Three launches (init / union over the +x, +y, +z neighbours with atomicMin on roots /
+ *                          flatten); a parent is never larger than its child, so every walk and every retry ends after at most nx ny nz
+ *                          steps, and the result is the same array whatever the order of the atomics.
+ * The pocket points are then compacted with ddp_select_jobs (mask, payloads labels and mask with pay_add -1 = bur).
+ * DDP_EINVAL without a launch: a NULL pointer, n_atoms <= 0, a dimension <= 0, nx ny nz >= 2^31, spacing <= 0 (or not finite),
+ * ray_length < 0, min_lines outside [0, 7]. */
+int ddp_pocket_occupancy(const float* pos, const float* r2, int n_atoms, float lo_x, float lo_y, float lo_z, float spacing, int nx, int ny,
+                         int nz, uint8_t* occ, void* stream);
+int ddp_pocket_buriedness(const uint8_t* occ, int nx, int ny, int nz, double spacing, double ray_length, int min_lines, uint8_t* bur,
+                          int32_t* mask, void* stream);
+int ddp_pocket_label(const int32_t* mask, int nx, int ny, int nz, int32_t* labels, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
 /* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, the csrc headers, include/ddp_hip.h) the library was built from */
