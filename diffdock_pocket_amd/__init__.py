@@ -6,7 +6,7 @@ from .diffusion import SigmaRanges, get_t_schedule, get_timestep_embedding, sinu
 
 __all__ = ["HeteroBatch", "Store", "collate", "set_time", "SigmaRanges", "get_t_schedule", "get_timestep_embedding",
            "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize", "PoseRefiner",
-           "RefineConfig", "RefineResult"]
+           "RefineConfig", "RefineResult", "PoseScorer", "ScoreConfig", "PoseScores"]
 
 
 def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ctypes binding
@@ -22,4 +22,7 @@ def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ct
     if name in ("PoseRefiner", "RefineConfig", "RefineResult"):
         from . import refine
         return getattr(refine, name)
+    if name in ("PoseScorer", "ScoreConfig", "PoseScores"):
+        from . import scoring
+        return getattr(scoring, name)
     raise AttributeError(name)

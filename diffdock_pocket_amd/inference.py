@@ -36,6 +36,7 @@ from .evaluation import PoseClusters, PoseEvaluator, PoseMetrics  # noqa: F401
 from .pockets import Pocket, PocketConfig, find_pockets as _find_pockets  # noqa: F401
 from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
 from .sampler import Sampler, SamplerConfig
+from .scoring import PoseScorer, PoseScores, ScoreConfig, rank_order, typed_receptor  # noqa: F401
 
 
 @dataclass
@@ -55,6 +56,8 @@ class ComplexResult:
     refine: Optional["RefineResult"] = None        # run_csv(resolve_clashes=cfg): refine.RefineResult of the ranked poses (host tensors)
     refined_metrics: Optional["PoseMetrics"] = None  # resolve_clashes with evaluate=True: PoseMetrics of refined_pos (`metrics` is untouched)
     pockets: Optional[List["Pocket"]] = None       # run_csv(find_pockets=cfg), row without a centre: every pocket found, best first
+    scores: Optional["PoseScores"] = None          # run_csv(score_poses=cfg): scoring.PoseScores of the ranked poses (host tensors)
+    refined_scores: Optional["PoseScores"] = None  # score_poses with resolve_clashes: PoseScores of refined_pos
 
 
 def _none(v):
@@ -120,7 +123,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             allow_zero_esm: bool = False, evaluate: bool = False, out_dir: Optional[str] = None,
             save_visualisation: bool = False, cluster_rmsd: Optional[float] = None,
             resolve_clashes: Optional[RefineConfig] = None, find_pockets: Optional[PocketConfig] = None,
-            pockets_top_k: int = 1) -> List[ComplexResult]:
+            pockets_top_k: int = 1, score_poses: Optional[ScoreConfig] = None, rank_by: str = "confidence") -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -162,7 +165,20 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     result carries `pockets` (all pockets found), and with out_dir its directory gets pockets.csv (outputs.write_pockets_csv: one line
     per pocket found, `docked` = 1 for the pockets this run docked).  A protein on which no pocket survives, or that cannot be read,
     fails the row like any other per-row failure.  A row with an explicit centre keeps it and gets none of this.  None: nothing is
-    computed or written, and a row without a centre takes it from the ligand's pose as before."""
+    computed or written, and a row without a centre takes it from the ligand's pose as before.
+
+    score_poses=ScoreConfig(...): the gathered poses also get the Vinardo-form physics score of scoring.PoseScorer (an empirical function
+    over ligand-receptor atom pairs; not validated against smina or Vina, no replacement for the confidence model), before the order is
+    formed: `scores` in ranked order, with resolve_clashes also `refined_scores`, with out_dir also scores.csv
+    (outputs.write_scores_csv).  The receptor is the one the evaluation chooses: the row's full PDB for rigid rows, each sample's own
+    atom nodes for flexible rows.  rank_by="score" (implies scoring with the default ScoreConfig) orders the poses by ascending
+    `total` instead of by confidence - ties in sample order, NaN last - and everything downstream follows that order: `order`, the
+    files, the clustering, the clash relief.  rank_by="confidence" keeps the order described above exactly; without either argument
+    nothing is computed or written.  A scoring failure skips the row like a failure of the evaluation."""
+    if rank_by not in ("confidence", "score"):
+        raise ValueError(f"rank_by: 'confidence' or 'score', got {rank_by!r}")
+    if rank_by == "score" and score_poses is None:
+        score_poses = ScoreConfig()
     if pockets_top_k < 1:
         raise ValueError("pockets_top_k must be at least 1")
     if sampler_cfg is not None and sampler_cfg.svgd_weight > 0:
@@ -175,7 +191,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
             shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd, resolve_clashes,
-            find_pockets, pockets_top_k)
+            find_pockets, pockets_top_k, score_poses, rank_by)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(*args)
@@ -192,7 +208,8 @@ def _all_ok(dist, ok: bool, device) -> bool:
 
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
              world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
-             save_visualisation=False, cluster_rmsd=None, resolve_clashes=None, find_pockets=None, pockets_top_k=1) -> List[ComplexResult]:
+             save_visualisation=False, cluster_rmsd=None, resolve_clashes=None, find_pockets=None, pockets_top_k=1, score_poses=None,
+             rank_by="confidence") -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if find_pockets is not None:
         rows = expand_pocket_rows(rows, root, device, find_pockets, pockets_top_k)
@@ -237,7 +254,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             smp.randomize()
             smp.run(schedule)
             lig = smp.lig_pos
-            if ((evaluate or resolve_clashes is not None) and flex) or (out_dir is not None and moved):
+            if ((evaluate or resolve_clashes is not None or score_poses is not None) and flex) or (out_dir is not None and moved):
                 apos = smp.atom_pos.clone()
             if save_visualisation:
                 ltraj = smp.lig_traj.clone()
@@ -268,7 +285,20 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 ltraj = _gather_rows(dist, ltraj, sizes)
             if atraj is not None:
                 atraj = _gather_rows(dist, atraj, sizes)
-        if conf is not None:      # reference inference.py:212-219: descending confidence (first column of a multi-output head)
+        scorer = scores = None
+        if score_poses is not None:       # on the gathered poses, in sample order: the ranking below may depend on it
+            try:
+                scorer = _scorer_row(row, root, g, device, flex, score_poses)
+                scores = scorer.score(lig, apos if flex else None)
+            except Exception as e:      # noqa: BLE001
+                res.skipped = f"scoring: {type(e).__name__}: {e}"
+            if split and not _all_ok(dist, scores is not None, device):
+                res.skipped = res.skipped or "skipped: scoring failed on another rank"
+            if res.skipped is not None:
+                continue
+        if rank_by == "score":
+            order = rank_order(scores.total)
+        elif conf is not None:      # reference inference.py:212-219: descending confidence (first column of a multi-output head)
             key = conf[:, 0] if conf.dim() == 2 else conf
             order = torch.argsort(key, descending=True)
         else:
@@ -277,6 +307,8 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
         res.ligand_pos = lig[order].cpu()
         res.confidence = conf[order].cpu() if conf is not None else None
         res.original_center = getattr(g, "original_center", None)
+        if scores is not None:
+            res.scores = scores.index(order).cpu()
         if evaluate:
             metrics = None
             try:
@@ -286,7 +318,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, metrics is not None, device):
                 res.skipped = res.skipped or "skipped: evaluation failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = None
+                res.ligand_pos = res.confidence = res.order = res.scores = None
                 continue
             res.metrics = metrics
         if cluster_rmsd is not None:
@@ -298,23 +330,27 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, clusters is not None, device):
                 res.skipped = res.skipped or "skipped: clustering failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = None
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.scores = None
                 continue
             res.clusters = clusters
         if resolve_clashes is not None:
-            refined = None
+            refined = refined_scores = None
             try:
-                refined = _refine_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order], resolve_clashes,
-                                      evaluate)
+                done = _refine_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order], resolve_clashes,
+                                   evaluate)
+                if scorer is not None:
+                    refined_scores = scorer.score(done[0].lig_pos.to(lig.device), apos[order] if flex else None).cpu()
+                refined = done
             except Exception as e:      # noqa: BLE001
                 res.skipped = f"clash relief: {type(e).__name__}: {e}"
             if split and not _all_ok(dist, refined is not None, device):
                 res.skipped = res.skipped or "skipped: clash relief failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = None
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = None
                 continue
             res.refine, res.refined_metrics = refined
             res.refined_pos = res.refine.lig_pos
+            res.refined_scores = refined_scores
         if save_visualisation:
             res.lig_traj = ltraj[order].cpu()
             res.atom_traj = atraj[order].cpu() if atraj is not None else None
@@ -331,7 +367,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 ok = False
             if not ok:
                 res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = res.clusters = None
-                res.refined_pos = res.refine = res.refined_metrics = None
+                res.refined_pos = res.refine = res.refined_metrics = res.scores = res.refined_scores = None
                 res.files = []
     return out
 
@@ -372,7 +408,8 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
             pdb_text = f.read()
     return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
                            apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order,
-                           refine=res.refine, pockets=res.pockets, pockets_docked=row.get("pockets_docked", 0))
+                           refine=res.refine, pockets=res.pockets, pockets_docked=row.get("pockets_docked", 0), scores=res.scores,
+                           refined_scores=res.refined_scores)
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -398,6 +435,15 @@ def _refine_row(row, root, g, device, flex, lig, apos, config, evaluate):
     out = rf.refine(lig, apos if flex else None)
     metrics = _evaluate_row(row, root, g, device, flex, out.lig_pos, apos) if evaluate else None
     return out.cpu(), metrics
+
+
+def _scorer_row(row, root, g, device, flex, config) -> PoseScorer:
+    """The PoseScorer of one row (see run_csv).  The receptor is the one _evaluate_row scores against."""
+    if flex:
+        return PoseScorer(g, device, config=config)
+    with open(os.path.join(root, row["experimental_protein"])) as f:
+        rec = typed_receptor(f.read(), g.original_center)
+    return PoseScorer(g, device, receptor=rec, config=config)
 
 
 def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
@@ -454,6 +500,12 @@ def _parser():
     p.add_argument("--resolve_clashes_iterations", type=int, default=RefineConfig.iterations)
     p.add_argument("--resolve_clashes_restraint", type=float, default=RefineConfig.restraint,
                    help="weight of the restraint to the sampled pose")
+    p.add_argument("--score_poses", action="store_true", default=False,
+                   help="score every pose with this package's Vinardo-form empirical function (not validated against smina or Vina) and "
+                        "write scores.csv (default: off)")
+    p.add_argument("--rank_by", type=str, choices=("confidence", "score"), default="confidence",
+                   help="order of the written poses: the confidence model's (without one: sample order), or ascending physics score "
+                        "(implies --score_poses)")
     p.add_argument("--find_pockets", action="store_true", default=False,
                    help="complexes without --pocket_center_* / pocket_center columns: find the pocket on the protein's geometry (this "
                         "package's grid buriedness finder, no learned predictor) and dock there; writes pockets.csv (default: off)")
@@ -564,7 +616,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       cluster_rmsd=a.cluster_rmsd,
                       resolve_clashes=RefineConfig(iterations=a.resolve_clashes_iterations, restraint=a.resolve_clashes_restraint)
                       if a.resolve_clashes else None,
-                      find_pockets=pocket_config_from_args(a), pockets_top_k=a.pockets_top_k)
+                      find_pockets=pocket_config_from_args(a), pockets_top_k=a.pockets_top_k,
+                      score_poses=ScoreConfig() if (a.score_poses or a.rank_by == "score") else None, rank_by=a.rank_by)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

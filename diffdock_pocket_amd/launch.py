@@ -779,6 +779,48 @@ def refine_accept(a: L.RefineArgs):
     L.check(L.load().ddp_refine_accept(C.byref(a), stream()), "ddp_refine_accept")
 
 
+# ------------------------------------------------------------------------------------------------ physics score (csrc/ddp_score.hip)
+def pose_score(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, tor_divisor=1.0, self_pairs=None, energy=None, grad=None,
+               with_grad=False):
+    """ddp_pose_score: pos [S, n, 3], lig_radii [n], rec [m, 3] (one receptor for all samples) or [S, m, 3] (one per sample), rec_radii [m]
+    fp32 (negative: untyped); lig_flags [n], rec_flags [m] uint8 (bit 0 hydrophobic, 1 donor, 2 acceptor); self_pairs uint8 [n, n] or
+    None; config: scoring.ScoreConfig (the constants of the form).  Returns (energy [S, 7] fp64 = gauss, repulsion, hydrophobic, hbond,
+    inter, intra, total; grad [S, n, 3] fp64 or None).  energy / grad: tensors to write into (grad given, or with_grad: the gradient is
+    computed)."""
+    dev = pos.device
+    _eval_arg(pos, torch.float32, dev, "pose_score pos")
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise L.DdpError("pose_score: pos [S, n, 3]")
+    S, n = pos.shape[0], pos.shape[1]
+    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
+        raise L.DdpError("pose_score: rec [m, 3] or [S, m, 3]")
+    m = rec.shape[-2]
+    if energy is None:
+        energy = torch.empty(S, 7, dtype=torch.float64, device=dev)
+    if grad is None and with_grad:
+        grad = torch.empty(S, n, 3, dtype=torch.float64, device=dev)
+    want = [(lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"), (rec, torch.float32, None, "rec"),
+            (rec_radii, torch.float32, (m,), "rec_radii"), (rec_flags, torch.uint8, (m,), "rec_flags"),
+            (self_pairs, torch.uint8, (n, n), "self_pairs"), (energy, torch.float64, (S, 7), "energy"), (grad, torch.float64, (S, n, 3), "grad")]
+    for t, dt, shape, what in want:
+        if t is None:
+            continue
+        _eval_arg(t, dt, dev, f"pose_score {what}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise L.DdpError(f"pose_score {what}: expected {shape}, got {tuple(t.shape)}")
+    c = config
+    a = L.ScoreArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, cutoff=float(c.cutoff),
+                    gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width), hydrophobic_good=float(c.hydrophobic_good),
+                    hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good), hbond_bad=float(c.hbond_bad),
+                    w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion), w_hydrophobic=float(c.w_hydrophobic),
+                    w_hbond=float(c.w_hbond), tor_divisor=float(tor_divisor))
+    for name, t in (("pos", pos), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_radii", rec_radii),
+                    ("rec_flags", rec_flags), ("self_pairs", self_pairs), ("energy", energy), ("grad", grad)):
+        setattr(a, name, _p(t) or None)
+    L.check(L.load().ddp_pose_score(C.byref(a), stream()), "ddp_pose_score")
+    return energy, grad
+
+
 # ------------------------------------------------------------------------------------------------ pocket finder (csrc/ddp_pockets.hip)
 def _grid_n(dims) -> int:
     nx, ny, nz = (int(d) for d in dims)

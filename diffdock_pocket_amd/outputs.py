@@ -244,6 +244,34 @@ def write_clashes_csv(path: str, refine, order=None) -> str:
     return path
 
 
+# ---------------------------------------------------------------------------------------------- physics score
+SCORES_COLUMNS = ["rank", "sample", "confidence", "total", "inter", "intra", "gauss", "repulsion", "hydrophobic", "hbond"]
+
+
+def write_scores_csv(path: str, scores, confidence=None, order=None, resolved=None) -> str:
+    """scores.csv of one complex: one row per pose in RANKED order (scoring.PoseScores of the ranked poses).  rank counts from 1, sample
+    is the pose's index before ranking (order [N]; None: rank - 1), confidence is empty without a confidence model; total, inter and
+    intra are the Vinardo-form energies of scoring.py (lower is better), gauss ... hbond the unweighted sums over the ligand-receptor
+    pairs.  resolved (PoseScores of the poses after clash relief): one more column, total_resolved."""
+    import csv
+    sc = scores.cpu()
+    N = sc.total.shape[0]
+    conf = None
+    if confidence is not None:
+        conf = _np(confidence)
+        conf = conf[:, 0] if conf.ndim == 2 else conf
+    sample = list(range(N)) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    res = None if resolved is None else resolved.cpu()
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(SCORES_COLUMNS + (["total_resolved"] if res is not None else []))
+        for k in range(N):
+            w.writerow([k + 1, sample[k], "" if conf is None else f"{float(conf[k]):.4f}", f"{float(sc.total[k]):.6g}",
+                        f"{float(sc.inter[k]):.6g}", f"{float(sc.intra[k]):.6g}"] + [f"{float(v):.6g}" for v in sc.terms[k]]
+                       + ([f"{float(res.total[k]):.6g}"] if res is not None else []))
+    return path
+
+
 # ---------------------------------------------------------------------------------------------- pockets
 POCKETS_COLUMNS = ["pocket", "score", "size", "center_x", "center_y", "center_z", "ca_center_x", "ca_center_y", "ca_center_z", "docked"]
 
@@ -269,7 +297,7 @@ def complex_dir(out_dir: str, index: int, name: str) -> str:
 
 def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
                   lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None, refine=None, pockets=None,
-                  pockets_docked: int = 1) -> List[str]:
+                  pockets_docked: int = 1, scores=None, refined_scores=None) -> List[str]:
     """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
     ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
     lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
@@ -280,7 +308,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     side-chain trajectories by rank instead of by sample, inference.py:276-279).
     clusters (evaluation.PoseClusters of the ranked poses; order [N]: the sample index of each rank): also modes.csv.
     refine (refine.RefineResult of the ranked poses): also rank{k}_resolved.sdf, the pose after clash relief, and clashes.csv.
-    pockets (pockets.find_pockets of the protein, when the centre came from there): also pockets.csv."""
+    pockets (pockets.find_pockets of the protein, when the centre came from there): also pockets.csv.
+    scores (scoring.PoseScores of the ranked poses; refined_scores: of the poses after clash relief): also scores.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -325,4 +354,6 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
         write_clashes_csv(put(os.path.join(write_dir, "clashes.csv")), refine, order)
     if pockets is not None:
         write_pockets_csv(put(os.path.join(write_dir, "pockets.csv")), pockets, pockets_docked)
+    if scores is not None:
+        write_scores_csv(put(os.path.join(write_dir, "scores.csv")), scores, confidence, order, refined_scores)
     return written

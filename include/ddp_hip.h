@@ -835,6 +835,49 @@ int ddp_refine_energy(const ddp_refine_args_t* args, void* stream);
 int ddp_refine_direction(const ddp_refine_args_t* args, void* stream);
 int ddp_refine_accept(const ddp_refine_args_t* args, void* stream);
 
+/* ---- a Vinardo-form empirical score of sampled poses (csrc/ddp_score.hip; host side diffdock_pocket_amd/scoring.py, which states the
+ * whole definition and the atom typing).  The functional form of Vinardo (Quiroga & Villarreal 2016); NOT validated against smina or
+ * Vina.  n_samples poses of one complex, pos [n_samples][n][3] fp32; rec, m, rec_stride as ddp_pose_contacts (rec_stride 0: one receptor
+ * [m][3] for all samples; >= 3 m: sample s reads rec + s rec_stride).  Every atom carries a radius (fp32; negative: untyped, the atom
+ * takes part in nothing) and a flag byte (bit 0 hydrophobic, bit 1 hydrogen-bond donor, bit 2 acceptor).  self_pairs uint8 [n][n], upper
+ * triangle (NULL: no ligand-ligand term).  All arithmetic is fp64 on the fp32 inputs.  For a typed pair with centre distance
+ * d < cutoff (strict) and s = d - R_i - R_j:
+ *   gauss       = exp(-((s - gauss_offset) / gauss_width)^2)
+ *   repulsion   = s^2 if s < 0, else 0
+ *   hydrophobic = (both atoms hydrophobic)  1 if s <= hydrophobic_good, (hydrophobic_bad - s) / (hydrophobic_bad - hydrophobic_good) if
+ *                 s < hydrophobic_bad, else 0
+ *   hbond       = (one atom a donor, the other an acceptor)  the same ramp between hbond_good and hbond_bad
+ * energy[s] = [sum gauss, sum repulsion, sum hydrophobic, sum hbond (ligand-receptor pairs, unweighted), inter, intra, total]:
+ *   inter = w_gauss sum gauss + w_repulsion sum repulsion + w_hydrophobic sum hydrophobic + w_hbond sum hbond (the weights carry their
+ *   signs), intra = the same weighted sum over the pairs of self_pairs, total = inter / tor_divisor (intra is not part of it).
+ * grad[s][i] = d(inter + intra)/dx_i (NULL: not computed; the energies are the same bits either way), not divided by tor_divisor.  The
+ * ramps have their slope on the open interval only; a pair with d = 0 adds its energy and no gradient; the gradient of an untyped
+ * atom is 0.  A NaN coordinate of a typed atom gives NaN energies for that sample only.
+ * One workgroup per sample, the ligand staged in LDS (n > DDP_EVAL_MAX_ATOMS: DDP_ELIMIT), the receptor streamed through an LDS tile,
+ * every sum in a fixed order, no atomics: two launches give the same bits, and a sample's result does not depend on the other samples
+ * of the launch.  n_samples = 0: no-op; m = 0: zeros for the ligand-receptor terms.  DDP_EINVAL without a launch: a NULL struct, pos,
+ * lig_radii, lig_flags or energy (m > 0: rec, rec_radii, rec_flags), n_samples < 0, n <= 0, m < 0, 0 < rec_stride < 3 m, cutoff <= 0 or
+ * not finite, gauss_width <= 0, tor_divisor <= 0, a ramp without good < bad. */
+typedef struct {
+  int32_t n_samples, n, m, rec_stride;
+  const float* pos;             /* [n_samples][n][3] */
+  const float* lig_radii;       /* [n] */
+  const uint8_t* lig_flags;     /* [n] */
+  const float* rec;
+  const float* rec_radii;       /* [m] */
+  const uint8_t* rec_flags;     /* [m] */
+  const uint8_t* self_pairs;
+  double cutoff;
+  double gauss_offset, gauss_width;
+  double hydrophobic_good, hydrophobic_bad;
+  double hbond_good, hbond_bad;
+  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  double tor_divisor;
+  double* energy;               /* [n_samples][7] */
+  double* grad;                 /* [n_samples][n][3] */
+} ddp_score_args_t;
+int ddp_pose_score(const ddp_score_args_t* args, void* stream);
+
 /* ---- geometric pocket finder: LIGSITE-style buriedness on a grid (csrc/ddp_pockets.hip; host side diffdock_pocket_amd/pockets.py, which
  * states the whole definition).  This project's own method, no learned predictor.  Grid point (i, j, k), 0 <= i < nx ..., has the flat
  * index g = (i ny + j) nz + k and sits at lo + (i, j, k) spacing; everything outside the grid is free space.  nx ny nz < 2^31.
