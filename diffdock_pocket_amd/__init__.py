@@ -6,7 +6,8 @@ from .diffusion import SigmaRanges, get_t_schedule, get_timestep_embedding, sinu
 
 __all__ = ["HeteroBatch", "Store", "collate", "set_time", "SigmaRanges", "get_t_schedule", "get_timestep_embedding",
            "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize", "PoseRefiner",
-           "RefineConfig", "RefineResult", "PoseScorer", "ScoreConfig", "PoseScores"]
+           "RefineConfig", "RefineResult", "PoseScorer", "ScoreConfig", "PoseScores", "PoseMinimizer", "MinimizeConfig",
+           "MinimizeResult"]
 
 
 def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ctypes binding
@@ -25,4 +26,7 @@ def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ct
     if name in ("PoseScorer", "ScoreConfig", "PoseScores"):
         from . import scoring
         return getattr(scoring, name)
+    if name in ("PoseMinimizer", "MinimizeConfig", "MinimizeResult"):
+        from . import minimize
+        return getattr(minimize, name)
     raise AttributeError(name)

@@ -34,6 +34,7 @@ from . import outputs as O
 from .diffusion import get_t_schedule
 from .evaluation import PoseClusters, PoseEvaluator, PoseMetrics  # noqa: F401
 from .pockets import Pocket, PocketConfig, find_pockets as _find_pockets  # noqa: F401
+from .minimize import MinimizeConfig, MinimizeResult, PoseMinimizer  # noqa: F401
 from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 from .scoring import PoseScorer, PoseScores, ScoreConfig, rank_order, typed_receptor  # noqa: F401
@@ -58,6 +59,8 @@ class ComplexResult:
     pockets: Optional[List["Pocket"]] = None       # run_csv(find_pockets=cfg), row without a centre: every pocket found, best first
     scores: Optional["PoseScores"] = None          # run_csv(score_poses=cfg): scoring.PoseScores of the ranked poses (host tensors)
     refined_scores: Optional["PoseScores"] = None  # score_poses with resolve_clashes: PoseScores of refined_pos
+    minimized: Optional["MinimizeResult"] = None   # run_csv(minimize_poses=cfg): minimize.MinimizeResult of the ranked poses (host tensors)
+    minimized_pos: Optional[torch.Tensor] = None   # run_csv(minimize_poses=cfg): [N, n_lig, 3] the ranked poses after the minimisation
 
 
 def _none(v):
@@ -123,7 +126,8 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             allow_zero_esm: bool = False, evaluate: bool = False, out_dir: Optional[str] = None,
             save_visualisation: bool = False, cluster_rmsd: Optional[float] = None,
             resolve_clashes: Optional[RefineConfig] = None, find_pockets: Optional[PocketConfig] = None,
-            pockets_top_k: int = 1, score_poses: Optional[ScoreConfig] = None, rank_by: str = "confidence") -> List[ComplexResult]:
+            pockets_top_k: int = 1, score_poses: Optional[ScoreConfig] = None, rank_by: str = "confidence",
+            minimize_poses: Optional[MinimizeConfig] = None) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -174,11 +178,23 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     atom nodes for flexible rows.  rank_by="score" (implies scoring with the default ScoreConfig) orders the poses by ascending
     `total` instead of by confidence - ties in sample order, NaN last - and everything downstream follows that order: `order`, the
     files, the clustering, the clash relief.  rank_by="confidence" keeps the order described above exactly; without either argument
-    nothing is computed or written.  A scoring failure skips the row like a failure of the evaluation."""
-    if rank_by not in ("confidence", "score"):
-        raise ValueError(f"rank_by: 'confidence' or 'score', got {rank_by!r}")
+    nothing is computed or written.  A scoring failure skips the row like a failure of the evaluation.
+
+    minimize_poses=MinimizeConfig(...): the gathered poses, in sample order and right after the scoring, also go through
+    minimize.PoseMinimizer: a local descent of every pose in the physics score (score_poses' constants, else the default ScoreConfig)
+    along the sampler's degrees of freedom, then rescoring - no receptor motion, no global search, a score that is not validated
+    against smina or Vina.  `minimized` (a MinimizeResult) and `minimized_pos` in ranked order; with out_dir also
+    rank{k}_minimized.sdf per pose and minimized.csv (outputs.write_minimized_csv).  The receptor is the scoring's: the row's full typed
+    PDB for rigid rows, each sample's own atom nodes for flexible rows.  The clash relief is independent of it: both start from the
+    sampled poses.  rank_by="minimized_score" (implies minimisation with the default MinimizeConfig) orders the poses by ascending
+    `scores_after.total` through scoring.rank_order, and everything downstream follows that order, as with "score".  Without either
+    argument nothing is allocated, launched or written differently.  A failure skips the row like a failure of the evaluation."""
+    if rank_by not in ("confidence", "score", "minimized_score"):
+        raise ValueError(f"rank_by: 'confidence', 'score' or 'minimized_score', got {rank_by!r}")
     if rank_by == "score" and score_poses is None:
         score_poses = ScoreConfig()
+    if rank_by == "minimized_score" and minimize_poses is None:
+        minimize_poses = MinimizeConfig()
     if pockets_top_k < 1:
         raise ValueError("pockets_top_k must be at least 1")
     if sampler_cfg is not None and sampler_cfg.svgd_weight > 0:
@@ -191,7 +207,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
             shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd, resolve_clashes,
-            find_pockets, pockets_top_k, score_poses, rank_by)
+            find_pockets, pockets_top_k, score_poses, rank_by, minimize_poses)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(*args)
@@ -209,7 +225,7 @@ def _all_ok(dist, ok: bool, device) -> bool:
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
              world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
              save_visualisation=False, cluster_rmsd=None, resolve_clashes=None, find_pockets=None, pockets_top_k=1, score_poses=None,
-             rank_by="confidence") -> List[ComplexResult]:
+             rank_by="confidence", minimize_poses=None) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if find_pockets is not None:
         rows = expand_pocket_rows(rows, root, device, find_pockets, pockets_top_k)
@@ -254,7 +270,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             smp.randomize()
             smp.run(schedule)
             lig = smp.lig_pos
-            if ((evaluate or resolve_clashes is not None or score_poses is not None) and flex) or (out_dir is not None and moved):
+            if ((evaluate or resolve_clashes is not None or score_poses is not None or minimize_poses is not None) and flex) or (out_dir is not None and moved):
                 apos = smp.atom_pos.clone()
             if save_visualisation:
                 ltraj = smp.lig_traj.clone()
@@ -296,8 +312,20 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 res.skipped = res.skipped or "skipped: scoring failed on another rank"
             if res.skipped is not None:
                 continue
+        minimized = None
+        if minimize_poses is not None:    # on the gathered poses, in sample order: the ranking below may depend on it
+            try:
+                minimized = _minimize_row(row, root, g, device, flex, lig, apos, score_poses, minimize_poses)
+            except Exception as e:      # noqa: BLE001
+                res.skipped = f"minimisation: {type(e).__name__}: {e}"
+            if split and not _all_ok(dist, minimized is not None, device):
+                res.skipped = res.skipped or "skipped: minimisation failed on another rank"
+            if res.skipped is not None:
+                continue
         if rank_by == "score":
             order = rank_order(scores.total)
+        elif rank_by == "minimized_score":
+            order = rank_order(minimized.scores_after.total).to(lig.device)
         elif conf is not None:      # reference inference.py:212-219: descending confidence (first column of a multi-output head)
             key = conf[:, 0] if conf.dim() == 2 else conf
             order = torch.argsort(key, descending=True)
@@ -309,6 +337,9 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
         res.original_center = getattr(g, "original_center", None)
         if scores is not None:
             res.scores = scores.index(order).cpu()
+        if minimized is not None:
+            res.minimized = minimized.index(order.cpu())
+            res.minimized_pos = res.minimized.lig_pos
         if evaluate:
             metrics = None
             try:
@@ -318,7 +349,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, metrics is not None, device):
                 res.skipped = res.skipped or "skipped: evaluation failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.scores = None
+                res.ligand_pos = res.confidence = res.order = res.scores = res.minimized = res.minimized_pos = None
                 continue
             res.metrics = metrics
         if cluster_rmsd is not None:
@@ -330,7 +361,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, clusters is not None, device):
                 res.skipped = res.skipped or "skipped: clustering failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.scores = None
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.scores = res.minimized = res.minimized_pos = None
                 continue
             res.clusters = clusters
         if resolve_clashes is not None:
@@ -346,7 +377,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, refined is not None, device):
                 res.skipped = res.skipped or "skipped: clash relief failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = None
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = None
                 continue
             res.refine, res.refined_metrics = refined
             res.refined_pos = res.refine.lig_pos
@@ -368,6 +399,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if not ok:
                 res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = res.clusters = None
                 res.refined_pos = res.refine = res.refined_metrics = res.scores = res.refined_scores = None
+                res.minimized = res.minimized_pos = None
                 res.files = []
     return out
 
@@ -409,7 +441,7 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
     return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
                            apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order,
                            refine=res.refine, pockets=res.pockets, pockets_docked=row.get("pockets_docked", 0), scores=res.scores,
-                           refined_scores=res.refined_scores)
+                           refined_scores=res.refined_scores, minimized=res.minimized)
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -444,6 +476,17 @@ def _scorer_row(row, root, g, device, flex, config) -> PoseScorer:
     with open(os.path.join(root, row["experimental_protein"])) as f:
         rec = typed_receptor(f.read(), g.original_center)
     return PoseScorer(g, device, receptor=rec, config=config)
+
+
+def _minimize_row(row, root, g, device, flex, lig, apos, score_config, config) -> MinimizeResult:
+    """MinimizeResult of the poses of one row in sample order (see run_csv), on the host.  The receptor is the one _scorer_row takes."""
+    if flex:
+        mz = PoseMinimizer(g, device, score_config=score_config, config=config)
+    else:
+        with open(os.path.join(root, row["experimental_protein"])) as f:
+            rec = typed_receptor(f.read(), g.original_center)
+        mz = PoseMinimizer(g, device, receptor=rec, score_config=score_config, config=config)
+    return mz.minimize(lig, apos if flex else None).cpu()
 
 
 def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
@@ -503,9 +546,15 @@ def _parser():
     p.add_argument("--score_poses", action="store_true", default=False,
                    help="score every pose with this package's Vinardo-form empirical function (not validated against smina or Vina) and "
                         "write scores.csv (default: off)")
-    p.add_argument("--rank_by", type=str, choices=("confidence", "score"), default="confidence",
-                   help="order of the written poses: the confidence model's (without one: sample order), or ascending physics score "
-                        "(implies --score_poses)")
+    p.add_argument("--rank_by", type=str, choices=("confidence", "score", "minimized_score"), default="confidence",
+                   help="order of the written poses: the confidence model's (without one: sample order), ascending physics score "
+                        "(implies --score_poses), or ascending physics score after the minimisation (implies --minimize_poses)")
+    p.add_argument("--minimize_poses", action="store_true", default=False,
+                   help="minimise every pose locally in the physics score along translation, rotation and torsions (no receptor motion, "
+                        "no global search) and write rank{k}_minimized.sdf and minimized.csv beside the unchanged poses (default: off)")
+    p.add_argument("--minimize_iterations", type=int, default=MinimizeConfig.iterations)
+    p.add_argument("--minimize_restraint", type=float, default=MinimizeConfig.restraint,
+                   help="weight of the restraint to the sampled pose")
     p.add_argument("--find_pockets", action="store_true", default=False,
                    help="complexes without --pocket_center_* / pocket_center columns: find the pocket on the protein's geometry (this "
                         "package's grid buriedness finder, no learned predictor) and dock there; writes pockets.csv (default: off)")
@@ -562,6 +611,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error(f"--filtering_model_dir {a.filtering_model_dir!r} holds no model_parameters.yml")
     if a.resolve_clashes_iterations < 0 or a.resolve_clashes_restraint < 0:
         ap.error("--resolve_clashes_iterations and --resolve_clashes_restraint must not be negative")
+    if a.minimize_iterations < 0 or not a.minimize_restraint >= 0:
+        ap.error("--minimize_iterations and --minimize_restraint must not be negative")
     if a.pockets_top_k < 1 or not a.pocket_spacing > 0 or not 0 <= a.pocket_min_lines <= 7 or a.pocket_probe < 0:
         ap.error("--pockets_top_k must be at least 1, --pocket_spacing positive, --pocket_min_lines in 0..7, --pocket_probe not negative")
     if a.samples_per_complex < 1 or a.inference_steps < 1:
@@ -617,7 +668,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       resolve_clashes=RefineConfig(iterations=a.resolve_clashes_iterations, restraint=a.resolve_clashes_restraint)
                       if a.resolve_clashes else None,
                       find_pockets=pocket_config_from_args(a), pockets_top_k=a.pockets_top_k,
-                      score_poses=ScoreConfig() if (a.score_poses or a.rank_by == "score") else None, rank_by=a.rank_by)
+                      score_poses=ScoreConfig() if (a.score_poses or a.rank_by == "score") else None, rank_by=a.rank_by,
+                      minimize_poses=MinimizeConfig(iterations=a.minimize_iterations, restraint=a.minimize_restraint)
+                      if (a.minimize_poses or a.rank_by == "minimized_score") else None)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

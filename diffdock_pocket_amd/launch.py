@@ -821,6 +821,54 @@ def pose_score(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, tor
     return energy, grad
 
 
+# ------------------------------------------------------------------------------------------------ fused minimiser (csrc/ddp_minimize.hip)
+def pose_minimize(pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate, step, accepted,
+                  energy_in, energy_out, iterations, restraint=0.0, grow=2.0, shrink=0.5, step_max=1024.0, history=None, grad=None):
+    """ddp_pose_minimize: `iterations` iterations of the line search of minimize.py on every pose, in one launch.  pos (in/out), anchor
+    [S, n, 3] fp32; lig_radii [n], rec [m, 3] or [S, m, 3], rec_radii [m] fp32; lig_flags [n], rec_flags [m] uint8; self_pairs uint8 [n, n]
+    or None; config: scoring.ScoreConfig; bonds int32 [T, 2] as refine_bonds returns it (its values are not looked at here), mask_rotate
+    uint8 [T, n]; step [S] fp64 and accepted [S] int32 (in/out); energy_in, energy_out [S, 4], history [iterations + 1, S] or None,
+    grad [S, n, 3] or None, fp64.  Shapes and dtypes are checked here; no device tensor is downloaded."""
+    dev = pos.device
+    _eval_arg(pos, torch.float32, dev, "pose_minimize pos")
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise L.DdpError("pose_minimize: pos [S, n, 3]")
+    S, n = pos.shape[0], pos.shape[1]
+    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
+        raise L.DdpError("pose_minimize: rec [m, 3] or [S, m, 3]")
+    m = rec.shape[-2]
+    T = 0 if bonds is None else int(bonds.shape[0])
+    iterations = int(iterations)
+    if iterations < 0:
+        raise L.DdpError("pose_minimize: iterations < 0")
+    want = [(anchor, torch.float32, (S, n, 3), "anchor"), (lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"),
+            (rec, torch.float32, None, "rec"), (rec_radii, torch.float32, (m,), "rec_radii"), (rec_flags, torch.uint8, (m,), "rec_flags"),
+            (self_pairs, torch.uint8, (n, n), "self_pairs"), (bonds, torch.int32, (T, 2), "bonds"), (mask_rotate, torch.uint8, (T, n), "mask_rotate"),
+            (step, torch.float64, (S,), "step"), (accepted, torch.int32, (S,), "accepted"), (energy_in, torch.float64, (S, 4), "energy_in"),
+            (energy_out, torch.float64, (S, 4), "energy_out"), (history, torch.float64, (iterations + 1, S), "history"),
+            (grad, torch.float64, (S, n, 3), "grad")]
+    for t, dt, shape, what in want:
+        if t is None:
+            if what in ("self_pairs", "history", "grad") or (what in ("bonds", "mask_rotate") and T == 0):
+                continue
+            raise L.DdpError(f"pose_minimize {what}: missing")
+        _eval_arg(t, dt, dev, f"pose_minimize {what}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise L.DdpError(f"pose_minimize {what}: expected {shape}, got {tuple(t.shape)}")
+    c = config
+    a = L.MinimizeArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, n_tor=T, iterations=iterations,
+                       cutoff=float(c.cutoff), gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width),
+                       hydrophobic_good=float(c.hydrophobic_good), hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good),
+                       hbond_bad=float(c.hbond_bad), w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion),
+                       w_hydrophobic=float(c.w_hydrophobic), w_hbond=float(c.w_hbond), restraint=float(restraint), grow=float(grow),
+                       shrink=float(shrink), step_max=float(step_max))
+    for name, t in (("pos", pos), ("anchor", anchor), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_radii", rec_radii),
+                    ("rec_flags", rec_flags), ("self_pairs", self_pairs), ("bonds", bonds), ("mask_rotate", mask_rotate), ("step", step),
+                    ("accepted", accepted), ("energy_in", energy_in), ("energy_out", energy_out), ("history", history), ("grad", grad)):
+        setattr(a, name, _p(t) or None)
+    L.check(L.load().ddp_pose_minimize(C.byref(a), stream()), "ddp_pose_minimize")
+
+
 # ------------------------------------------------------------------------------------------------ pocket finder (csrc/ddp_pockets.hip)
 def _grid_n(dims) -> int:
     nx, ny, nz = (int(d) for d in dims)

@@ -272,6 +272,30 @@ def write_scores_csv(path: str, scores, confidence=None, order=None, resolved=No
     return path
 
 
+# ---------------------------------------------------------------------------------------------- minimisation in the physics score
+MINIMIZED_COLUMNS = ["rank", "sample", "total_before", "total_after", "energy_before", "energy_after", "inter_after", "intra_after",
+                     "restraint_after", "rmsd_moved", "accepted_steps"]
+
+
+def write_minimized_csv(path: str, minimized, order=None) -> str:
+    """minimized.csv of one complex: one row per pose in RANKED order (minimize.MinimizeResult of the ranked poses).  rank counts from
+    1, sample is the pose's index before ranking (order [N]; None: rank - 1); total_* are scoring.PoseScores.total of the pose before and
+    after (comparable with scores.csv), energy_* the minimised E = inter + intra + restraint term of minimize.py, rmsd_moved in
+    angstrom, accepted_steps the accepted trials of the line search."""
+    import csv
+    r = minimized.cpu()
+    sample = list(range(r.lig_pos.shape[0])) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(MINIMIZED_COLUMNS)
+        for k in range(r.lig_pos.shape[0]):
+            w.writerow([k + 1, sample[k], f"{float(r.scores_before.total[k]):.6g}", f"{float(r.scores_after.total[k]):.6g}",
+                        f"{float(r.energy_before[k, 3]):.6g}", f"{float(r.energy_after[k, 3]):.6g}", f"{float(r.energy_after[k, 0]):.6g}",
+                        f"{float(r.energy_after[k, 1]):.6g}", f"{float(r.energy_after[k, 2]):.6g}", f"{float(r.rmsd_moved[k]):.4f}",
+                        int(r.accepted[k])])
+    return path
+
+
 # ---------------------------------------------------------------------------------------------- pockets
 POCKETS_COLUMNS = ["pocket", "score", "size", "center_x", "center_y", "center_z", "ca_center_x", "ca_center_y", "ca_center_z", "docked"]
 
@@ -297,7 +321,7 @@ def complex_dir(out_dir: str, index: int, name: str) -> str:
 
 def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
                   lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None, refine=None, pockets=None,
-                  pockets_docked: int = 1, scores=None, refined_scores=None) -> List[str]:
+                  pockets_docked: int = 1, scores=None, refined_scores=None, minimized=None) -> List[str]:
     """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
     ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
     lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
@@ -309,7 +333,9 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     clusters (evaluation.PoseClusters of the ranked poses; order [N]: the sample index of each rank): also modes.csv.
     refine (refine.RefineResult of the ranked poses): also rank{k}_resolved.sdf, the pose after clash relief, and clashes.csv.
     pockets (pockets.find_pockets of the protein, when the centre came from there): also pockets.csv.
-    scores (scoring.PoseScores of the ranked poses; refined_scores: of the poses after clash relief): also scores.csv."""
+    scores (scoring.PoseScores of the ranked poses; refined_scores: of the poses after clash relief): also scores.csv.
+    minimized (minimize.MinimizeResult of the ranked poses): also rank{k}_minimized.sdf, the pose after the minimisation in the physics
+    score, and minimized.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -356,4 +382,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
         write_pockets_csv(put(os.path.join(write_dir, "pockets.csv")), pockets, pockets_docked)
     if scores is not None:
         write_scores_csv(put(os.path.join(write_dir, "scores.csv")), scores, confidence, order, refined_scores)
+    if minimized is not None:
+        for k in range(minimized.lig_pos.shape[0]):
+            write_sdf(put(os.path.join(write_dir, f"rank{k + 1}_minimized.sdf")), mol, minimized.lig_pos[k], name, oc)
+        write_minimized_csv(put(os.path.join(write_dir, "minimized.csv")), minimized, order)
     return written

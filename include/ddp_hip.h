@@ -878,6 +878,58 @@ typedef struct {
 } ddp_score_args_t;
 int ddp_pose_score(const ddp_score_args_t* args, void* stream);
 
+/* ---- local minimisation of sampled poses in the score above, the whole line search in ONE launch (csrc/ddp_minimize.hip; host side
+ * diffdock_pocket_amd/minimize.py, which states the whole definition).  Per pose x with start pose x0 = anchor[s], fp64 on the fp32
+ * inputs:
+ *   E(x) = inter(x) + intra(x) + restraint * mean_i |x_i - x0_i|^2
+ * inter, intra, radii, flags, self_pairs, rec / m / rec_stride and the constants exactly as ddp_pose_score (not divided by a torsion
+ * divisor); gradient = ddp_pose_score's + (2 restraint / n)(x - x0).  One 256-thread workgroup per pose runs `iterations` iterations;
+ * each is: the direction of ddp_refine_direction from the current gradient, multiplied by step[s] and rounded to fp32; the pose map of
+ * ddp_pose_update in fp32 (rigid move about the centroid, the torsions in bond order, Horn re-alignment) on the pose held in LDS;
+ * energy and gradient of the trial; the rule of ddp_refine_accept: E(trial) < E(x) (strict, fp64, false for NaN) takes the trial and
+ * step = min(grow step, step_max), accepted += 1, otherwise the pose is kept bit for bit and step = shrink step.
+ * In/out state: pos, step, accepted.  Outputs: energy_in / energy_out [n_samples][4] = inter, intra, restraint term, E before the first
+ * and after the last iteration; history (or NULL) [iterations + 1][n_samples] = E before the first and after every iteration; grad (or
+ * NULL) [n_samples][n][3] = the gradient of the pose at exit.
+ * The energy of a pose is a function of its fp32 coordinates and the anchor only (one evaluation routine, every sum in a fixed order,
+ * no atomics, no receptor pruning), so: two launches give the same bits; row s of a batch equals the one-sample launch; a call with
+ * a + b iterations equals a call with a followed by a call with b on the state left in memory, bit for bit.  pos[s] is written only if
+ * the call accepted a trial of sample s.  No data-dependent control flow around a barrier: a NaN pose takes the same path (its energy
+ * is NaN, it never accepts); a bonds entry outside [0, n) is skipped without a read (direction 0, no rotation).
+ * n_samples = 0: no-op.  iterations = 0: energy_in = energy_out, history[0] and grad are written, pos, step and accepted are not.
+ * DDP_EINVAL without a launch: a NULL struct or required pointer (pos, anchor, lig_radii, lig_flags, step, accepted, energy_in,
+ * energy_out; m > 0: rec, rec_radii, rec_flags; n_tor > 0: bonds, mask_rotate), n_samples < 0, n <= 0, m < 0, n_tor < 0, 0 < rec_stride
+ * < 3 m, iterations < 0, restraint < 0 (or NaN), and the constant checks of ddp_pose_score.  DDP_ELIMIT: n > DDP_MINIMIZE_MAX_ATOMS
+ * (the LDS plan is 17.9 KiB + 89 n bytes: 62.4 KiB at the limit), n_tor > DDP_MINIMIZE_MAX_TORSIONS. */
+#define DDP_MINIMIZE_MAX_ATOMS 512
+#define DDP_MINIMIZE_MAX_TORSIONS 4096
+typedef struct {
+  int32_t n_samples, n, m, rec_stride, n_tor, iterations;
+  float* pos;                   /* [n_samples][n][3], in/out */
+  const float* anchor;          /* [n_samples][n][3] */
+  const float* lig_radii;       /* [n] */
+  const uint8_t* lig_flags;     /* [n] */
+  const float* rec;
+  const float* rec_radii;       /* [m] */
+  const uint8_t* rec_flags;     /* [m] */
+  const uint8_t* self_pairs;
+  const int32_t* bonds;         /* [n_tor][2] */
+  const uint8_t* mask_rotate;   /* [n_tor][n] */
+  double cutoff;
+  double gauss_offset, gauss_width;
+  double hydrophobic_good, hydrophobic_bad;
+  double hbond_good, hbond_bad;
+  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  double restraint, grow, shrink, step_max;
+  double* step;                 /* [n_samples], in/out */
+  int32_t* accepted;            /* [n_samples], in/out */
+  double* energy_in;            /* [n_samples][4] */
+  double* energy_out;           /* [n_samples][4] */
+  double* history;              /* [iterations + 1][n_samples] or NULL */
+  double* grad;                 /* [n_samples][n][3] or NULL */
+} ddp_minimize_args_t;
+int ddp_pose_minimize(const ddp_minimize_args_t* args, void* stream);
+
 /* ---- geometric pocket finder: LIGSITE-style buriedness on a grid (csrc/ddp_pockets.hip; host side diffdock_pocket_amd/pockets.py, which
  * states the whole definition).  This project's own method, no learned predictor.  Grid point (i, j, k), 0 <= i < nx ..., has the flat
  * index g = (i ny + j) nz + k and sits at lo + (i, j, k) spacing; everything outside the grid is free space.  nx ny nz < 2^31.
