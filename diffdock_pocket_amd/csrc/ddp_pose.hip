@@ -16,24 +16,6 @@
 
 #define DDP_POSE_THREADS 128
 
-__device__ __forceinline__ void rotvec_to_matrix(float vx, float vy, float vz, float* R) {
-  // Rodrigues; small-angle series below 1e-6 as in sampler.rotvec_to_matrix / scipy
-  const float ang = sqrtf(vx * vx + vy * vy + vz * vz);
-  float a, b;
-  if (ang < 1e-6f) {
-    a = 1.0f - ang * ang / 6.0f;
-    b = 0.5f - ang * ang / 24.0f;
-  } else {
-    a = sinf(ang) / ang;
-    b = (1.0f - cosf(ang)) / (ang * ang);
-  }
-  // K = [[0,-z,y],[z,0,-x],[-y,x,0]];  R = I + a K + b K^2
-  const float xx = vx * vx, yy = vy * vy, zz = vz * vz, xy = vx * vy, xz = vx * vz, yz = vy * vz;
-  R[0] = 1.f - b * (yy + zz); R[1] = -a * vz + b * xy;     R[2] = a * vy + b * xz;
-  R[3] = a * vz + b * xy;     R[4] = 1.f - b * (xx + zz);  R[5] = -a * vx + b * yz;
-  R[6] = -a * vy + b * xz;    R[7] = a * vx + b * yz;      R[8] = 1.f - b * (xx + yy);
-}
-
 // block-wide sum of three floats (all threads get the result); red: LDS scratch of 3 * DDP_POSE_THREADS floats
 __device__ __forceinline__ void block_sum3(float& x, float& y, float& z, float* red, int tid) {
   red[tid] = x; red[DDP_POSE_THREADS + tid] = y; red[2 * DDP_POSE_THREADS + tid] = z;
@@ -134,23 +116,11 @@ __global__ __launch_bounds__(DDP_POSE_THREADS) void ddp_pose_update_kernel(const
   block_sum3(S1[0], S1[1], S1[2], red, tid);
   block_sum3(S2[0], S2[1], S2[2], red, tid);
   if (tid == 0) {
-    const double Sxx = S0[0], Sxy = S0[1], Sxz = S0[2], Syx = S1[0], Syy = S1[1], Syz = S1[2], Szx = S2[0], Szy = S2[1], Szz = S2[2];
-    double N[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
-                      {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
-                      {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
-                      {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
-    double q[4];
-    max_eigvec4(N, q);
-    const double nq = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double w = q[0] * nq, x = q[1] * nq, y = q[2] * nq, z = q[3] * nq;
-    const float R[9] = {(float)(1 - 2 * (y * y + z * z)), (float)(2 * (x * y - z * w)), (float)(2 * (x * z + y * w)),
-                        (float)(2 * (x * y + z * w)), (float)(1 - 2 * (x * x + z * z)), (float)(2 * (y * z - x * w)),
-                        (float)(2 * (x * z - y * w)), (float)(2 * (y * z + x * w)), (float)(1 - 2 * (x * x + y * y))};
+    const float S[9] = {S0[0], S0[1], S0[2], S1[0], S1[1], S1[2], S2[0], S2[1], S2[2]}, ca[3] = {cax, cay, caz}, cb[3] = {cbx, cby, cbz};
+    float R[9], t[3];
+    horn_rigid(S, ca, cb, R, t);
     for (int k = 0; k < 9; ++k) M[k] = R[k];
-    // t = cb - R ca
-    M[9] = cbx - (R[0] * cax + R[1] * cay + R[2] * caz);
-    M[10] = cby - (R[3] * cax + R[4] * cay + R[5] * caz);
-    M[11] = cbz - (R[6] * cax + R[7] * cay + R[8] * caz);
+    for (int k = 0; k < 3; ++k) M[9 + k] = t[k];
   }
   __syncthreads();
   float* __restrict__ po = pos_out + (size_t)b * n_atoms * 3;

@@ -1,0 +1,199 @@
+// ddp_pose_descent.h - the pieces that the clash relief (ddp_refine.hip), the physics score (ddp_score.hip) and the fused minimiser
+// (ddp_minimize.hip) share, each defined once: the fixed-order reductions, the search direction in pose space and the evaluation of the
+// Vinardo-form score.  All three run one 256-thread workgroup per sample.  Every function takes plain pointers (global memory or LDS:
+// the callers are inlined, so the compiler sees the address space) and the LDS carve stays the calling kernel's own.  Every sum has a
+// fixed order: a wave owns an output (a ligand atom, a rotatable bond), its 64 lanes stride over the summands, a butterfly of
+// __shfl_xor (every stage adds two equal-rank partial sums, addition is commutative: all lanes end with the same bits), and sums over
+// waves run in wave order.  No atomics: two launches give the same bits.
+#ifndef DDP_POSE_DESCENT_H
+#define DDP_POSE_DESCENT_H
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "ddp_internal.h"
+#include "ddp_score_pair.h"
+
+#define DDP_DESCENT_THREADS 256
+#define DDP_DESCENT_WAVES (DDP_DESCENT_THREADS / 64)
+#define DDP_SCORE_TILE 1024                      // receptor atoms per LDS tile of score_evaluate
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// block sum of K values, all threads get the result: butterfly, then the waves in wave order.  red: LDS, [waves][K].  Two barriers:
+// the first frees `red` of the previous sum's readers, the second publishes this one.
+template <typename T, int K>
+__device__ __forceinline__ void block_sum(T* v, T* red, int lane, int wave) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    T acc = red[k];
+    for (int w = 1; w < DDP_DESCENT_WAVES; ++w) acc += red[w * K + k];
+    v[k] = acc;
+  }
+}
+
+// ---- search direction of one sample, each degree of freedom scaled by its unit-mass inertia and multiplied by step:
+//   tr = -sum g_i / n,   rot = -sum (x_i - c) x g_i / sum |x_i - c|^2,   tor[b] = -sum g_i . a_i / sum |a_i|^2 over mask_rotate[b],
+//   a_i = u^ x (x_i - x_v), u^ = (x_u - x_v) / |x_u - x_v| (axis and sense of ddp_pose_update; atoms u and v themselves are left out of
+//   the sums: their lever is zero); a zero denominator gives 0.  fp64 on the fp32 pose x [n][3] and the gradient g [n][3], rounded to
+//   fp32 at the end.  tr[3] and rot[3] are written by every thread (EVERY_THREAD: the caller hands in registers and every thread
+//   goes on with the steps, as the fused minimiser does) or by thread 0 alone (memory, as ddp_refine_direction_kernel hands in; there
+//   the divisions of all threads would cost 32 VGPRs and three of eight waves per SIMD).  tor[b] is written by lane 0 of the wave that
+//   owns bond b = w, w + 4, ...: global memory or LDS, visible to the other threads after the caller's next barrier.  red: LDS, 4 * 6
+//   doubles.
+template <bool EVERY_THREAD>
+__device__ __forceinline__ void descent_direction(const float* __restrict__ x, const double* __restrict__ g, int n, int T,
+                                                  const int32_t* __restrict__ bonds, const uint8_t* __restrict__ mask_rotate, double step,
+                                                  double* red, float* tr, float* rot, float* tor) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += DDP_DESCENT_THREADS) {
+    v[0] += (double)x[3 * i]; v[1] += (double)x[3 * i + 1]; v[2] += (double)x[3 * i + 2];
+    v[3] += g[3 * i]; v[4] += g[3 * i + 1]; v[5] += g[3 * i + 2];
+  }
+  block_sum<double, 6>(v, red, lane, wave);
+  const double cx = v[0] / n, cy = v[1] / n, cz = v[2] / n;
+  if (EVERY_THREAD || tid == 0) {
+    tr[0] = (float)(step * (-v[3] / n)); tr[1] = (float)(step * (-v[4] / n)); tr[2] = (float)(step * (-v[5] / n));
+  }
+  double r[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += DDP_DESCENT_THREADS) {
+    const double px = (double)x[3 * i] - cx, py = (double)x[3 * i + 1] - cy, pz = (double)x[3 * i + 2] - cz;
+    const double gx = g[3 * i], gy = g[3 * i + 1], gz = g[3 * i + 2];
+    r[0] += py * gz - pz * gy; r[1] += pz * gx - px * gz; r[2] += px * gy - py * gx;
+    r[3] += px * px + py * py + pz * pz;
+  }
+  block_sum<double, 4>(r, red, lane, wave);
+  if (EVERY_THREAD || tid == 0) {
+    for (int k = 0; k < 3; ++k) rot[k] = (float)(step * (r[3] == 0.0 ? 0.0 : -r[k] / r[3]));
+  }
+  for (int b = wave; b < T; b += DDP_DESCENT_WAVES) {
+    const int u = bonds[2 * b], w = bonds[2 * b + 1];
+    double num = 0.0, den = 0.0;
+    if (u >= 0 && u < n && w >= 0 && w < n) {    // an entry outside the ligand: no read, the bond gets 0
+      const double vx = x[3 * w], vy = x[3 * w + 1], vz = x[3 * w + 2];
+      double ux = (double)x[3 * u] - vx, uy = (double)x[3 * u + 1] - vy, uz = (double)x[3 * u + 2] - vz;
+      const double len = sqrt(ux * ux + uy * uy + uz * uz);
+      ux /= len; uy /= len; uz /= len;
+      const uint8_t* __restrict__ mk = mask_rotate + (size_t)b * n;
+      for (int i = lane; i < n; i += 64) {
+        if (!mk[i] || i == u || i == w) continue;  // the bond's own atoms lie on the axis: no lever, exactly
+        const double px = (double)x[3 * i] - vx, py = (double)x[3 * i + 1] - vy, pz = (double)x[3 * i + 2] - vz;
+        const double ax = uy * pz - uz * py, ay = uz * px - ux * pz, az = ux * py - uy * px;
+        num += g[3 * i] * ax + g[3 * i + 1] * ay + g[3 * i + 2] * az;
+        den += ax * ax + ay * ay + az * az;
+      }
+    }
+    num = wave_sum(num); den = wave_sum(den);
+    if (lane == 0) tor[b] = (float)(step * (den == 0.0 ? 0.0 : -num / den));
+  }
+}
+
+// ---- the Vinardo-form score of one pose.  x [n][3], rad [n], lflag [n]: the ligand in LDS, visible to all threads no later than the
+// first barrier inside (the caller may stage it right before the call); rs: the sample's receptor in global memory, streamed through
+// tile / tflag (LDS, DDP_SCORE_TILE atoms) that all 256 threads fill with coalesced reads.  Wave w owns the ligand atoms w, w + 4, ...;
+// its lanes stride over the tile, then over the ligand atoms j with self_pairs[min(i, j)][max(i, j)].  The energy sums stay in
+// lane-private accumulators over all the atoms and tiles a lane meets (a fixed sequence) and go through one butterfly at the end;
+// with GRAD the gradient of atom i goes through the butterfly once per tile and once for the self pairs, and lane 0 adds it to
+// gacc [n][3] (LDS; tiles in increasing order, then the self pairs).  Ends with a barrier, after which we [waves][8] holds every wave's
+// partial of the eight unweighted sums (cross, then self: gauss, repulsion, hydrophobic, hbond) and gacc the gradient of inter + intra.
+template <bool GRAD, class Args>
+__device__ __forceinline__ void score_evaluate(const Args& A, const float* __restrict__ rs, float4* tile, uint8_t* tflag, const float* x,
+                                               const float* rad, const uint8_t* lflag, double* gacc, double (*we)[8]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m;
+  if (GRAD)
+    for (int i = tid; i < 3 * n; i += DDP_DESCENT_THREADS) gacc[i] = 0.0;
+  const double cut2 = A.cutoff * A.cutoff;
+  ScoreAcc cross = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};  // this lane's share, over every atom and tile it meets
+  for (int j0 = 0; j0 < m; j0 += DDP_SCORE_TILE) {
+    const int mt = min(DDP_SCORE_TILE, m - j0);
+    __syncthreads();                             // the previous tile has been used (first pass: the ligand and gacc are visible)
+    for (int j = tid; j < mt; j += DDP_DESCENT_THREADS) {
+      tile[j] = make_float4(rs[3 * (j0 + j)], rs[3 * (j0 + j) + 1], rs[3 * (j0 + j) + 2], A.rec_radii[j0 + j]);
+      tflag[j] = A.rec_flags[j0 + j];
+    }
+    __syncthreads();
+    for (int i = wave; i < n; i += DDP_DESCENT_WAVES) {
+      const double ri = rad[i];
+      if (ri < 0.0) continue;                    // an untyped ligand atom (wave-uniform, no barrier inside)
+      const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
+      const unsigned fi = lflag[i];
+      cross.gx = cross.gy = cross.gz = 0.0;
+      for (int j = lane; j < mt; j += 64) {
+        const float4 r = tile[j];
+        if (r.w < 0.f) continue;                 // an untyped receptor atom
+        score_pair<GRAD>(A, cut2, xi - (double)r.x, yi - (double)r.y, zi - (double)r.z, ri + (double)r.w, fi, tflag[j], cross);
+      }
+      if (GRAD) {
+        const double gx = wave_sum(cross.gx), gy = wave_sum(cross.gy), gz = wave_sum(cross.gz);
+        if (lane == 0) { gacc[3 * i] += gx; gacc[3 * i + 1] += gy; gacc[3 * i + 2] += gz; }   // (atom i is this wave's alone)
+      }
+    }
+  }
+  __syncthreads();                               // m = 0: the ligand and gacc are visible
+  ScoreAcc self = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};
+  for (int i = wave; i < n; i += DDP_DESCENT_WAVES) {
+    const double ri = rad[i];
+    self.gx = self.gy = self.gz = 0.0;
+    if (A.self_pairs && ri >= 0.0) {
+      const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
+      const unsigned fi = lflag[i];
+      for (int j = lane; j < n; j += 64) {
+        if (j == i || rad[j] < 0.f || !A.self_pairs[(size_t)min(i, j) * n + max(i, j)]) continue;
+        score_pair<GRAD>(A, cut2, xi - (double)x[3 * j], yi - (double)x[3 * j + 1], zi - (double)x[3 * j + 2], ri + (double)rad[j], fi,
+                         lflag[j], self);
+      }
+    }
+    if (GRAD) {
+      const double gx = wave_sum(self.gx), gy = wave_sum(self.gy), gz = wave_sum(self.gz);
+      if (lane == 0) { gacc[3 * i] = gacc[3 * i] + gx; gacc[3 * i + 1] = gacc[3 * i + 1] + gy; gacc[3 * i + 2] = gacc[3 * i + 2] + gz; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double c = wave_sum(cross.t[k]), f = wave_sum(self.t[k]);
+    if (lane == 0) { we[wave][k] = c; we[wave][4 + k] = f; }
+  }
+  __syncthreads();
+}
+
+// by one thread, after score_evaluate: t[8] = the eight sums over the waves in wave order, inter and intra = the weighted energies
+template <class Args>
+__device__ __forceinline__ void score_totals(const Args& A, const double (*we)[8], double* t, double& inter, double& intra) {
+  for (int k = 0; k < 8; ++k) {
+    t[k] = we[0][k];
+    for (int w = 1; w < DDP_DESCENT_WAVES; ++w) t[k] += we[w][k];
+  }
+  inter = A.w_gauss * t[0] + A.w_repulsion * t[1] + A.w_hydrophobic * t[2] + A.w_hbond * t[3];
+  // every self pair is met from both ends and counts half each time: exact
+  intra = A.w_gauss * (0.5 * t[4]) + A.w_repulsion * (0.5 * t[5]) + A.w_hydrophobic * (0.5 * t[6]) + A.w_hbond * (0.5 * t[7]);
+}
+
+// host: the constants of the form that ddp_pose_score and ddp_pose_minimize both take; 0, or DDP_EINVAL with a text that names `who`
+template <class Args>
+static inline int score_check_constants(const Args* a, const char* who) {
+  char msg[128];
+  const char* what = nullptr;
+  if (!(a->cutoff > 0.0) || !isfinite(a->cutoff)) what = "cutoff must be positive and finite";
+  else if (!(a->gauss_width > 0.0) || !(a->hydrophobic_bad > a->hydrophobic_good) || !(a->hbond_bad > a->hbond_good))
+    what = "gauss_width must be positive, every ramp must have good < bad";
+  if (!what) return 0;
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return ddp_fail(DDP_EINVAL, msg);
+}
+
+#endif

@@ -6,10 +6,8 @@
 // ddp_pose_update re-aligns the conformer after the torsions, so the torsion component of the search direction is NOT the exact
 // derivative of the map that is applied: the direction is a heuristic, the strict accept rule of ddp_refine_accept (E(trial) < E(x)
 // in fp64) is what guarantees descent.
-// One 256-thread workgroup per sample.  All arithmetic is fp64 on the fp32 inputs (converted first).  Every sum has a fixed order:
-// a wave owns an output (a ligand atom, a rotatable bond), its 64 lanes stride over the summands, a butterfly of __shfl_xor (every
-// stage adds two equal-rank partial sums, fp64 addition is commutative: all lanes end with the same bits), and sums over waves run in
-// wave order.  No atomics: two launches give the same bits.
+// One 256-thread workgroup per sample.  All arithmetic is fp64 on the fp32 inputs (converted first).  Every sum has a fixed order,
+// through the reductions of ddp_pose_descent.h, which also holds the search direction (shared with the fused minimiser).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -17,15 +15,10 @@
 
 #include "ddp_hip.h"
 #include "ddp_internal.h"
+#include "ddp_pose_descent.h"
 
-#define DDP_REFINE_THREADS 256
-#define DDP_REFINE_WAVES (DDP_REFINE_THREADS / 64)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
+#define DDP_REFINE_THREADS DDP_DESCENT_THREADS
+#define DDP_REFINE_WAVES DDP_DESCENT_WAVES
 
 // max(0, t - d)^2 of one pair and its gradient with respect to the first atom, added to e and (gx, gy, gz).  The square root is
 // taken only where d^2 < t^2 can hold; the comparison is written so that a NaN distance goes through and poisons the sums (a NaN
@@ -152,71 +145,12 @@ extern "C" int ddp_refine_energy(const ddp_refine_args_t* a, void* stream) {
   return 0;
 }
 
-// ---- search direction of sample s, each degree of freedom scaled by its unit-mass inertia and multiplied by step[s]:
-//   tr = -sum g_i / n,   rot = -sum (x_i - c) x g_i / sum |x_i - c|^2,   tor[b] = -sum g_i . a_i / sum |a_i|^2 over mask_rotate[b],
-//   a_i = u^ x (x_i - x_v), u^ = (x_u - x_v) / |x_u - x_v| (axis and sense of ddp_pose_update; atoms u and v themselves are left out of
-//   the sums: their lever is zero); a zero denominator gives 0.
-// Block sums: lanes stride over the atoms, butterfly, the waves in wave order.  Bonds: wave w owns b = w, w + 4, ...
-__device__ __forceinline__ void block_sum(double* v, int K, double (*red)[8], int lane, int wave) {
-  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-  __syncthreads();                               // red is free again
-  if (lane == 0)
-    for (int k = 0; k < K; ++k) red[wave][k] = v[k];
-  __syncthreads();
-  for (int k = 0; k < K; ++k) {
-    double acc = red[0][k];
-    for (int w = 1; w < DDP_REFINE_WAVES; ++w) acc += red[w][k];
-    v[k] = acc;
-  }
-}
-
+// ---- search direction of sample s: descent_direction (ddp_pose_descent.h) on the pose and the gradient in global memory
 __global__ __launch_bounds__(DDP_REFINE_THREADS) void ddp_refine_direction_kernel(const ddp_refine_args_t A) {
-  __shared__ double red[DDP_REFINE_WAVES][8];
-  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, T = A.n_tor;
-  const float* __restrict__ x = A.pos + (size_t)s * n * 3;
-  const double* __restrict__ g = A.grad + (size_t)s * n * 3;
-  const double step = A.step[s];
-  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = tid; i < n; i += DDP_REFINE_THREADS) {
-    v[0] += (double)x[3 * i]; v[1] += (double)x[3 * i + 1]; v[2] += (double)x[3 * i + 2];
-    v[3] += g[3 * i]; v[4] += g[3 * i + 1]; v[5] += g[3 * i + 2];
-  }
-  block_sum(v, 6, red, lane, wave);
-  const double cx = v[0] / n, cy = v[1] / n, cz = v[2] / n;
-  if (tid == 0) {
-    A.tr[3 * s] = (float)(step * (-v[3] / n)); A.tr[3 * s + 1] = (float)(step * (-v[4] / n)); A.tr[3 * s + 2] = (float)(step * (-v[5] / n));
-  }
-  double r[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = tid; i < n; i += DDP_REFINE_THREADS) {
-    const double px = (double)x[3 * i] - cx, py = (double)x[3 * i + 1] - cy, pz = (double)x[3 * i + 2] - cz;
-    const double gx = g[3 * i], gy = g[3 * i + 1], gz = g[3 * i + 2];
-    r[0] += py * gz - pz * gy; r[1] += pz * gx - px * gz; r[2] += px * gy - py * gx;
-    r[3] += px * px + py * py + pz * pz;
-  }
-  block_sum(r, 4, red, lane, wave);
-  if (tid == 0) {
-    for (int k = 0; k < 3; ++k) A.rot[3 * s + k] = (float)(step * (r[3] == 0.0 ? 0.0 : -r[k] / r[3]));
-  }
-  for (int b = wave; b < T; b += DDP_REFINE_WAVES) {
-    const int u = A.bonds[2 * b], w = A.bonds[2 * b + 1];
-    double num = 0.0, den = 0.0;
-    if (u >= 0 && u < n && w >= 0 && w < n) {    // an entry outside the ligand: no read, the bond gets 0
-      const double vx = x[3 * w], vy = x[3 * w + 1], vz = x[3 * w + 2];
-      double ux = (double)x[3 * u] - vx, uy = (double)x[3 * u + 1] - vy, uz = (double)x[3 * u + 2] - vz;
-      const double len = sqrt(ux * ux + uy * uy + uz * uz);
-      ux /= len; uy /= len; uz /= len;
-      const uint8_t* __restrict__ mk = A.mask_rotate + (size_t)b * n;
-      for (int i = lane; i < n; i += 64) {
-        if (!mk[i] || i == u || i == w) continue;  // the bond's own atoms lie on the axis: no lever, exactly
-        const double px = (double)x[3 * i] - vx, py = (double)x[3 * i + 1] - vy, pz = (double)x[3 * i + 2] - vz;
-        const double ax = uy * pz - uz * py, ay = uz * px - ux * pz, az = ux * py - uy * px;
-        num += g[3 * i] * ax + g[3 * i + 1] * ay + g[3 * i + 2] * az;
-        den += ax * ax + ay * ay + az * az;
-      }
-    }
-    num = wave_sum(num); den = wave_sum(den);
-    if (lane == 0) A.tor[(size_t)s * T + b] = (float)(step * (den == 0.0 ? 0.0 : -num / den));
-  }
+  __shared__ double red[DDP_REFINE_WAVES * 6];
+  const int s = blockIdx.x, n = A.n, T = A.n_tor;
+  descent_direction<false>(A.pos + (size_t)s * n * 3, A.grad + (size_t)s * n * 3, n, T, A.bonds, A.mask_rotate, A.step[s], red, A.tr + 3 * s,
+                           A.rot + 3 * s, A.tor + (size_t)s * T);
 }
 
 extern "C" int ddp_refine_direction(const ddp_refine_args_t* a, void* stream) {

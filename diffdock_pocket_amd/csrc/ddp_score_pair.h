@@ -1,15 +1,9 @@
-// ddp_score_pair.h - the pair arithmetic of the Vinardo-form score, shared by ddp_pose_score (ddp_score.hip) and the fused minimiser
-// (ddp_minimize.hip).  Args is any struct that carries the constants of the form under the names of ddp_score_args_t.
+// ddp_score_pair.h - the pair arithmetic of the Vinardo-form score, used by score_evaluate (ddp_pose_descent.h) for ddp_pose_score and
+// the fused minimiser.  Args is any struct that carries the constants of the form under the names of ddp_score_args_t.
 #ifndef DDP_SCORE_PAIR_H
 #define DDP_SCORE_PAIR_H
 #include <hip/hip_runtime.h>
 #include <math.h>
-
-__device__ __forceinline__ double score_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // The four unweighted sums (gauss, repulsion, hydrophobic, hbond) and, with GRAD, the gradient of the weighted energy with respect to
 // the first atom.

@@ -9,11 +9,9 @@ Energy of one pose x against the pose x0 it started from, fp64 on the fp32 input
 inter and intra are scoring.py's, exactly: the same ScoreConfig, typing, cutoff, self pairs and NaN rule; they are NOT divided by the
 torsion divisor.  Gradient: scoring.py's d(inter + intra)/dx plus (2 k / n)(x - x0).  Default k = 0.
 
-One iteration, per pose with its own step size: (d_tr, d_rot, d_tor) = refine.direction_torch(x, gradient), unchanged; trial =
-modify_conformer(x, step d_tr, step d_rot, step d_tor), its fp32 arguments rounded from fp64 as ddp_refine_direction rounds them.
-The accept rule is that of the clash relief: the trial is taken iff E(trial) < E(x), strictly, in fp64 (a NaN energy is never
-accepted), and then step = min(grow step, step_max); otherwise x is kept bit for bit and step = shrink step.  A fixed number of
-iterations, no convergence test, no host decision inside the loop.  MinimizeConfig holds the constants; they are untuned choices.
+The search direction and the backtracking line search with its strict accept rule are those of descent.py, which states them, shared
+with the clash relief: the trial is modify_conformer(x, step d_tr, step d_rot, step d_tor), its fp32 arguments rounded from fp64 as
+ddp_refine_direction rounds them.  MinimizeConfig holds the constants; they are untuned choices.
 
 What it does not do:
   - no receptor or side-chain motion: flexible rows are minimised against each sample's own, fixed side chains;
@@ -26,11 +24,10 @@ What it does not do:
     guarantees that E never rises.
 
 Three forms of the same algorithm:
-  - CPU tensors: the fp64 PyTorch form below, built on scoring.score_torch, refine.direction_torch and sampler.modify_conformer.  This
-    form is the definition.
+  - CPU tensors: descent.descend_torch on the fp64 energy below, built on scoring.score_torch.  This form is the definition.
   - device tensors, fused=True: csrc/ddp_minimize.hip (ddp_pose_minimize), one workgroup per pose runs all iterations in ONE launch.
-  - device tensors, fused=False: launch by launch from the existing entries (ddp_pose_score with its gradient, a few elementwise torch
-    operations for the restraint, ddp_refine_direction, ddp_pose_update, ddp_refine_accept); it never synchronises.  It is the timing
+  - device tensors, fused=False: descent.descend_hip, launch by launch from the existing entries (ddp_pose_score with its gradient and
+    a few elementwise torch operations for the restraint as the evaluation); it never synchronises.  It is the timing
     baseline and the path of ligands above the fused kernel's limits (DDP_MINIMIZE_MAX_ATOMS atoms, DDP_MINIMIZE_MAX_TORSIONS
     rotatable bonds): fused=True falls back to it there, with a one-time warning that names the limit.
 The device forms follow the CPU form up to rounding: a trial whose energy equals the current one to the last bits may be accepted by
@@ -43,8 +40,8 @@ from typing import List, Optional
 
 import torch
 
-from .refine import direction_torch, ligand_torsions
-from .sampler import modify_conformer, modify_conformer_hip, rotate_index_lists
+from .descent import DescentBuffers, descend_hip, descend_torch, ligand_torsions
+from .sampler import rotate_index_lists
 from .scoring import PoseScorer, PoseScores, ScoreConfig, score_torch
 
 
@@ -189,8 +186,12 @@ class PoseMinimizer:
         if iterations < 0:
             raise ValueError("iterations must not be negative")
         step, accepted = step.to(torch.float64).clone(), accepted.to(torch.int32).clone()
+        c = self.config
         if not x.is_cuda:
-            return self._run_torch(x, a, atom_pos, step, accepted, iterations, history)
+            t, rec = self._tables(x, atom_pos)
+            return descend_torch(lambda p: energy_torch(p, a, t["lig_r"], t["lig_f"], rec, t["rec_r"], t["rec_f"], t["pairs"], self.score_config,
+                                                        c.restraint),
+                                 x, step, accepted, iterations, c, self.bonds, self.mask_rotate, self.rot_idx, self._ref_lig, history)
         with torch.cuda.device(x.device):
             if fused and not self.fused_available():
                 from . import _lib as L
@@ -200,38 +201,15 @@ class PoseMinimizer:
                 fused = False
             if fused:
                 return self._run_fused(x, a, atom_pos, step, accepted, iterations, history, None)
-            return self._run_hip(x, a, atom_pos, step, accepted, iterations, history)
-
-    def _run_torch(self, x0, anchor, atom_pos, step, acc, iterations, history):
-        c = self.config
-        t, rec = self._tables(x0, atom_pos)
-
-        def E(p):
-            return energy_torch(p, anchor, t["lig_r"], t["lig_f"], rec, t["rec_r"], t["rec_f"], t["pairs"], self.score_config, c.restraint)
-
-        x = x0.clone()
-        e, g = E(x)
-        e0 = e.clone()
-        if history is not None:
-            history.append(e[:, 3].clone())
-        for _ in range(iterations if x.shape[0] else 0):
-            d_tr, d_rot, d_tor = direction_torch(x, g, self.bonds, self.mask_rotate)
-            # a sample without a finite energy can never accept (NaN compares false): the graph's own pose goes through the update in
-            # its place with a zero move, so that its NaNs do not reach the batched SVD of the alignment
-            fin = torch.isfinite(e[:, 3])
-            tr, rot, tor = (torch.where(fin[:, None], step[:, None] * d, torch.zeros_like(d)).float() for d in (d_tr, d_rot, d_tor))
-            trial = modify_conformer(torch.where(fin[:, None, None], x, self._ref_lig[None]), tr, rot,
-                                     tor if self.T else None, self.bonds, self.rot_idx)
-            et, gt = E(trial)
-            take = et[:, 3] < e[:, 3]                      # strict, fp64; False for NaN
-            x = torch.where(take[:, None, None], trial, x)
-            g = torch.where(take[:, None, None], gt, g)
-            e = torch.where(take[:, None], et, e)
-            step = torch.where(take, (c.step_grow * step).clamp(max=c.step_max), c.step_shrink * step)
-            acc = acc + take.to(torch.int32)
-            if history is not None:
-                history.append(e[:, 3].clone())
-        return x, step, acc, e0, e
+            from . import launch as LA
+            t, rec = self._tables(x, atom_pos)
+            b, a64 = DescentBuffers(x, self.T), a.double()
+            e7 = torch.empty(S, 7, dtype=torch.float64, device=x.device)
+            cur = LA.refine_args(b.x, a, t["lig_r"], rec, t["rec_r"], bonds=self._bonds_i32, mask_rotate=self._mask_u8, step=step,
+                                 accepted=accepted, grow=c.step_grow, shrink=c.step_shrink, step_max=c.step_max, **b.refine_kwargs())
+            x, e0, e1 = descend_hip(lambda pos, e_out, g_out: self._score_hip(pos, a64, atom_pos, e7, g_out, e_out), cur, b, iterations,
+                                    self._bonds_i32, self._mask_u8, history)
+            return x, step, accepted, e0, e1
 
     def _run_fused(self, x0, anchor, atom_pos, step, acc, iterations, history, grad):
         from . import launch as LA
@@ -260,30 +238,3 @@ class PoseMinimizer:
         g.add_(dx, alpha=2.0 * k / self.n)
         e4[:, 0], e4[:, 1], e4[:, 2] = e7[:, 4], e7[:, 5], rest
         e4[:, 3] = e7[:, 4] + e7[:, 5] + rest
-
-    def _run_hip(self, x0, anchor, atom_pos, step, acc, iterations, history):
-        from . import launch as LA
-        c = self.config
-        dev, S, n, T = x0.device, x0.shape[0], self.n, self.T
-        f64 = dict(dtype=torch.float64, device=dev)
-        t, rec = self._tables(x0, atom_pos)
-        x, trial = x0.clone(), torch.empty_like(x0)
-        a64 = anchor.double()
-        e, et, e7 = torch.empty(S, 4, **f64), torch.empty(S, 4, **f64), torch.empty(S, 7, **f64)
-        g, gt = torch.empty(S, n, 3, **f64), torch.empty(S, n, 3, **f64)
-        tr, rot, tor = torch.empty(S, 3, device=dev), torch.empty(S, 3, device=dev), torch.empty(S, T, device=dev)
-        cur = LA.refine_args(x, anchor, t["lig_r"], rec, t["rec_r"], energy=e, grad=g, bonds=self._bonds_i32, mask_rotate=self._mask_u8,
-                             step=step, tr=tr, rot=rot, tor=tor, trial=trial, trial_energy=et, trial_grad=gt, accepted=acc,
-                             grow=c.step_grow, shrink=c.step_shrink, step_max=c.step_max)
-        self._score_hip(x, a64, atom_pos, e7, g, e)
-        e0 = e.clone()
-        if history is not None:
-            history.append(e[:, 3].clone())
-        for _ in range(iterations if S else 0):
-            LA.refine_direction(cur)
-            modify_conformer_hip(x, tr, rot, tor if T else None, self._bonds_i32, self._mask_u8, out=trial)
-            self._score_hip(trial, a64, atom_pos, e7, gt, et)
-            LA.refine_accept(cur)
-            if history is not None:
-                history.append(e[:, 3].clone())
-        return x, step, acc, e0, e

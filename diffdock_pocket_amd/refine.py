@@ -11,24 +11,16 @@ pairs with t_ij <= 0 never count, receptor hydrogens (negative radius) are ignor
     E_self  = the same sum over the ligand pairs of `self_pairs` (more than 3 bonds apart AND separated by a rotatable bond)
     E_rest  = k * mean_i |x_i - x0_i|^2
 
-Search direction from the per-atom gradient g = dE/dx, each degree of freedom scaled by its unit-mass inertia (c the centroid,
-u^ the unit axis x_u - x_v of bond (u, v), a_i = u^ x (x_i - x_v) over the atoms the bond rotates, u and v themselves left out: they
-lie on the axis; a zero denominator gives 0):
-
-    d_tr = -sum g_i / n      d_rot = -sum (x_i - c) x g_i / sum |x_i - c|^2      d_tor[b] = -sum g_i . a_i / sum |a_i|^2
-
-One iteration, per sample with its own step size: trial = pose_update(x, step d_tr, step d_rot, step d_tor); the trial is taken iff
-E(trial) < E(x) strictly in fp64 (a NaN energy is never accepted) and then step = min(2 step, 1024); otherwise x is kept bit for
-bit and step = step / 2.  The pose update re-aligns the conformer after the torsions, so d_tor is not the exact derivative of the
-map that is applied: the direction is a heuristic and the accept rule is what guarantees that the energy never rises.  A fixed
-number of iterations, no convergence test, no host decision inside the loop.
+The search direction from the per-atom gradient dE/dx and the backtracking line search with its strict accept rule are those of
+descent.py, which states them (the minimiser of minimize.py runs the same loop on another energy); the step constants are
+RefineConfig's.  The pose update re-aligns the conformer after the torsions, so d_tor is not the exact derivative of the map that is
+applied: the direction is a heuristic and the accept rule is what guarantees that the energy never rises.
 
 What it does not do: no attraction or electrostatic term (it can only push atoms apart), no side-chain or receptor motion (the
 receptor is static during the refinement), no hydrogens.
 
-Device tensors go through csrc/ddp_refine.hip (ddp_refine_direction, ddp_pose_update, ddp_refine_energy, ddp_refine_accept per
-iteration: energies, step sizes and accept counters stay in device memory, nothing synchronises); CPU tensors through the PyTorch
-fp64 form below with sampler.modify_conformer as the pose update."""
+Device tensors go through descent.descend_hip with ddp_refine_energy (csrc/ddp_refine.hip) as the evaluation; CPU tensors through
+descent.descend_torch with the PyTorch fp64 energy below."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -37,8 +29,9 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from .descent import DescentBuffers, descend_hip, descend_torch, direction_torch, ligand_torsions  # noqa: F401 (the last two: re-exported)
 from .evaluation import OVERLAP_DISTANCE, PoseEvaluator
-from .sampler import modify_conformer, modify_conformer_hip, rotate_index_lists, torsion_tables
+from .sampler import rotate_index_lists
 
 
 @dataclass
@@ -68,19 +61,6 @@ class RefineResult:
 
 
 # ---------------------------------------------------------------------------------------------- host tables
-def ligand_torsions(graph):
-    """(bonds [T, 2] int64 (u, v), mask_rotate [T, n] bool) of a complex graph: sampler.torsion_tables, the tables a Sampler hands to
-    ddp_pose_update, checked against the ligand's size on the host."""
-    n = int(graph["ligand"].pos.shape[0])
-    bonds, mask = torsion_tables(graph)
-    bonds, mask = torch.as_tensor(bonds).long().reshape(-1, 2), mask.reshape(-1, n)
-    if mask.shape[0] != bonds.shape[0]:
-        raise ValueError(f"mask_rotate has {mask.shape[0]} rows for {bonds.shape[0]} rotatable bonds")
-    if bonds.numel() and (int(bonds.min()) < 0 or int(bonds.max()) >= n):
-        raise ValueError(f"rotatable bond outside the ligand's {n} atoms")
-    return bonds, mask
-
-
 def build_self_pairs(n: int, edge_index, mask_rotate) -> torch.Tensor:
     """uint8 [n, n], upper triangle: pair (i, j), i < j, counts iff its topological distance in the ligand bond graph is greater
     than 3 bonds (or there is no path) and some rotatable bond has mask_rotate[b][i] != mask_rotate[b][j], i.e. some torsion can
@@ -138,28 +118,6 @@ def energy_torch(x, anchor, lig_r, rec, rec_r, self_pairs, overlap, restraint):
     g += (2.0 * restraint / n) * dx
     e[:, 3] = e[:, 0] + e[:, 1] + e[:, 2]
     return e, g
-
-
-def direction_torch(x, g, bonds, mask_rotate):
-    """fp64 (d_tr [S, 3], d_rot [S, 3], d_tor [S, T]) of the module docstring (not yet multiplied by the step)."""
-    x = x.double()
-    n = x.shape[1]
-    zero = torch.zeros((), dtype=torch.float64)
-    d_tr = -g.sum(1) / n
-    p = x - x.mean(1, keepdim=True)
-    den = p.pow(2).sum((1, 2))
-    d_rot = torch.where(den[:, None] == 0, zero, -torch.cross(p, g, dim=-1).sum(1) / den[:, None])
-    d_tor = torch.zeros(x.shape[0], bonds.shape[0], dtype=torch.float64)
-    for b in range(bonds.shape[0]):
-        u, v = int(bonds[b, 0]), int(bonds[b, 1])
-        axis = x[:, u] - x[:, v]
-        axis = axis / axis.norm(dim=-1, keepdim=True)
-        mk = mask_rotate[b].bool().clone()
-        mk[u] = mk[v] = False                              # the bond's own atoms lie on the axis: no lever, exactly
-        a = torch.cross(axis[:, None, :].expand(-1, int(mk.sum()), -1), x[:, mk] - x[:, v:v + 1], dim=-1)
-        num, dn = (g[:, mk] * a).sum((1, 2)), a.pow(2).sum((1, 2))
-        d_tor[:, b] = torch.where(dn == 0, zero, -num / dn)
-    return d_tr, d_rot, d_tor
 
 
 # ---------------------------------------------------------------------------------------------- refiner
@@ -234,75 +192,23 @@ class PoseRefiner:
         self._check(lig_pos, atom_pos)
         x0 = lig_pos.float().contiguous()
         lig_r, rec, rec_r = self._tables(x0, atom_pos)
-        if x0.is_cuda:
-            with torch.cuda.device(x0.device):
-                x, e0, e1, acc = self._refine_hip(x0, lig_r, rec, rec_r, history)
-        else:
-            x, e0, e1, acc = self._refine_torch(x0, lig_r, rec, rec_r, history)
-        moved = (x.double() - x0.double()).pow(2).sum(-1).mean(-1).sqrt().float()
-        return RefineResult(x, e0, e1, self.clashes(x0, atom_pos), self.clashes(x, atom_pos), moved, acc)
-
-    def _refine_torch(self, x0, lig_r, rec, rec_r, history):
         c = self.config
         S = x0.shape[0]
-
-        def E(p):
-            return energy_torch(p, x0, lig_r, rec, rec_r, self.self_pairs, self.overlap, c.restraint)
-
-        x = x0.clone()
-        e, g = E(x)
-        e0 = e.clone()
-        step = torch.full((S,), float(c.step_init), dtype=torch.float64)
-        acc = torch.zeros(S, dtype=torch.int32)
-        if history is not None:
-            history.append(e[:, 3].clone())
-        for _ in range(c.iterations):
-            d_tr, d_rot, d_tor = direction_torch(x, g, self.bonds, self.mask_rotate)
-            # a sample without a finite energy can never accept (NaN compares false): the graph's own pose goes through the update in
-            # its place with a zero move, so that its NaNs do not reach the batched SVD of the alignment
-            fin = torch.isfinite(e[:, 3])
-            tr, rot, tor = (torch.where(fin[:, None], step[:, None] * d, torch.zeros_like(d)).float() for d in (d_tr, d_rot, d_tor))
-            trial = modify_conformer(torch.where(fin[:, None, None], x, self._ref_lig[None]), tr, rot,
-                                     tor if self.T else None, self.bonds, self.rot_idx)
-            et, gt = E(trial)
-            take = et[:, 3] < e[:, 3]                      # strict, fp64; False for NaN
-            x = torch.where(take[:, None, None], trial, x)
-            g = torch.where(take[:, None, None], gt, g)
-            e = torch.where(take[:, None], et, e)
-            step = torch.where(take, (c.step_grow * step).clamp(max=c.step_max), c.step_shrink * step)
-            acc += take.to(torch.int32)
-            if history is not None:
-                history.append(e[:, 3].clone())
-        return x, e0, e, acc
-
-    def _refine_hip(self, x0, lig_r, rec, rec_r, history):
-        from . import launch as LA
-        c = self.config
-        dev, S, n, T = x0.device, x0.shape[0], self.n, self.T
-        f64 = dict(dtype=torch.float64, device=dev)
-        x, trial = x0.clone(), torch.empty_like(x0)
-        e, et = torch.empty(S, 4, **f64), torch.empty(S, 4, **f64)
-        g, gt = torch.empty(S, n, 3, **f64), torch.empty(S, n, 3, **f64)
-        step = torch.full((S,), float(c.step_init), **f64)
-        acc = torch.zeros(S, dtype=torch.int32, device=dev)
-        tr, rot = torch.empty(S, 3, device=dev), torch.empty(S, 3, device=dev)
-        tor = torch.empty(S, T, device=dev)
-        common = dict(lig_radii=lig_r, rec=rec, rec_radii=rec_r, self_pairs=self._pairs_dev, overlap=self.overlap, restraint=c.restraint)
-        cur = LA.refine_args(x, x0, energy=e, grad=g, bonds=self._bonds_i32, mask_rotate=self._mask_u8, step=step, tr=tr, rot=rot,
-                             tor=tor, trial=trial, trial_energy=et, trial_grad=gt, accepted=acc, grow=c.step_grow,
-                             shrink=c.step_shrink, step_max=c.step_max, **common)
-        tri = LA.refine_args(trial, x0, energy=et, grad=gt, **common)
-        LA.refine_energy(cur)
-        e0 = e.clone()
-        if history is not None:
-            history.append(e[:, 3].clone())
-        for _ in range(c.iterations if S else 0):
-            LA.refine_direction(cur)
-            # ddp_pose_update, the existing kernel: x -> trial (never in place: the accept kernel may have to keep x)
-            modify_conformer_hip(x, tr, rot, tor if T else None, self._bonds_i32, self._mask_u8, out=trial)
-            LA.refine_energy(tri)
-            LA.refine_accept(cur)
-            if history is not None:
-                history.append(e[:, 3].clone())
-        return x, e0, e, acc
-
+        step = torch.full((S,), float(c.step_init), dtype=torch.float64, device=x0.device)
+        acc = torch.zeros(S, dtype=torch.int32, device=x0.device)
+        if x0.is_cuda:
+            from . import launch as LA
+            with torch.cuda.device(x0.device):
+                b = DescentBuffers(x0, self.T)
+                common = dict(lig_radii=lig_r, rec=rec, rec_radii=rec_r, self_pairs=self._pairs_dev, overlap=self.overlap, restraint=c.restraint)
+                cur = LA.refine_args(b.x, x0, bonds=self._bonds_i32, mask_rotate=self._mask_u8, step=step, accepted=acc, grow=c.step_grow,
+                                     shrink=c.step_shrink, step_max=c.step_max, **b.refine_kwargs(), **common)
+                tri = LA.refine_args(b.trial, x0, energy=b.et, grad=b.gt, **common)
+                # (the loop evaluates b.x into b.e, b.g once and b.trial into b.et, b.gt from then on: both structs are built once)
+                x, e0, e1 = descend_hip(lambda pos, e_out, g_out: LA.refine_energy(cur if pos is b.x else tri), cur, b, c.iterations,
+                                        self._bonds_i32, self._mask_u8, history)
+        else:
+            x, _, acc, e0, e1 = descend_torch(lambda p: energy_torch(p, x0, lig_r, rec, rec_r, self.self_pairs, self.overlap, c.restraint),
+                                              x0, step, acc, c.iterations, c, self.bonds, self.mask_rotate, self.rot_idx, self._ref_lig, history)
+        moved = (x.double() - x0.double()).pow(2).sum(-1).mean(-1).sqrt().float()
+        return RefineResult(x, e0, e1, self.clashes(x0, atom_pos), self.clashes(x, atom_pos), moved, acc)

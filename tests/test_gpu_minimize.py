@@ -89,6 +89,31 @@ def test_zero_iterations_match_the_fp64_restatement(n, m):
     print(f"n={n} m={m}: worst |err| / bound energy {worst_e:.3e}, gradient {worst_g:.3e}")
 
 
+@pytest.mark.parametrize("with_pairs", [True, False])
+@pytest.mark.parametrize("m", [0, 1, TILE + 1])
+@pytest.mark.parametrize("n", [1, 5, 37, 256])
+def test_zero_iterations_equal_ddp_pose_score_bit_for_bit(n, m, with_pairs):
+    """Both entries evaluate the score through the one score_evaluate of csrc/ddp_pose_descent.h: with restraint 0 and iterations = 0,
+    energy_in[:, 0:2] of ddp_pose_minimize are the bits of energy[:, 4:6] of ddp_pose_score (gradient variant, tor_divisor 1) on the
+    same poses, and the two gradients are the same bits.  S = 3; n = 5 is one more than the waves, n = 256 the fused limit; m = no
+    tile, one atom, one atom into the second tile; one untyped atom on either side wherever there is more than one."""
+    dev = _dev()
+    t, _ = as_torch(V.random_case(3, n, m, 53 * n + m + with_pairs, False, with_pairs))
+    if n > 1:
+        t[1][n // 2] = -1.0
+    if m > 1:
+        t[4][m // 2] = -1.0
+    td = [None if a is None else a.to(dev) for a in t]
+    x, lig_r, lig_f, rec, rec_r, rec_f, pairs = td
+    assert (pairs is None) == (not with_pairs)
+    _, _, _, e0, _, _, g = _raw(td, x, 0, 0.0)
+    e7, gs = LA.pose_score(x, lig_r, lig_f, rec, rec_r, rec_f, CFG, 1.0, pairs, with_grad=True)
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(e0[:, 0:2]), _bits(e7[:, 4:6])), (e0[:, 0:2] - e7[:, 4:6]).abs().max()
+    assert torch.equal(_bits(g), _bits(gs)), (g - gs).abs().max()
+    assert bool(torch.isfinite(gs).all())
+
+
 # ---------------------------------------------------------------------------------------------- 2. one iteration against the CPU form
 @pytest.mark.parametrize("fused", [True, False])
 def test_one_iteration_matches_the_cpu_form(fused):
