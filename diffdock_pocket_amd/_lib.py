@@ -19,10 +19,11 @@ FS = 68  # feature-buffer row stride of ddp_conv.hip
 DDP_MAX_GEMM_BATCH = 16
 DDP_EVAL_MAX_ATOMS = 1024
 DDP_MINIMIZE_MAX_ATOMS, DDP_MINIMIZE_MAX_TORSIONS = 512, 4096
+DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS, DDP_MINIMIZE_FLEX_MAX_STATE_BYTES = 256, 256, 47040
 DDP_PAIRWISE_MAX_SAMPLES, DDP_CLUSTER_MAX_SAMPLES = 32768, 1024
 EXPORTS = ["ddp_conv_messages", "ddp_conv_rows", "ddp_stage_a_gh", "ddp_stage_a_gh3", "ddp_segment_reduce", "ddp_edge_featurize", "ddp_edge_featurize_jobs", "ddp_torsion_sh", "ddp_stage_a", "ddp_stage_a_h2",
            "ddp_pose_update", "ddp_sidechain_update", "ddp_sde_update", "ddp_radius_count", "ddp_radius_fill", "ddp_knn", "ddp_group_by_key", "ddp_node_linear", "ddp_scan_jobs", "ddp_mark_jobs", "ddp_rowcopy_jobs", "ddp_select_jobs",
-           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_pose_score", "ddp_pose_minimize", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
+           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_pose_score", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
 
 
 class Seg(C.Structure):
@@ -131,6 +132,18 @@ class MinimizeArgs(C.Structure):
                 ("w_gauss", C.c_double), ("w_repulsion", C.c_double), ("w_hydrophobic", C.c_double), ("w_hbond", C.c_double),
                 ("restraint", C.c_double), ("grow", C.c_double), ("shrink", C.c_double), ("step_max", C.c_double), ("step", _P),
                 ("accepted", _P), ("energy_in", _P), ("energy_out", _P), ("history", _P), ("grad", _P)]
+
+
+class MinimizeFlexArgs(C.Structure):
+    """ddp_minimize_flex_args_t of include/ddp_hip.h: the fields of ddp_minimize_args_t, then the side chains'."""
+    _fields_ = MinimizeArgs._fields_ + [("rec_anchor", _P), ("n_mov", _I), ("n_sc", _I), ("n_sub", _I), ("reserved", _I), ("mov", _P),
+                                        ("sc_edge_idx", _P), ("sc_sub", _P), ("sc_map", _P), ("sc_pairs", _P),
+                                        ("restraint_sc", C.c_double), ("grad_mov", _P)]
+
+
+def flex_state_bytes(n: int, n_mov: int, n_sc: int) -> int:
+    """The per-atom part of ddp_pose_minimize_flex's LDS plan, bounded by DDP_MINIMIZE_FLEX_MAX_STATE_BYTES."""
+    return 89 * n + 81 * n_mov + 4 * n_sc
 
 
 class GroupJob(C.Structure):
@@ -303,6 +316,8 @@ def load():
     lib.ddp_pose_score.restype = C.c_int
     lib.ddp_pose_minimize.argtypes = [C.POINTER(MinimizeArgs), C.c_void_p]
     lib.ddp_pose_minimize.restype = C.c_int
+    lib.ddp_pose_minimize_flex.argtypes = [C.POINTER(MinimizeFlexArgs), C.c_void_p]
+    lib.ddp_pose_minimize_flex.restype = C.c_int
     lib.ddp_pocket_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p]
     lib.ddp_pocket_occupancy.restype = C.c_int

@@ -77,81 +77,11 @@ __device__ __forceinline__ void mz_evaluate(const ddp_minimize_args_t& A, const 
   __syncthreads();
 }
 
-// xt = the pose map of ddp_pose_update_kernel applied to x with (tr, rot, tor), fp32.  Ends with a barrier: xt is visible on return.
+// xt = the pose map of ddp_pose_update_kernel applied to x with (tr, rot, tor): descent_pose_update of ddp_pose_descent.h on this kernel's
+// carve (the torsion steps in the tile's first floats).  Ends with a barrier: xt is visible on return.
 __device__ __forceinline__ void mz_pose_update(const ddp_minimize_args_t& A, const MzLds& L, const float* x, float* xt, const float* tr,
                                                const float* rot) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, T = A.n_tor;
-  float* redf = (float*)L.red;
-  const float* tor = (const float*)L.tile;
-  float* rg = L.rg;
-  const float inv_n = 1.0f / (float)n;
-  float M[9];
-  // rigid move about the centre: (x - c) R^T + tr + c
-  float c[3] = {0.f, 0.f, 0.f};
-  for (int i = tid; i < n; i += DDP_MZ_THREADS) { c[0] += x[3 * i]; c[1] += x[3 * i + 1]; c[2] += x[3 * i + 2]; }
-  block_sum<float, 3>(c, redf, lane, wave);
-  {
-    const float cx = c[0] * inv_n, cy = c[1] * inv_n, cz = c[2] * inv_n;
-    rotvec_to_matrix(rot[0], rot[1], rot[2], M);
-    const float tx = tr[0] + cx, ty = tr[1] + cy, tz = tr[2] + cz;
-    for (int i = tid; i < n; i += DDP_MZ_THREADS) {
-      const float px = x[3 * i] - cx, py = x[3 * i + 1] - cy, pz = x[3 * i + 2] - cz;
-      const float ox = M[0] * px + M[1] * py + M[2] * pz + tx, oy = M[3] * px + M[4] * py + M[5] * pz + ty,
-                  oz = M[6] * px + M[7] * py + M[8] * pz + tz;
-      xt[3 * i] = ox; xt[3 * i + 1] = oy; xt[3 * i + 2] = oz;
-      rg[3 * i] = ox; rg[3 * i + 1] = oy; rg[3 * i + 2] = oz;
-    }
-  }
-  __syncthreads();
-  if (T == 0) return;                            // (the same for all threads)
-  // torsions, in bond order: the atoms of mask_rotate[j] turn about the axis xt[u] - xt[v] through xt[v]
-  for (int j = 0; j < T; ++j) {
-    const int u = A.bonds[2 * j], v = A.bonds[2 * j + 1];
-    if (u < 0 || u >= n || v < 0 || v >= n) continue;   // an entry outside the ligand: no read, no rotation (the same for all threads)
-    const float pvx = xt[3 * v], pvy = xt[3 * v + 1], pvz = xt[3 * v + 2];
-    const float ax = xt[3 * u] - pvx, ay = xt[3 * u + 1] - pvy, az = xt[3 * u + 2] - pvz;
-    const float k = tor[j] / sqrtf(ax * ax + ay * ay + az * az);
-    rotvec_to_matrix(ax * k, ay * k, az * k, M);
-    __syncthreads();                             // every thread has read the axis before an atom on it may move
-    const uint8_t* __restrict__ mk = A.mask_rotate + (size_t)j * n;
-    for (int i = tid; i < n; i += DDP_MZ_THREADS)
-      if (mk[i]) {
-        const float px = xt[3 * i] - pvx, py = xt[3 * i + 1] - pvy, pz = xt[3 * i + 2] - pvz;
-        xt[3 * i] = M[0] * px + M[1] * py + M[2] * pz + pvx;
-        xt[3 * i + 1] = M[3] * px + M[4] * py + M[5] * pz + pvy;
-        xt[3 * i + 2] = M[6] * px + M[7] * py + M[8] * pz + pvz;
-      }
-    __syncthreads();
-  }
-  // Horn / Kabsch alignment of xt (A) onto rg (B): centroids, covariance S[x][y] = sum (a - ca)_x (b - cb)_y
-  float ab[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i = tid; i < n; i += DDP_MZ_THREADS) {
-    ab[0] += xt[3 * i]; ab[1] += xt[3 * i + 1]; ab[2] += xt[3 * i + 2];
-    ab[3] += rg[3 * i]; ab[4] += rg[3 * i + 1]; ab[5] += rg[3 * i + 2];
-  }
-  block_sum<float, 6>(ab, redf, lane, wave);
-  const float cax = ab[0] * inv_n, cay = ab[1] * inv_n, caz = ab[2] * inv_n, cbx = ab[3] * inv_n, cby = ab[4] * inv_n, cbz = ab[5] * inv_n;
-  float S[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i = tid; i < n; i += DDP_MZ_THREADS) {
-    const float px = xt[3 * i] - cax, py = xt[3 * i + 1] - cay, pz = xt[3 * i + 2] - caz;
-    const float p = rg[3 * i] - cbx, q = rg[3 * i + 1] - cby, r = rg[3 * i + 2] - cbz;
-    S[0] += px * p; S[1] += px * q; S[2] += px * r;
-    S[3] += py * p; S[4] += py * q; S[5] += py * r;
-    S[6] += pz * p; S[7] += pz * q; S[8] += pz * r;
-  }
-  block_sum<float, 9>(S, redf, lane, wave);
-  {
-    const float ca[3] = {cax, cay, caz}, cb[3] = {cbx, cby, cbz};
-    float R[9], t[3];
-    horn_rigid(S, ca, cb, R, t);                 // by every thread, on the same sums: the same bits
-    for (int i = tid; i < n; i += DDP_MZ_THREADS) {   // (atom i is this thread's alone)
-      const float px = xt[3 * i], py = xt[3 * i + 1], pz = xt[3 * i + 2];
-      xt[3 * i] = R[0] * px + R[1] * py + R[2] * pz + t[0];
-      xt[3 * i + 1] = R[3] * px + R[4] * py + R[5] * pz + t[1];
-      xt[3 * i + 2] = R[6] * px + R[7] * py + R[8] * pz + t[2];
-    }
-  }
-  __syncthreads();
+  descent_pose_update(A, x, xt, L.rg, (const float*)L.tile, (float*)L.red, tr, rot);
 }
 
 __global__ __launch_bounds__(DDP_MZ_THREADS) void ddp_pose_minimize_kernel(const ddp_minimize_args_t A) {

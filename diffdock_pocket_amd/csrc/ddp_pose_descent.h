@@ -1,6 +1,7 @@
-// ddp_pose_descent.h - the pieces that the clash relief (ddp_refine.hip), the physics score (ddp_score.hip) and the fused minimiser
-// (ddp_minimize.hip) share, each defined once: the fixed-order reductions, the search direction in pose space and the evaluation of the
-// Vinardo-form score.  All three run one 256-thread workgroup per sample.  Every function takes plain pointers (global memory or LDS:
+// ddp_pose_descent.h - the pieces that the clash relief (ddp_refine.hip), the physics score (ddp_score.hip), the fused minimiser
+// (ddp_minimize.hip) and the joint minimiser (ddp_minimize_flex.hip) share, each defined once: the fixed-order reductions, the search
+// direction in pose space, the pose map on a pose held in LDS and the evaluation of the Vinardo-form score.  All of them run one
+// 256-thread workgroup per sample.  Every function takes plain pointers (global memory or LDS:
 // the callers are inlined, so the compiler sees the address space) and the LDS carve stays the calling kernel's own.  Every sum has a
 // fixed order: a wave owns an output (a ligand atom, a rotatable bond), its 64 lanes stride over the summands, a butterfly of
 // __shfl_xor (every stage adds two equal-rank partial sums, addition is commutative: all lanes end with the same bits), and sums over
@@ -13,6 +14,7 @@
 #include <stdio.h>
 
 #include "ddp_internal.h"
+#include "ddp_horn.h"
 #include "ddp_score_pair.h"
 
 #define DDP_DESCENT_THREADS 256
@@ -103,6 +105,86 @@ __device__ __forceinline__ void descent_direction(const float* __restrict__ x, c
   }
 }
 
+// ---- xt = the pose map of ddp_pose_update_kernel applied to x with (tr, rot, tor), fp32, on a pose held in LDS: the rigid move about the
+// centroid, the torsions in bond order, the Horn re-alignment through ddp_horn.h (every thread runs the 4x4 Jacobi on the same block
+// sums: the same bits in every thread, and no barrier to publish a matrix).  A: the kernel's arguments (n, n_tor, bonds, mask_rotate);
+// rg [n][3]: LDS, receives the rigid copy; tor [n_tor]: the torsion steps, LDS, visible on entry; redf: LDS scratch of block_sum, at
+// least [waves][9] floats.  Called by all 256 threads; ends with a barrier: xt is visible on return.  Shared by the fused minimiser
+// (ddp_minimize.hip) and the joint minimiser (ddp_minimize_flex.hip).
+template <class Args>
+__device__ __forceinline__ void descent_pose_update(const Args& A, const float* x, float* xt, float* rg, const float* tor, float* redf,
+                                                    const float* tr, const float* rot) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, T = A.n_tor;
+  const float inv_n = 1.0f / (float)n;
+  float M[9];
+  // rigid move about the centre: (x - c) R^T + tr + c
+  float c[3] = {0.f, 0.f, 0.f};
+  for (int i = tid; i < n; i += DDP_DESCENT_THREADS) { c[0] += x[3 * i]; c[1] += x[3 * i + 1]; c[2] += x[3 * i + 2]; }
+  block_sum<float, 3>(c, redf, lane, wave);
+  {
+    const float cx = c[0] * inv_n, cy = c[1] * inv_n, cz = c[2] * inv_n;
+    rotvec_to_matrix(rot[0], rot[1], rot[2], M);
+    const float tx = tr[0] + cx, ty = tr[1] + cy, tz = tr[2] + cz;
+    for (int i = tid; i < n; i += DDP_DESCENT_THREADS) {
+      const float px = x[3 * i] - cx, py = x[3 * i + 1] - cy, pz = x[3 * i + 2] - cz;
+      const float ox = M[0] * px + M[1] * py + M[2] * pz + tx, oy = M[3] * px + M[4] * py + M[5] * pz + ty,
+                  oz = M[6] * px + M[7] * py + M[8] * pz + tz;
+      xt[3 * i] = ox; xt[3 * i + 1] = oy; xt[3 * i + 2] = oz;
+      rg[3 * i] = ox; rg[3 * i + 1] = oy; rg[3 * i + 2] = oz;
+    }
+  }
+  __syncthreads();
+  if (T == 0) return;                            // (the same for all threads)
+  // torsions, in bond order: the atoms of mask_rotate[j] turn about the axis xt[u] - xt[v] through xt[v]
+  for (int j = 0; j < T; ++j) {
+    const int u = A.bonds[2 * j], v = A.bonds[2 * j + 1];
+    if (u < 0 || u >= n || v < 0 || v >= n) continue;   // an entry outside the ligand: no read, no rotation (the same for all threads)
+    const float pvx = xt[3 * v], pvy = xt[3 * v + 1], pvz = xt[3 * v + 2];
+    const float ax = xt[3 * u] - pvx, ay = xt[3 * u + 1] - pvy, az = xt[3 * u + 2] - pvz;
+    const float k = tor[j] / sqrtf(ax * ax + ay * ay + az * az);
+    rotvec_to_matrix(ax * k, ay * k, az * k, M);
+    __syncthreads();                             // every thread has read the axis before an atom on it may move
+    const uint8_t* __restrict__ mk = A.mask_rotate + (size_t)j * n;
+    for (int i = tid; i < n; i += DDP_DESCENT_THREADS)
+      if (mk[i]) {
+        const float px = xt[3 * i] - pvx, py = xt[3 * i + 1] - pvy, pz = xt[3 * i + 2] - pvz;
+        xt[3 * i] = M[0] * px + M[1] * py + M[2] * pz + pvx;
+        xt[3 * i + 1] = M[3] * px + M[4] * py + M[5] * pz + pvy;
+        xt[3 * i + 2] = M[6] * px + M[7] * py + M[8] * pz + pvz;
+      }
+    __syncthreads();
+  }
+  // Horn / Kabsch alignment of xt (A) onto rg (B): centroids, covariance S[x][y] = sum (a - ca)_x (b - cb)_y
+  float ab[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = tid; i < n; i += DDP_DESCENT_THREADS) {
+    ab[0] += xt[3 * i]; ab[1] += xt[3 * i + 1]; ab[2] += xt[3 * i + 2];
+    ab[3] += rg[3 * i]; ab[4] += rg[3 * i + 1]; ab[5] += rg[3 * i + 2];
+  }
+  block_sum<float, 6>(ab, redf, lane, wave);
+  const float cax = ab[0] * inv_n, cay = ab[1] * inv_n, caz = ab[2] * inv_n, cbx = ab[3] * inv_n, cby = ab[4] * inv_n, cbz = ab[5] * inv_n;
+  float S[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = tid; i < n; i += DDP_DESCENT_THREADS) {
+    const float px = xt[3 * i] - cax, py = xt[3 * i + 1] - cay, pz = xt[3 * i + 2] - caz;
+    const float p = rg[3 * i] - cbx, q = rg[3 * i + 1] - cby, r = rg[3 * i + 2] - cbz;
+    S[0] += px * p; S[1] += px * q; S[2] += px * r;
+    S[3] += py * p; S[4] += py * q; S[5] += py * r;
+    S[6] += pz * p; S[7] += pz * q; S[8] += pz * r;
+  }
+  block_sum<float, 9>(S, redf, lane, wave);
+  {
+    const float ca[3] = {cax, cay, caz}, cb[3] = {cbx, cby, cbz};
+    float R[9], t[3];
+    horn_rigid(S, ca, cb, R, t);                 // by every thread, on the same sums: the same bits
+    for (int i = tid; i < n; i += DDP_DESCENT_THREADS) {   // (atom i is this thread's alone)
+      const float px = xt[3 * i], py = xt[3 * i + 1], pz = xt[3 * i + 2];
+      xt[3 * i] = R[0] * px + R[1] * py + R[2] * pz + t[0];
+      xt[3 * i + 1] = R[3] * px + R[4] * py + R[5] * pz + t[1];
+      xt[3 * i + 2] = R[6] * px + R[7] * py + R[8] * pz + t[2];
+    }
+  }
+  __syncthreads();
+}
+
 // ---- the Vinardo-form score of one pose.  x [n][3], rad [n], lflag [n]: the ligand in LDS, visible to all threads no later than the
 // first barrier inside (the caller may stage it right before the call); rs: the sample's receptor in global memory, streamed through
 // tile / tflag (LDS, DDP_SCORE_TILE atoms) that all 256 threads fill with coalesced reads.  Wave w owns the ligand atoms w, w + 4, ...;
@@ -111,9 +193,17 @@ __device__ __forceinline__ void descent_direction(const float* __restrict__ x, c
 // with GRAD the gradient of atom i goes through the butterfly once per tile and once for the self pairs, and lane 0 adds it to
 // gacc [n][3] (LDS; tiles in increasing order, then the self pairs).  Ends with a barrier, after which we [waves][8] holds every wave's
 // partial of the eight unweighted sums (cross, then self: gauss, repulsion, hydrophobic, hbond) and gacc the gradient of inter + intra.
-template <bool GRAD, class Args>
+// patch: the tile-load hook, patch(j, r, f) may replace what receptor atom j brings into the tile (coordinates and radius r, flag byte
+// f); ScoreTileIdentity, the default, leaves the atom as global memory has it (ddp_pose_score, ddp_pose_minimize), the joint minimiser
+// of ddp_minimize_flex.hip puts the moving side-chain atoms in from LDS.
+struct ScoreTileIdentity {
+  __device__ __forceinline__ void operator()(int, float4&, uint8_t&) const {}
+};
+
+template <bool GRAD, class Args, class Patch = ScoreTileIdentity>
 __device__ __forceinline__ void score_evaluate(const Args& A, const float* __restrict__ rs, float4* tile, uint8_t* tflag, const float* x,
-                                               const float* rad, const uint8_t* lflag, double* gacc, double (*we)[8]) {
+                                               const float* rad, const uint8_t* lflag, double* gacc, double (*we)[8],
+                                               const Patch& patch = Patch()) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m;
   if (GRAD)
     for (int i = tid; i < 3 * n; i += DDP_DESCENT_THREADS) gacc[i] = 0.0;
@@ -123,8 +213,11 @@ __device__ __forceinline__ void score_evaluate(const Args& A, const float* __res
     const int mt = min(DDP_SCORE_TILE, m - j0);
     __syncthreads();                             // the previous tile has been used (first pass: the ligand and gacc are visible)
     for (int j = tid; j < mt; j += DDP_DESCENT_THREADS) {
-      tile[j] = make_float4(rs[3 * (j0 + j)], rs[3 * (j0 + j) + 1], rs[3 * (j0 + j) + 2], A.rec_radii[j0 + j]);
-      tflag[j] = A.rec_flags[j0 + j];
+      float4 r = make_float4(rs[3 * (j0 + j)], rs[3 * (j0 + j) + 1], rs[3 * (j0 + j) + 2], A.rec_radii[j0 + j]);
+      uint8_t f = A.rec_flags[j0 + j];
+      patch(j0 + j, r, f);
+      tile[j] = r;
+      tflag[j] = f;
     }
     __syncthreads();
     for (int i = wave; i < n; i += DDP_DESCENT_WAVES) {

@@ -35,6 +35,7 @@ from .diffusion import get_t_schedule
 from .evaluation import PoseClusters, PoseEvaluator, PoseMetrics  # noqa: F401
 from .pockets import Pocket, PocketConfig, find_pockets as _find_pockets  # noqa: F401
 from .minimize import MinimizeConfig, MinimizeResult, PoseMinimizer  # noqa: F401
+from .minimize_flex import FlexMinimizeResult, FlexPoseMinimizer  # noqa: F401
 from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 from .scoring import PoseScorer, PoseScores, ScoreConfig, rank_order, typed_receptor  # noqa: F401
@@ -59,7 +60,8 @@ class ComplexResult:
     pockets: Optional[List["Pocket"]] = None       # run_csv(find_pockets=cfg), row without a centre: every pocket found, best first
     scores: Optional["PoseScores"] = None          # run_csv(score_poses=cfg): scoring.PoseScores of the ranked poses (host tensors)
     refined_scores: Optional["PoseScores"] = None  # score_poses with resolve_clashes: PoseScores of refined_pos
-    minimized: Optional["MinimizeResult"] = None   # run_csv(minimize_poses=cfg): minimize.MinimizeResult of the ranked poses (host tensors)
+    minimized: Optional["MinimizeResult"] = None   # run_csv(minimize_poses=cfg): minimize.MinimizeResult of the ranked poses (host tensors);
+    #                                                a flexible row with cfg.sidechains: minimize_flex.FlexMinimizeResult
     minimized_pos: Optional[torch.Tensor] = None   # run_csv(minimize_poses=cfg): [N, n_lig, 3] the ranked poses after the minimisation
 
 
@@ -186,7 +188,10 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     against smina or Vina.  `minimized` (a MinimizeResult) and `minimized_pos` in ranked order; with out_dir also
     rank{k}_minimized.sdf per pose and minimized.csv (outputs.write_minimized_csv).  The receptor is the scoring's: the row's full typed
     PDB for rigid rows, each sample's own atom nodes for flexible rows.  The clash relief is independent of it: both start from the
-    sampled poses.  rank_by="minimized_score" (implies minimisation with the default MinimizeConfig) orders the poses by ascending
+    sampled poses.  minimize_poses.sidechains=True: a flexible row goes through minimize_flex.FlexPoseMinimizer instead, which moves the
+    chi angles of the flexible residues with the ligand (k_sc = minimize_poses.sidechain_restraint); `minimized` is then a
+    FlexMinimizeResult, E in minimized.csv the joint E, and with out_dir also rank{k}_minimized_protein.pdb (the receptor with the
+    minimised side chains) and minimized_sidechains.csv; rigid rows take the path above.  rank_by="minimized_score" (implies minimisation with the default MinimizeConfig) orders the poses by ascending
     `scores_after.total` through scoring.rank_order, and everything downstream follows that order, as with "score".  Without either
     argument nothing is allocated, launched or written differently.  A failure skips the row like a failure of the evaluation."""
     if rank_by not in ("confidence", "score", "minimized_score"):
@@ -435,7 +440,7 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
     with open(os.path.join(root, row["ligand"])) as f:
         sdf_text = f.read()
     pdb_text = None
-    if apos is not None or res.atom_traj is not None:
+    if apos is not None or res.atom_traj is not None or isinstance(res.minimized, FlexMinimizeResult):
         with open(os.path.join(root, row["experimental_protein"])) as f:
             pdb_text = f.read()
     return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
@@ -479,7 +484,10 @@ def _scorer_row(row, root, g, device, flex, config) -> PoseScorer:
 
 
 def _minimize_row(row, root, g, device, flex, lig, apos, score_config, config) -> MinimizeResult:
-    """MinimizeResult of the poses of one row in sample order (see run_csv), on the host.  The receptor is the one _scorer_row takes."""
+    """MinimizeResult of the poses of one row in sample order (see run_csv), on the host.  The receptor is the one _scorer_row takes.
+    A flexible row with config.sidechains: the FlexMinimizeResult of the joint minimisation."""
+    if flex and config.sidechains:
+        return FlexPoseMinimizer(g, device, score_config=score_config, config=config).minimize(lig, apos).cpu()
     if flex:
         mz = PoseMinimizer(g, device, score_config=score_config, config=config)
     else:
@@ -555,6 +563,12 @@ def _parser():
     p.add_argument("--minimize_iterations", type=int, default=MinimizeConfig.iterations)
     p.add_argument("--minimize_restraint", type=float, default=MinimizeConfig.restraint,
                    help="weight of the restraint to the sampled pose")
+    p.add_argument("--minimize_sidechains", action="store_true", default=False,
+                   help="implies --minimize_poses; flexible rows: the chi angles of the flexible residues are minimised together with "
+                        "the ligand (this package's own local descent, not the reference's --relax) and rank{k}_minimized_protein.pdb and "
+                        "minimized_sidechains.csv are written too; rigid rows are minimised as without the flag (default: off)")
+    p.add_argument("--minimize_sidechain_restraint", type=float, default=MinimizeConfig.sidechain_restraint,
+                   help="with --minimize_sidechains: weight of the restraint of the moving side-chain atoms to their sampled positions")
     p.add_argument("--find_pockets", action="store_true", default=False,
                    help="complexes without --pocket_center_* / pocket_center columns: find the pocket on the protein's geometry (this "
                         "package's grid buriedness finder, no learned predictor) and dock there; writes pockets.csv (default: off)")
@@ -613,6 +627,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--resolve_clashes_iterations and --resolve_clashes_restraint must not be negative")
     if a.minimize_iterations < 0 or not a.minimize_restraint >= 0:
         ap.error("--minimize_iterations and --minimize_restraint must not be negative")
+    if not a.minimize_sidechain_restraint >= 0:
+        ap.error("--minimize_sidechain_restraint must not be negative")
     if a.pockets_top_k < 1 or not a.pocket_spacing > 0 or not 0 <= a.pocket_min_lines <= 7 or a.pocket_probe < 0:
         ap.error("--pockets_top_k must be at least 1, --pocket_spacing positive, --pocket_min_lines in 0..7, --pocket_probe not negative")
     if a.samples_per_complex < 1 or a.inference_steps < 1:
@@ -669,8 +685,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       if a.resolve_clashes else None,
                       find_pockets=pocket_config_from_args(a), pockets_top_k=a.pockets_top_k,
                       score_poses=ScoreConfig() if (a.score_poses or a.rank_by == "score") else None, rank_by=a.rank_by,
-                      minimize_poses=MinimizeConfig(iterations=a.minimize_iterations, restraint=a.minimize_restraint)
-                      if (a.minimize_poses or a.rank_by == "minimized_score") else None)
+                      minimize_poses=MinimizeConfig(iterations=a.minimize_iterations, restraint=a.minimize_restraint,
+                                                    sidechains=a.minimize_sidechains, sidechain_restraint=a.minimize_sidechain_restraint)
+                      if (a.minimize_poses or a.minimize_sidechains or a.rank_by == "minimized_score") else None)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

@@ -869,6 +869,83 @@ def pose_minimize(pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, 
     L.check(L.load().ddp_pose_minimize(C.byref(a), stream()), "ddp_pose_minimize")
 
 
+# ------------------------------------------------------------------------------------------------ joint minimiser (csrc/ddp_minimize_flex.hip)
+def flex_tables(sc, m: int, device) -> dict:
+    """The side-chain tables of ddp_pose_minimize_flex: HOST tensors (a minimize_flex.SidechainTables, or anything with its fields mov,
+    edge_idx, sub, mapping, pairs) are checked against the m receptor atoms here, on the host, as refine_bonds checks the ligand's
+    bonds, and then uploaded (once per complex).  The device skips an entry outside the receptor without a read, but it is never
+    handed one."""
+    from .minimize_flex import check_sidechain_tables
+    host = {k: torch.as_tensor(getattr(sc, k)) for k in ("mov", "edge_idx", "sub", "mapping", "pairs")}
+    if any(t.is_cuda for t in host.values()):
+        raise L.DdpError("flex tables: the tables are validated on the host - pass host tensors")
+    mov, edge, sub, mapping = (host[k].to(torch.int64) for k in ("mov", "edge_idx", "sub", "mapping"))
+    mov, edge, sub, mapping = mov.reshape(-1), edge.reshape(-1, 2), sub.reshape(-1), mapping.reshape(-1, 2)
+    try:
+        check_sidechain_tables(m, edge, sub, mapping, mov)
+    except ValueError as e:
+        raise L.DdpError(f"flex tables: {e}") from None
+    pairs = host["pairs"]
+    if pairs.dtype != torch.uint8 or tuple(pairs.shape) != (mov.shape[0], m):
+        raise L.DdpError(f"flex tables: pairs uint8 [{mov.shape[0]}, {m}], got {pairs.dtype} {tuple(pairs.shape)}")
+    out = {k: t.to(torch.int32).contiguous().to(device) for k, t in (("mov", mov), ("edge_idx", edge), ("sub", sub), ("mapping", mapping))}
+    out["pairs"] = pairs.contiguous().to(device)
+    return out
+
+
+def pose_minimize_flex(pos, anchor, lig_radii, lig_flags, rec, rec_anchor, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate,
+                       tables, step, accepted, energy_in, energy_out, iterations, restraint=0.0, restraint_sc=0.0, grow=2.0, shrink=0.5,
+                       step_max=1024.0, history=None, grad=None, grad_mov=None):
+    """ddp_pose_minimize_flex: `iterations` iterations of the joint line search of minimize_flex.py on every pose, in one launch.  As
+    pose_minimize, with: rec (in/out) and rec_anchor [S, m, 3] fp32, one receptor per sample; tables: what flex_tables returns (its
+    values are not looked at here); energy_in, energy_out [S, 6]; grad_mov [S, n_mov, 3] fp64 or None.  Shapes and dtypes are checked
+    here; no device tensor is downloaded."""
+    dev = pos.device
+    _eval_arg(pos, torch.float32, dev, "pose_minimize_flex pos")
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise L.DdpError("pose_minimize_flex: pos [S, n, 3]")
+    S, n = pos.shape[0], pos.shape[1]
+    if rec.dim() != 3 or rec.shape[-1] != 3 or rec.shape[0] != S:
+        raise L.DdpError("pose_minimize_flex: rec [S, m, 3], one receptor per sample")
+    m = rec.shape[1]
+    T = 0 if bonds is None else int(bonds.shape[0])
+    mov, edge, sub, mapping, pairs = (tables[k] for k in ("mov", "edge_idx", "sub", "mapping", "pairs"))
+    n_mov, n_sc, n_sub = int(mov.shape[0]), int(edge.shape[0]), int(sub.shape[0])
+    iterations = int(iterations)
+    if iterations < 0:
+        raise L.DdpError("pose_minimize_flex: iterations < 0")
+    want = [(anchor, torch.float32, (S, n, 3), "anchor"), (lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"),
+            (rec, torch.float32, (S, m, 3), "rec"), (rec_anchor, torch.float32, (S, m, 3), "rec_anchor"), (rec_radii, torch.float32, (m,), "rec_radii"),
+            (rec_flags, torch.uint8, (m,), "rec_flags"), (self_pairs, torch.uint8, (n, n), "self_pairs"), (bonds, torch.int32, (T, 2), "bonds"),
+            (mask_rotate, torch.uint8, (T, n), "mask_rotate"), (mov, torch.int32, (n_mov,), "mov"), (edge, torch.int32, (n_sc, 2), "edge_idx"),
+            (sub, torch.int32, (n_sub,), "sub"), (mapping, torch.int32, (n_sc, 2), "mapping"), (pairs, torch.uint8, (n_mov, m), "pairs"),
+            (step, torch.float64, (S,), "step"), (accepted, torch.int32, (S,), "accepted"), (energy_in, torch.float64, (S, 6), "energy_in"),
+            (energy_out, torch.float64, (S, 6), "energy_out"), (history, torch.float64, (iterations + 1, S), "history"),
+            (grad, torch.float64, (S, n, 3), "grad"), (grad_mov, torch.float64, (S, n_mov, 3), "grad_mov")]
+    for t, dt, shape, what in want:
+        if t is None:
+            if what in ("self_pairs", "history", "grad", "grad_mov") or (what in ("bonds", "mask_rotate") and T == 0):
+                continue
+            raise L.DdpError(f"pose_minimize_flex {what}: missing")
+        _eval_arg(t, dt, dev, f"pose_minimize_flex {what}")
+        if tuple(t.shape) != shape:
+            raise L.DdpError(f"pose_minimize_flex {what}: expected {shape}, got {tuple(t.shape)}")
+    c = config
+    a = L.MinimizeFlexArgs(n_samples=S, n=n, m=m, rec_stride=3 * m, n_tor=T, iterations=iterations, cutoff=float(c.cutoff),
+                           gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width), hydrophobic_good=float(c.hydrophobic_good),
+                           hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good), hbond_bad=float(c.hbond_bad),
+                           w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion), w_hydrophobic=float(c.w_hydrophobic),
+                           w_hbond=float(c.w_hbond), restraint=float(restraint), grow=float(grow), shrink=float(shrink),
+                           step_max=float(step_max), n_mov=n_mov, n_sc=n_sc, n_sub=n_sub, restraint_sc=float(restraint_sc))
+    for name, t in (("pos", pos), ("anchor", anchor), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_anchor", rec_anchor),
+                    ("rec_radii", rec_radii), ("rec_flags", rec_flags), ("self_pairs", self_pairs), ("bonds", bonds), ("mask_rotate", mask_rotate),
+                    ("mov", mov), ("sc_edge_idx", edge), ("sc_sub", sub), ("sc_map", mapping), ("sc_pairs", pairs), ("step", step),
+                    ("accepted", accepted), ("energy_in", energy_in), ("energy_out", energy_out), ("history", history), ("grad", grad),
+                    ("grad_mov", grad_mov)):
+        setattr(a, name, _p(t) or None)
+    L.check(L.load().ddp_pose_minimize_flex(C.byref(a), stream()), "ddp_pose_minimize_flex")
+
+
 # ------------------------------------------------------------------------------------------------ pocket finder (csrc/ddp_pockets.hip)
 def _grid_n(dims) -> int:
     nx, ny, nz = (int(d) for d in dims)

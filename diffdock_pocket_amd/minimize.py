@@ -14,7 +14,8 @@ with the clash relief: the trial is modify_conformer(x, step d_tr, step d_rot, s
 ddp_refine_direction rounds them.  MinimizeConfig holds the constants; they are untuned choices.
 
 What it does not do:
-  - no receptor or side-chain motion: flexible rows are minimised against each sample's own, fixed side chains;
+  - no receptor or side-chain motion: flexible rows are minimised against each sample's own, fixed side chains (the joint form,
+    in which the chi angles of the flexible residues descend with the ligand, is minimize_flex.py);
   - no hydrogens;
   - no global search: it is a local descent from the sampled pose;
   - the score is not validated against smina or Vina (see scoring.py), so neither is its minimum: on the 3dpf fixture the crystal
@@ -54,6 +55,8 @@ class MinimizeConfig:
     step_grow: float = 2.0        # factor after an accepted trial
     step_shrink: float = 0.5      # factor after a rejected trial
     step_max: float = 1024.0      # cap of the step size
+    sidechains: bool = False      # run_csv: flexible rows go through minimize_flex.FlexPoseMinimizer (PoseMinimizer ignores it)
+    sidechain_restraint: float = 0.0   # k_sc of minimize_flex.py, the restraint of the moving side-chain atoms to their start
 
 
 @dataclass

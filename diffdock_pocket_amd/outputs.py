@@ -281,18 +281,40 @@ def write_minimized_csv(path: str, minimized, order=None) -> str:
     """minimized.csv of one complex: one row per pose in RANKED order (minimize.MinimizeResult of the ranked poses).  rank counts from
     1, sample is the pose's index before ranking (order [N]; None: rank - 1); total_* are scoring.PoseScores.total of the pose before and
     after (comparable with scores.csv), energy_* the minimised E = inter + intra + restraint term of minimize.py, rmsd_moved in
-    angstrom, accepted_steps the accepted trials of the line search."""
+    angstrom, accepted_steps the accepted trials of the line search.  A minimize_flex.FlexMinimizeResult (energies [N, 6]): the same
+    columns, energy_* the joint E of minimize_flex.py, restraint_after the ligand's restraint term."""
     import csv
     r = minimized.cpu()
+    e_col, rest_col = (5, 3) if r.energy_after.shape[1] == 6 else (3, 2)
     sample = list(range(r.lig_pos.shape[0])) if order is None else [int(v) for v in _np(order).reshape(-1)]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(MINIMIZED_COLUMNS)
         for k in range(r.lig_pos.shape[0]):
             w.writerow([k + 1, sample[k], f"{float(r.scores_before.total[k]):.6g}", f"{float(r.scores_after.total[k]):.6g}",
-                        f"{float(r.energy_before[k, 3]):.6g}", f"{float(r.energy_after[k, 3]):.6g}", f"{float(r.energy_after[k, 0]):.6g}",
-                        f"{float(r.energy_after[k, 1]):.6g}", f"{float(r.energy_after[k, 2]):.6g}", f"{float(r.rmsd_moved[k]):.4f}",
+                        f"{float(r.energy_before[k, e_col]):.6g}", f"{float(r.energy_after[k, e_col]):.6g}", f"{float(r.energy_after[k, 0]):.6g}",
+                        f"{float(r.energy_after[k, 1]):.6g}", f"{float(r.energy_after[k, rest_col]):.6g}", f"{float(r.rmsd_moved[k]):.4f}",
                         int(r.accepted[k])])
+    return path
+
+
+MINIMIZED_SIDECHAINS_COLUMNS = ["rank", "sample", "sc_before", "sc_after", "sidechain_restraint_after", "sidechain_rmsd_moved"]
+
+
+def write_minimized_sidechains_csv(path: str, minimized, order=None) -> str:
+    """minimized_sidechains.csv of one complex whose side chains were minimised with the ligand (minimize_flex.FlexMinimizeResult of
+    the ranked poses): one row per pose in RANKED order, rank and sample as minimized.csv; sc_* the side chains' own pair energy sc(y)
+    of minimize_flex.py before and after, sidechain_restraint_after their restraint term, sidechain_rmsd_moved the RMSD over the
+    moving atoms in angstrom."""
+    import csv
+    r = minimized.cpu()
+    sample = list(range(r.lig_pos.shape[0])) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(MINIMIZED_SIDECHAINS_COLUMNS)
+        for k in range(r.lig_pos.shape[0]):
+            w.writerow([k + 1, sample[k], f"{float(r.energy_before[k, 2]):.6g}", f"{float(r.energy_after[k, 2]):.6g}",
+                        f"{float(r.energy_after[k, 4]):.6g}", f"{float(r.sidechain_rmsd_moved[k]):.4f}"])
     return path
 
 
@@ -335,7 +357,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     pockets (pockets.find_pockets of the protein, when the centre came from there): also pockets.csv.
     scores (scoring.PoseScores of the ranked poses; refined_scores: of the poses after clash relief): also scores.csv.
     minimized (minimize.MinimizeResult of the ranked poses): also rank{k}_minimized.sdf, the pose after the minimisation in the physics
-    score, and minimized.csv."""
+    score, and minimized.csv; a minimize_flex.FlexMinimizeResult: also rank{k}_minimized_protein.pdb, the receptor with the side chains
+    the pose was minimised with (write_receptor), and minimized_sidechains.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -386,4 +409,10 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
         for k in range(minimized.lig_pos.shape[0]):
             write_sdf(put(os.path.join(write_dir, f"rank{k + 1}_minimized.sdf")), mol, minimized.lig_pos[k], name, oc)
         write_minimized_csv(put(os.path.join(write_dir, "minimized.csv")), minimized, order)
+        if hasattr(minimized, "atom_pos"):
+            mv = moving_atoms(graph).tolist()
+            for k in range(minimized.atom_pos.shape[0]):
+                write_receptor(put(os.path.join(write_dir, f"rank{k + 1}_minimized_protein.pdb")), pdb_text, graph,
+                               [_np(minimized.atom_pos[k])[mv]], remove_hs)
+            write_minimized_sidechains_csv(put(os.path.join(write_dir, "minimized_sidechains.csv")), minimized, order)
     return written

@@ -17,7 +17,8 @@ RefineConfig's.  The pose update re-aligns the conformer after the torsions, so 
 applied: the direction is a heuristic and the accept rule is what guarantees that the energy never rises.
 
 What it does not do: no attraction or electrostatic term (it can only push atoms apart), no side-chain or receptor motion (the
-receptor is static during the refinement), no hydrogens.
+receptor is static during the refinement; minimize_flex.py moves the flexible side chains with the ligand, in the physics score), no
+hydrogens.
 
 Device tensors go through descent.descend_hip with ddp_refine_energy (csrc/ddp_refine.hip) as the evaluation; CPU tensors through
 descent.descend_torch with the PyTorch fp64 energy below."""

@@ -930,6 +930,81 @@ typedef struct {
 } ddp_minimize_args_t;
 int ddp_pose_minimize(const ddp_minimize_args_t* args, void* stream);
 
+/* ---- the same line search with the flexible side chains of the receptor in the state (csrc/ddp_minimize_flex.hip; host side
+ * diffdock_pocket_amd/minimize_flex.py, which states the whole definition).  Per pose: the ligand x as above and the receptor y =
+ * rec + s rec_stride, [m][3] fp32, per sample and in/out (rec_stride >= 3 m; rec_stride = 0 with m > 0 is DDP_EINVAL).  The moving
+ * atoms are mov [n_mov] int32, sorted and unique; every other receptor atom is only read.  Bond j of the n_sc side-chain bonds turns
+ * the atoms sc_sub[sc_map[2 j] .. sc_map[2 j + 1]) (entries of mov, none twice in one bond; sc_sub has n_sub entries) about
+ * y_u - y_v through y_v, (u, v) = sc_edge_idx[j].  With start (x0, y0) = (anchor[s], rec_anchor + s rec_stride), fp64 on the fp32 inputs:
+ *   E(x, y) = inter(x, y) + intra(x) + sc(y) + restraint mean_i |x_i - x0_i|^2 + restraint_sc mean_{a in mov} |y_a - y0_a|^2
+ * inter and intra as ddp_pose_minimize, against the receptor with the moving atoms where they currently are.  sc = the same weighted
+ * sum of the four pair terms over the receptor pairs of sc_pairs, uint8 [n_mov][m]: row r lists the partners b of atom mov[r]; a pair
+ * of two moving atoms appears in both rows and counts half from each end.  Untyped atoms (negative radius) take part in no pair.
+ * Gradients: of x as ddp_pose_minimize; of y_a, a in mov: d inter/dy_a + d sc/dy_a + (2 restraint_sc / n_mov)(y_a - y0_a).
+ * One 256-thread workgroup per pose runs `iterations` iterations.  The direction of the ligand is ddp_refine_direction's; bond j gets
+ * -sum g_i . a_i / sum |a_i|^2 over its subcomponent without u and v, a_i = u^ x (y_i - y_v), u^ = (y_u - y_v) / |y_u - y_v| (fp64; a
+ * zero denominator gives 0).  Both are multiplied by step[s] and rounded to fp32.  The trial: the pose map of ddp_pose_update on the
+ * ligand, the arithmetic of ddp_sidechain_update (bonds in list order, fp32, no re-alignment) on the LDS copy of the moving atoms.  One
+ * evaluation = score_evaluate for the ligand side, the receptor tile patched with the current or trial moving atoms as it is loaded
+ * (the trial never goes through global memory), then a second pass in which a wave owns the moving atoms w, w + 4, ...: its lanes
+ * stride over the ligand atoms in LDS (d inter/dy_a by gather: no scatter, no atomics), then over the receptor tiles for the partners
+ * of sc_pairs.  Every sum has a fixed order.  The accept rule is ddp_pose_minimize's on E; x and y are taken or kept together.
+ * In/out state: pos, rec (moving atoms only), step, accepted.  Outputs: energy_in / energy_out [n_samples][6] = inter, intra, sc,
+ * ligand restraint term, side-chain restraint term, E; history as ddp_pose_minimize; grad (or NULL) [n_samples][n][3] and grad_mov (or
+ * NULL) [n_samples][n_mov][3] = the gradients at exit.
+ * The invariants of ddp_pose_minimize hold: two launches give the same bits; row s of a batch equals the one-sample launch; a + b
+ * iterations equal a then b on the state left in memory; iterations = 0 writes only outputs; pos[s] and the moving atoms of rec[s] are
+ * written once at exit and only if sample s accepted a trial; a NaN in x or in a moving atom makes that sample never accept and
+ * touches no other sample.  With n_mov = n_sc = 0 poses, step, accepted, inter, intra and E are the bits of ddp_pose_minimize.  No
+ * data-dependent control flow around a barrier; an entry of mov, sc_edge_idx or sc_sub outside [0, m) (or an entry of sc_sub that is
+ * not in mov, or a range of sc_map outside [0, n_sub]) is skipped without a read: such an atom takes part in nothing and never moves.
+ * The host validates the tables before the upload.
+ * Limits: n and n_tor as ddp_pose_minimize, n_mov <= DDP_MINIMIZE_FLEX_MAX_MOVING, n_sc <= DDP_MINIMIZE_FLEX_MAX_BONDS, and the LDS
+ * plan, 18496 bytes + 89 n + 81 n_mov + 4 n_sc (the fixed part of ddp_pose_minimize and the second pass's partial sums; per ligand
+ * atom as ddp_pose_minimize; per moving atom two coordinate sets, two fp64 gradients, radius, index and flag byte; a step per bond),
+ * stays inside the 64 KiB of a plain launch: 89 n + 81 n_mov + 4 n_sc <= DDP_MINIMIZE_FLEX_MAX_STATE_BYTES.  Above any of them:
+ * DDP_ELIMIT without a launch.  DDP_EINVAL without a launch: what ddp_pose_minimize rejects, rec_stride < 3 m or = 0 with m > 0, n_mov,
+ * n_sc or n_sub < 0, restraint_sc < 0 (or NaN), a NULL mov, sc_pairs or rec_anchor with n_mov > 0, a NULL sc_edge_idx or sc_map with
+ * n_sc > 0, a NULL sc_sub with n_sub > 0. */
+#define DDP_MINIMIZE_FLEX_MAX_MOVING 256
+#define DDP_MINIMIZE_FLEX_MAX_BONDS 256
+#define DDP_MINIMIZE_FLEX_MAX_STATE_BYTES 47040
+typedef struct {
+  int32_t n_samples, n, m, rec_stride, n_tor, iterations;
+  float* pos;                   /* [n_samples][n][3], in/out */
+  const float* anchor;          /* [n_samples][n][3] */
+  const float* lig_radii;       /* [n] */
+  const uint8_t* lig_flags;     /* [n] */
+  float* rec;                   /* sample s: rec + s rec_stride, [m][3]; in/out, the moving atoms only */
+  const float* rec_radii;       /* [m] */
+  const uint8_t* rec_flags;     /* [m] */
+  const uint8_t* self_pairs;
+  const int32_t* bonds;         /* [n_tor][2] */
+  const uint8_t* mask_rotate;   /* [n_tor][n] */
+  double cutoff;
+  double gauss_offset, gauss_width;
+  double hydrophobic_good, hydrophobic_bad;
+  double hbond_good, hbond_bad;
+  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  double restraint, grow, shrink, step_max;
+  double* step;                 /* [n_samples], in/out */
+  int32_t* accepted;            /* [n_samples], in/out */
+  double* energy_in;            /* [n_samples][6] */
+  double* energy_out;           /* [n_samples][6] */
+  double* history;              /* [iterations + 1][n_samples] or NULL */
+  double* grad;                 /* [n_samples][n][3] or NULL */
+  const float* rec_anchor;      /* sample s: rec_anchor + s rec_stride, [m][3]; the moving atoms are read */
+  int32_t n_mov, n_sc, n_sub, reserved;
+  const int32_t* mov;           /* [n_mov], sorted, unique */
+  const int32_t* sc_edge_idx;   /* [n_sc][2] */
+  const int32_t* sc_sub;        /* [n_sub] */
+  const int32_t* sc_map;        /* [n_sc][2] */
+  const uint8_t* sc_pairs;      /* [n_mov][m] */
+  double restraint_sc;
+  double* grad_mov;             /* [n_samples][n_mov][3] or NULL */
+} ddp_minimize_flex_args_t;
+int ddp_pose_minimize_flex(const ddp_minimize_flex_args_t* args, void* stream);
+
 /* ---- geometric pocket finder: LIGSITE-style buriedness on a grid (csrc/ddp_pockets.hip; host side diffdock_pocket_amd/pockets.py, which
  * states the whole definition).  This project's own method, no learned predictor.  Grid point (i, j, k), 0 <= i < nx ..., has the flat
  * index g = (i ny + j) nz + k and sits at lo + (i, j, k) spacing; everything outside the grid is free space.  nx ny nz < 2^31.
