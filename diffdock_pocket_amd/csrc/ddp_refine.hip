@@ -15,92 +15,23 @@
 
 #include "ddp_hip.h"
 #include "ddp_internal.h"
+#include "ddp_clash_energy.h"
 #include "ddp_pose_descent.h"
 
-#define DDP_REFINE_THREADS DDP_DESCENT_THREADS
-#define DDP_REFINE_WAVES DDP_DESCENT_WAVES
-
-// max(0, t - d)^2 of one pair and its gradient with respect to the first atom, added to e and (gx, gy, gz).  The square root is
-// taken only where d^2 < t^2 can hold; the comparison is written so that a NaN distance goes through and poisons the sums (a NaN
-// energy is never accepted).  d = 0: the energy term counts, the gradient term is zero.
-__device__ __forceinline__ void pair_term(double dx, double dy, double dz, double t, double& e, double& gx, double& gy, double& gz) {
-  const double d2 = dx * dx + dy * dy + dz * dz;
-  if (d2 >= t * t) return;
-  const double d = sqrt(d2);
-  const double p = t - d;
-  if (p <= 0.0) return;
-  e += p * p;
-  if (d == 0.0) return;
-  const double k = -2.0 * p / d;
-  gx += k * dx; gy += k * dy; gz += k * dz;
-}
-
-// ---- energy[s] = [E_cross, E_self, E_rest, total], grad[s][i] = dE/dx_i.  LDS: the sample's ligand coordinates and radii (fp32, as
-// ddp_pose_contacts stages them), one fp64 gradient accumulator per ligand atom, and a tile of DDP_REFINE_TILE receptor atoms
-// (x, y, z, radius).  The receptor is streamed through that tile, all 256 threads loading one tile with coalesced reads: a wave that
-// read the receptor from global memory inside its pair loop waited one L2 round trip per 64 pairs (measured on 40 poses of 3dpf:
-// 180 us per iteration of the refinement against 125 us with the tile).  Wave w owns the ligand atoms i = w, w + 4, ...: for every tile its lanes stride over the
-// tile's atoms, the butterfly gives the tile's contribution to atom i, and lane 0 adds it to the atom's accumulator (tiles in
-// increasing order: a fixed order).  Then the lanes stride over the ligand atoms j with self_pairs[min(i, j)][max(i, j)] (every self
-// pair is met from both ends and counts half each time: exact) and lane 0 adds the restraint term of atom i.  Per-wave energy
-// partials are summed in that fixed order and over the waves in wave order.
-#define DDP_REFINE_TILE 1024
+// ---- energy[s] = [E_cross, E_self, E_rest, total], grad[s][i] = dE/dx_i: the pass of ddp_clash_energy.h (shared with the guidance term
+// of ddp_guidance.hip).  LDS: the sample's ligand coordinates and radii (fp32), one fp64 gradient accumulator per ligand atom, and a
+// tile of DDP_REFINE_TILE receptor atoms.  Per-wave energy partials are summed over the waves in wave order.
 __global__ __launch_bounds__(DDP_REFINE_THREADS) void ddp_refine_energy_kernel(const ddp_refine_args_t A) {
   extern __shared__ float4 tile[];                        // [DDP_REFINE_TILE] (first: 16-byte aligned whatever n is)
-  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m;
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n;
   double* gacc = (double*)(tile + DDP_REFINE_TILE);       // [n][3]
   float* x = (float*)(gacc + 3 * n);                      // [n][3]
   float* rad = x + 3 * n;                                 // [n]
   __shared__ double we[DDP_REFINE_WAVES][3];
-  const float* __restrict__ ls = A.pos + (size_t)s * n * 3;
-  const float* __restrict__ as = A.anchor + (size_t)s * n * 3;
-  const float* __restrict__ rs = A.rec + (size_t)s * A.rec_stride;
-  for (int i = tid; i < 3 * n; i += DDP_REFINE_THREADS) { x[i] = ls[i]; gacc[i] = 0.0; }
-  for (int i = tid; i < n; i += DDP_REFINE_THREADS) rad[i] = A.lig_radii[i];
-  const double two_ov = 2.0 * A.overlap;
-  const double krest = 2.0 * A.restraint / (double)n;
-  double ec_w = 0.0, es_w = 0.0, er_w = 0.0;     // this wave's atoms, in a fixed order (all lanes hold the same values)
-  for (int j0 = 0; j0 < m; j0 += DDP_REFINE_TILE) {
-    const int mt = min(DDP_REFINE_TILE, m - j0);
-    __syncthreads();                             // the previous tile has been used (first pass: x, rad, gacc are visible)
-    for (int j = tid; j < mt; j += DDP_REFINE_THREADS)
-      tile[j] = make_float4(rs[3 * (j0 + j)], rs[3 * (j0 + j) + 1], rs[3 * (j0 + j) + 2], A.rec_radii[j0 + j]);
-    __syncthreads();
-    for (int i = wave; i < n; i += DDP_REFINE_WAVES) {
-      const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2], ri = rad[i];
-      double ec = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
-      for (int j = lane; j < mt; j += 64) {
-        const float4 r = tile[j];
-        if (r.w < 0.f) continue;                 // a receptor hydrogen
-        const double t = ri + (double)r.w - two_ov;
-        if (t <= 0.0) continue;
-        pair_term(xi - (double)r.x, yi - (double)r.y, zi - (double)r.z, t, ec, gx, gy, gz);
-      }
-      ec = wave_sum(ec); gx = wave_sum(gx); gy = wave_sum(gy); gz = wave_sum(gz);
-      ec_w += ec;
-      if (lane == 0) { gacc[3 * i] += gx; gacc[3 * i + 1] += gy; gacc[3 * i + 2] += gz; }   // (atom i is this wave's alone)
-    }
-  }
-  __syncthreads();                               // m = 0: x and rad are visible
-  for (int i = wave; i < n; i += DDP_REFINE_WAVES) {
-    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2], ri = rad[i];
-    double es = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
-    if (A.self_pairs) {
-      for (int j = lane; j < n; j += 64) {
-        if (j == i || !A.self_pairs[(size_t)min(i, j) * n + max(i, j)]) continue;
-        const double t = ri + (double)rad[j] - two_ov;
-        if (t <= 0.0) continue;
-        pair_term(xi - (double)x[3 * j], yi - (double)x[3 * j + 1], zi - (double)x[3 * j + 2], t, es, gx, gy, gz);
-      }
-      es = wave_sum(es); gx = wave_sum(gx); gy = wave_sum(gy); gz = wave_sum(gz);
-    }
-    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
-    es_w += 0.5 * es; er_w += ax * ax + ay * ay + az * az;
-    if (lane == 0 && A.grad) {
-      double* g = A.grad + ((size_t)s * n + i) * 3;
-      g[0] = gacc[3 * i] + gx + krest * ax; g[1] = gacc[3 * i + 1] + gy + krest * ay; g[2] = gacc[3 * i + 2] + gz + krest * az;
-    }
-  }
+  double ec_w, es_w, er_w;
+  clash_energy_gradient(A.pos + (size_t)s * n * 3, A.lig_radii, n, A.rec + (size_t)s * A.rec_stride, A.rec_radii, A.m, A.self_pairs,
+                        A.anchor + (size_t)s * n * 3, 2.0 * A.overlap, 2.0 * A.restraint / (double)n, tile, gacc, x, rad,
+                        A.grad ? A.grad + (size_t)s * n * 3 : nullptr, ec_w, es_w, er_w);
   if (lane == 0) { we[wave][0] = ec_w; we[wave][1] = es_w; we[wave][2] = er_w; }
   __syncthreads();
   if (tid == 0) {

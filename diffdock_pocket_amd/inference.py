@@ -508,6 +508,13 @@ def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------- command line
+def _guidance_fields(a) -> Dict:
+    """The --clash_guidance* flags as SamplerConfig fields."""
+    return dict(clash_guidance_weight=a.clash_guidance, clash_guidance_t_max=a.clash_guidance_t_max,
+                clash_guidance_max_tr=a.clash_guidance_max_tr, clash_guidance_max_rot=a.clash_guidance_max_rot,
+                clash_guidance_max_tor=a.clash_guidance_max_tor)
+
+
 def _parser():
     """Reference inference.py:49-103: the same flag names and defaults for what this package implements; --esm_embeddings,
     --allow_zero_esm, --device and --seed are this package's."""
@@ -543,6 +550,13 @@ def _parser():
     p.add_argument("--svgd_only", action="store_true", default=False, help="the SVGD term replaces the SDE / ODE update")
     p.add_argument("--svgd_rot_rel_weight", type=float, default=1.0)
     p.add_argument("--svgd_tor_rel_weight", type=float, default=1.0)
+    p.add_argument("--clash_guidance", type=float, default=0.0, metavar="W",
+                   help="> 0: nudge every denoising step down the gradient of the steric-clash energy with this per-step weight "
+                        "(guidance.py; untuned, not validated on real checkpoints; default: off)")
+    p.add_argument("--clash_guidance_t_max", type=float, default=1.0, help="guide only the steps with diffusion time t <= this")
+    p.add_argument("--clash_guidance_max_tr", type=float, default=1.0, help="cap of the guidance translation per step (Angstrom)")
+    p.add_argument("--clash_guidance_max_rot", type=float, default=0.5, help="cap of the guidance rotation per step (rad)")
+    p.add_argument("--clash_guidance_max_tor", type=float, default=0.5, help="cap of the guidance torsion step per bond (rad)")
     p.add_argument("--cluster_rmsd", type=float, default=None,
                    help="group the ranked poses into binding modes at this symmetry-corrected RMSD cutoff and write modes.csv (default: off)")
     p.add_argument("--resolve_clashes", action="store_true", default=False,
@@ -642,13 +656,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                                    "pocket_buffer", "pocket_cutoff") if hasattr(margs, k)}
     if flexible and getattr(margs, "flexdist", None) is not None:
         graph_kwargs["flexdist"] = float(margs.flexdist)
+    try:
+        from .guidance import check_config
+        check_config(*_guidance_fields(a).values())
+    except ValueError as e:
+        ap.error(str(e).replace("clash_guidance_weight", "--clash_guidance").replace("clash_guidance_", "--clash_guidance_"))
     cfg = SamplerConfig(inference_steps=a.inference_steps, sigma=sigma,
                         temp_sampling=[a.temp_sampling_tr, a.temp_sampling_rot, a.temp_sampling_tor, a.temp_sampling_sc_tor],
                         temp_psi=[a.temp_psi_tr, a.temp_psi_rot, a.temp_psi_tor, a.temp_psi_sc_tor], temp_sigma_data=a.temp_sigma_data,
                         no_final_step_noise=a.no_final_step_noise, no_random=a.no_random, ode=a.ode, flexible_sidechains=flexible,
                         no_torsion=bool(getattr(margs, "no_torsion", False)), record_trajectory=a.save_visualisation,
                         svgd_weight=a.svgd_weight, svgd_repulsive_weight=a.svgd_repulsive_weight, svgd_only=a.svgd_only,
-                        svgd_rot_rel_weight=a.svgd_rot_rel_weight, svgd_tor_rel_weight=a.svgd_tor_rel_weight)
+                        svgd_rot_rel_weight=a.svgd_rot_rel_weight, svgd_tor_rel_weight=a.svgd_tor_rel_weight, **_guidance_fields(a))
     if a.svgd_weight > 0 and (flexible or a.samples_per_complex < 3):
         ap.error("--svgd_weight > 0 needs a rigid receptor (--rigid or a model without flexible side chains) and "
                  "--samples_per_complex >= 3")

@@ -779,6 +779,13 @@ def refine_accept(a: L.RefineArgs):
     L.check(L.load().ddp_refine_accept(C.byref(a), stream()), "ddp_refine_accept")
 
 
+# ------------------------------------------------------------------------------------------------ clash guidance (csrc/ddp_guidance.hip)
+def clash_guidance(a: L.GuidanceArgs, st=None):
+    """ddp_clash_guidance: the guidance increments of a.pos added to a.upd, on stream `st` (None: the current stream of the current
+    device).  guidance.GuidanceWorkspace builds the struct and checks the tensors."""
+    L.check(L.load().ddp_clash_guidance(C.byref(a), stream() if st is None else st), "ddp_clash_guidance")
+
+
 # ------------------------------------------------------------------------------------------------ physics score (csrc/ddp_score.hip)
 def pose_score(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, tor_divisor=1.0, self_pairs=None, energy=None, grad=None,
                with_grad=False):

@@ -199,6 +199,20 @@ class SamplerConfig:
     svgd_only: bool = False
     svgd_rot_rel_weight: float = 1.0
     svgd_tor_rel_weight: float = 1.0
+    # steric-clash guidance (guidance.py, which states the definition; this project's own term): > 0 adds, at every step with
+    # t <= clash_guidance_t_max, the capped descent direction of the clash energy times this weight to the tr / rot / tor updates.  A
+    # per-step constant, not multiplied by g^2 dt: more steps mean more total guidance.  The schedule (t_max) and the caps (Angstrom,
+    # radians, radians) are untuned choices.  0: nothing is allocated, launched or uploaded.
+    clash_guidance_weight: float = 0.0
+    clash_guidance_t_max: float = 1.0
+    clash_guidance_max_tr: float = 1.0
+    clash_guidance_max_rot: float = 0.5
+    clash_guidance_max_tor: float = 0.5
+
+    def __post_init__(self):
+        from .guidance import check_config
+        check_config(self.clash_guidance_weight, self.clash_guidance_t_max, self.clash_guidance_max_tr, self.clash_guidance_max_rot,
+                     self.clash_guidance_max_tor)
 
 
 class Sampler:
@@ -248,6 +262,25 @@ class Sampler:
         self.svgd = cfg.svgd_weight > 0
         if self.svgd:
             self._init_svgd(g)
+        self.guidance = cfg.clash_guidance_weight > 0
+        if self.guidance:
+            self._init_guidance(g)
+
+    # -- steric-clash guidance (SamplerConfig.clash_guidance_weight > 0; guidance.py) ---------------------------------
+    def _init_guidance(self, g):
+        """The host tables (once; a ligand above the kernel's limits raises here) and, on a HIP device, the workspace of the one
+        ddp_clash_guidance launch.  With no_torsion the direction is rigid only."""
+        from . import guidance
+        cfg = self.cfg
+        self.guid_tables = guidance.build_tables(g, torsions=not cfg.no_torsion)
+        if self.on_hip:
+            self.guid_ws = guidance.GuidanceWorkspace(self.guid_tables, self.device, cfg.clash_guidance_max_tr, cfg.clash_guidance_max_rot,
+                                                      cfg.clash_guidance_max_tor)
+
+    def _guidance_weight(self, t: float) -> float:
+        """w_t of guidance.py: the weight while t <= clash_guidance_t_max, else 0."""
+        from .guidance import step_weight
+        return step_weight(self.cfg.clash_guidance_weight, t, self.cfg.clash_guidance_t_max)
 
     # -- SVGD particle interaction (SamplerConfig.svgd_weight > 0; svgd.py) ------------------------------------------
     def _init_svgd(self, g):
@@ -420,6 +453,8 @@ class Sampler:
             host[1] = t_idx + 1            # the trajectory slot of ddp_traj_record (exact as a float)
         if self.svgd:
             host[2:5] = torch.tensor(self._svgd_gdt(t_idx, schedule), dtype=torch.float64).float()     # read by ddp_svgd_rows
+        if self.guidance:
+            host[5] = self._guidance_weight(t)                                                         # read by ddp_clash_guidance
         host[8:16] = torch.tensor(coef, dtype=torch.float64).float()
         o = self._off
 
@@ -478,6 +513,9 @@ class Sampler:
         if self.svgd:      # on the poses the scores were computed for, into the updates just written
             self.svgd_ws.launch(self.lig_pos, (keep[0], keep[1], keep[2] if use_tor else None),
                                 (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[2:5])
+        if self.guidance:  # after SVGD (svgd_only does not erase it), against the receptor before this step's side-chain update
+            self.guid_ws.launch(self.lig_pos, self.atom_pos if self.has_flex else None,
+                                (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[5:6])
         if self.has_flex:
             L.check(lib.ddp_sidechain_update(self.atom_pos.data_ptr(), self.n, self.n_a, self.upd["sc"].data_ptr(), self.S,
                                              self.sc_edge_i32.data_ptr(), self.sc_sub_i32.data_ptr(), self.sc_map_i32.data_ptr(),
@@ -669,6 +707,12 @@ class Sampler:
         b["atom"].pos = self.atom_pos.reshape(-1, 3)
         set_time(b, t, t, t, t, device=dev)
         tr_score, rot_score, tor_score, sc_score = self._call_model(self.model, b)
+        guid = None
+        if self.guidance:  # on the poses the scores were computed for, against the receptor before this step's side-chain update
+            from . import guidance
+            guid = guidance.increments_torch(self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else self.guid_tables.rec,
+                                             self.guid_tables, self._guidance_weight(t), cfg.clash_guidance_max_tr,
+                                             cfg.clash_guidance_max_rot, cfg.clash_guidance_max_tor)
 
         def perturb(score, g, sigma, lo, hi, k, zz):
             if cfg.ode:
@@ -705,6 +749,10 @@ class Sampler:
             rot_p = cfg.svgd_weight * tot[1] + (0 if cfg.svgd_only else rot_p)
             if tor_p is not None:
                 tor_p = cfg.svgd_weight * tot[2] + (0 if cfg.svgd_only else tor_p)
+        if guid is not None:
+            tr_p, rot_p = tr_p + guid[0].to(dev), rot_p + guid[1].to(dev)
+            if tor_p is not None:
+                tor_p = tor_p + guid[2].to(dev)
         if self.lig_pos.is_cuda:   # one HIP launch; the PyTorch form below is the same arithmetic (CPU tests)
             self.lig_pos = modify_conformer_hip(self.lig_pos, tr_p, rot_p, tor_p, self.bonds_i32, self.mask_u8)
         else:

@@ -1030,6 +1030,47 @@ int ddp_pocket_buriedness(const uint8_t* occ, int nx, int ny, int nz, double spa
                           int32_t* mask, void* stream);
 int ddp_pocket_label(const int32_t* mask, int nx, int ny, int nz, int32_t* labels, void* stream);
 
+/* ---- steric-clash guidance term of the reverse-diffusion step (csrc/ddp_guidance.hip; host side diffdock_pocket_amd/guidance.py and
+ * sampler.py).  This project's own term, not part of the reference.  At a denoising step the updates of sample s are nudged down the
+ * gradient of the clash energy of ddp_refine_energy, along the sampler's own degrees of freedom.  pos [n_samples][n][3]: the fp32 poses
+ * x the scores were computed for; lig_radii, rec, m, rec_stride, rec_radii, self_pairs, overlap as ddp_refine_energy (rec_stride 0:
+ * one receptor for all samples; a negative receptor radius = a hydrogen, ignored); bonds [n_tor][2], mask_rotate [n_tor][n] as
+ * ddp_refine_direction.  With g = dE/dx the fp64 gradient of E = E_cross + E_self (restraint 0):
+ *   1. weight     w = *weight, ONE fp32 value in DEVICE memory (the sampler's step parameter block: w_t = clash_guidance_weight while
+ *                 t <= clash_guidance_t_max, else 0).  A per-step constant, NOT multiplied by g^2 dt: more steps mean more total
+ *                 guidance.  Unless w > 0 the workgroups return before any store: upd, energy and grad are left untouched.
+ *   2. direction  (d_tr, d_rot, d_tor) = what ddp_refine_direction writes for step[s] = w: the inertia-scaled descent direction times
+ *                 w, rounded to fp32.
+ *   3. cap factor f_s = min(1, max_tr / |d_tr|_2, max_rot / |d_rot|_2, max_tor / max_b |d_tor[b]|), in fp64 from those fp32 values; a
+ *                 zero norm contributes no constraint.  max_tr in Angstrom, max_rot and max_tor in radians; +infinity: no cap.
+ *   4. update     upd_X[s] += (float)(f_s * (double)d_X) for X in tr, rot, tor: a read-modify-write, every element by one thread, no
+ *                 atomics.  upd = the outputs of ddp_sde_update (after ddp_svgd_rows, where that runs), the inputs of ddp_pose_update.
+ * energy [n_samples][2] = (E_cross, E_self) and grad [n_samples][n][3] = g are optional outputs (NULL: not written), bit for bit what
+ * ddp_refine_energy gives with restraint 0 and anchor = pos; with caps of +infinity and upd = 0 the increments are bit for bit
+ * ddp_refine_direction's.  One 256-thread workgroup per sample; LDS: the receptor tile, the fp64 gradient, the pose and radii (the
+ * plan of ddp_refine_energy) plus the torsion components and the reductions' scratch, 16.3 KiB + 40 n + 4 n_tor bytes.  Every sum in
+ * a fixed order: two launches give the same bits; a NaN pose poisons its own sample only.  n_samples = 0: no-op; m = 0: no cross
+ * term; n_tor = 0: rigid only (bonds, mask_rotate, upd[2] may be NULL).  n > DDP_EVAL_MAX_ATOMS or n_tor > DDP_GUIDANCE_MAX_TORSIONS:
+ * DDP_ELIMIT; a NULL pointer, a bad shape, a negative or NaN cap: DDP_EINVAL; nothing is launched. */
+#define DDP_GUIDANCE_MAX_TORSIONS 1024
+typedef struct {
+  int32_t n_samples, n, m, rec_stride, n_tor;
+  const float* pos;             /* [n_samples][n][3] */
+  const float* lig_radii;       /* [n] */
+  const float* rec;             /* [m][3], or [n_samples] blocks rec_stride floats apart */
+  const float* rec_radii;       /* [m] */
+  const uint8_t* self_pairs;    /* [n][n] or NULL */
+  const int32_t* bonds;         /* [n_tor][2] */
+  const uint8_t* mask_rotate;   /* [n_tor][n] */
+  double overlap;
+  const float* weight;          /* one value, device memory */
+  double max_tr, max_rot, max_tor;
+  float* upd[3];                /* [n_samples][3], [n_samples][3], [n_samples][n_tor] */
+  double* energy;               /* [n_samples][2] or NULL */
+  double* grad;                 /* [n_samples][n][3] or NULL */
+} ddp_clash_guidance_args_t;
+int ddp_clash_guidance(const ddp_clash_guidance_args_t* args, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
 /* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, the csrc headers, include/ddp_hip.h) the library was built from */
