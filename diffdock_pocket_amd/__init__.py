@@ -7,7 +7,7 @@ from .diffusion import SigmaRanges, get_t_schedule, get_timestep_embedding, sinu
 __all__ = ["HeteroBatch", "Store", "collate", "set_time", "SigmaRanges", "get_t_schedule", "get_timestep_embedding",
            "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize", "PoseRefiner",
            "RefineConfig", "RefineResult", "PoseScorer", "ScoreConfig", "PoseScores", "PoseMinimizer", "MinimizeConfig",
-           "MinimizeResult", "FlexPoseMinimizer", "FlexMinimizeResult"]
+           "MinimizeResult", "FlexPoseMinimizer", "FlexMinimizeResult", "InteractionProfiler", "ProfileConfig", "InteractionProfile"]
 
 
 def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ctypes binding
@@ -32,4 +32,7 @@ def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ct
     if name in ("FlexPoseMinimizer", "FlexMinimizeResult"):
         from . import minimize_flex
         return getattr(minimize_flex, name)
+    if name in ("InteractionProfiler", "ProfileConfig", "InteractionProfile"):
+        from . import interactions
+        return getattr(interactions, name)
     raise AttributeError(name)

@@ -24,7 +24,7 @@ DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS, DDP_MINIMIZE_FLEX_MAX
 DDP_PAIRWISE_MAX_SAMPLES, DDP_CLUSTER_MAX_SAMPLES = 32768, 1024
 EXPORTS = ["ddp_conv_messages", "ddp_conv_rows", "ddp_stage_a_gh", "ddp_stage_a_gh3", "ddp_segment_reduce", "ddp_edge_featurize", "ddp_edge_featurize_jobs", "ddp_torsion_sh", "ddp_stage_a", "ddp_stage_a_h2",
            "ddp_pose_update", "ddp_sidechain_update", "ddp_sde_update", "ddp_radius_count", "ddp_radius_fill", "ddp_knn", "ddp_group_by_key", "ddp_node_linear", "ddp_scan_jobs", "ddp_mark_jobs", "ddp_rowcopy_jobs", "ddp_select_jobs",
-           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_pose_score", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
+           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
 
 
 class Seg(C.Structure):
@@ -129,6 +129,15 @@ class ScoreArgs(C.Structure):
                 ("gauss_width", C.c_double), ("hydrophobic_good", C.c_double), ("hydrophobic_bad", C.c_double), ("hbond_good", C.c_double),
                 ("hbond_bad", C.c_double), ("w_gauss", C.c_double), ("w_repulsion", C.c_double), ("w_hydrophobic", C.c_double),
                 ("w_hbond", C.c_double), ("tor_divisor", C.c_double), ("energy", _P), ("grad", _P)]
+
+
+class ProfileArgs(C.Structure):
+    """ddp_profile_args_t of include/ddp_hip.h."""
+    _fields_ = [("n_samples", _I), ("n", _I), ("m", _I), ("rec_stride", _I), ("n_res", _I), ("reserved", _I), ("pos", _P), ("lig_radii", _P),
+                ("lig_flags", _P), ("rec", _P), ("rec_radii", _P), ("rec_flags", _P), ("res_ptr", _P), ("cutoff", C.c_double),
+                ("gauss_offset", C.c_double), ("gauss_width", C.c_double), ("hydrophobic_good", C.c_double), ("hydrophobic_bad", C.c_double),
+                ("hbond_good", C.c_double), ("hbond_bad", C.c_double), ("w_gauss", C.c_double), ("w_repulsion", C.c_double),
+                ("w_hydrophobic", C.c_double), ("w_hbond", C.c_double), ("contact_distance", C.c_double), ("profile", _P), ("bits", _P)]
 
 
 class MinimizeArgs(C.Structure):
@@ -324,6 +333,8 @@ def load():
     lib.ddp_clash_guidance.restype = C.c_int
     lib.ddp_pose_score.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
     lib.ddp_pose_score.restype = C.c_int
+    lib.ddp_pose_profile.argtypes = [C.POINTER(ProfileArgs), C.c_void_p]
+    lib.ddp_pose_profile.restype = C.c_int
     lib.ddp_pose_minimize.argtypes = [C.POINTER(MinimizeArgs), C.c_void_p]
     lib.ddp_pose_minimize.restype = C.c_int
     lib.ddp_pose_minimize_flex.argtypes = [C.POINTER(MinimizeFlexArgs), C.c_void_p]

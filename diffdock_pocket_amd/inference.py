@@ -34,6 +34,7 @@ from . import outputs as O
 from .diffusion import get_t_schedule
 from .evaluation import PoseClusters, PoseEvaluator, PoseMetrics  # noqa: F401
 from .pockets import Pocket, PocketConfig, find_pockets as _find_pockets  # noqa: F401
+from .interactions import InteractionProfile, InteractionProfiler, ProfileConfig, receptor_residues  # noqa: F401
 from .minimize import MinimizeConfig, MinimizeResult, PoseMinimizer  # noqa: F401
 from .minimize_flex import FlexMinimizeResult, FlexPoseMinimizer  # noqa: F401
 from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
@@ -63,6 +64,9 @@ class ComplexResult:
     minimized: Optional["MinimizeResult"] = None   # run_csv(minimize_poses=cfg): minimize.MinimizeResult of the ranked poses (host tensors);
     #                                                a flexible row with cfg.sidechains: minimize_flex.FlexMinimizeResult
     minimized_pos: Optional[torch.Tensor] = None   # run_csv(minimize_poses=cfg): [N, n_lig, 3] the ranked poses after the minimisation
+    interactions: Optional["InteractionProfile"] = None  # run_csv(interaction_profile=cfg): interactions.InteractionProfile of the ranked
+    #                                                      poses (host tensors)
+    interaction_reference: Optional["InteractionProfile"] = None  # interaction_profile with evaluate=True: the profile of the input pose
 
 
 def _none(v):
@@ -129,7 +133,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             save_visualisation: bool = False, cluster_rmsd: Optional[float] = None,
             resolve_clashes: Optional[RefineConfig] = None, find_pockets: Optional[PocketConfig] = None,
             pockets_top_k: int = 1, score_poses: Optional[ScoreConfig] = None, rank_by: str = "confidence",
-            minimize_poses: Optional[MinimizeConfig] = None) -> List[ComplexResult]:
+            minimize_poses: Optional[MinimizeConfig] = None, interaction_profile: Optional[ProfileConfig] = None) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -193,7 +197,17 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     FlexMinimizeResult, E in minimized.csv the joint E, and with out_dir also rank{k}_minimized_protein.pdb (the receptor with the
     minimised side chains) and minimized_sidechains.csv; rigid rows take the path above.  rank_by="minimized_score" (implies minimisation with the default MinimizeConfig) orders the poses by ascending
     `scores_after.total` through scoring.rank_order, and everything downstream follows that order, as with "score".  Without either
-    argument nothing is allocated, launched or written differently.  A failure skips the row like a failure of the evaluation."""
+    argument nothing is allocated, launched or written differently.  A failure skips the row like a failure of the evaluation.
+
+    interaction_profile=ProfileConfig(...): the gathered, ranked poses also get the per-residue interaction profile of
+    interactions.InteractionProfiler (the pair terms of the physics score - score_poses' constants, else the default ScoreConfig -
+    summed per residue, and three bits per residue: contact, hydrophobic, hbond): `interactions` in ranked order, with out_dir also
+    interactions.csv, interaction_summary.csv and interaction_similarity.csv (outputs.write_interaction*_csv).  Rigid rows run
+    against the row's full typed PDB with the PDB's residue labels, flexible rows against each sample's own atom nodes with the
+    graph's.  evaluate=True: `interaction_reference` is the profile of the input ligand pose through the same profiler, and
+    interaction_similarity.csv also says how similar every pose's bits are to it and how many of them the pose recovers.  It changes
+    nothing else; a failure skips the row like a failure of the evaluation.  None: nothing is computed, allocated, launched or
+    written."""
     if rank_by not in ("confidence", "score", "minimized_score"):
         raise ValueError(f"rank_by: 'confidence', 'score' or 'minimized_score', got {rank_by!r}")
     if rank_by == "score" and score_poses is None:
@@ -212,7 +226,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
             shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd, resolve_clashes,
-            find_pockets, pockets_top_k, score_poses, rank_by, minimize_poses)
+            find_pockets, pockets_top_k, score_poses, rank_by, minimize_poses, interaction_profile)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(*args)
@@ -230,7 +244,7 @@ def _all_ok(dist, ok: bool, device) -> bool:
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
              world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
              save_visualisation=False, cluster_rmsd=None, resolve_clashes=None, find_pockets=None, pockets_top_k=1, score_poses=None,
-             rank_by="confidence", minimize_poses=None) -> List[ComplexResult]:
+             rank_by="confidence", minimize_poses=None, interaction_profile=None) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if find_pockets is not None:
         rows = expand_pocket_rows(rows, root, device, find_pockets, pockets_top_k)
@@ -275,7 +289,8 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             smp.randomize()
             smp.run(schedule)
             lig = smp.lig_pos
-            if ((evaluate or resolve_clashes is not None or score_poses is not None or minimize_poses is not None) and flex) or (out_dir is not None and moved):
+            if ((evaluate or resolve_clashes is not None or score_poses is not None or minimize_poses is not None
+                 or interaction_profile is not None) and flex) or (out_dir is not None and moved):
                 apos = smp.atom_pos.clone()
             if save_visualisation:
                 ltraj = smp.lig_traj.clone()
@@ -387,6 +402,20 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             res.refine, res.refined_metrics = refined
             res.refined_pos = res.refine.lig_pos
             res.refined_scores = refined_scores
+        if interaction_profile is not None:
+            found = None
+            try:
+                found = _interactions_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order], score_poses,
+                                          interaction_profile, evaluate)
+            except Exception as e:      # noqa: BLE001
+                res.skipped = f"interaction profile: {type(e).__name__}: {e}"
+            if split and not _all_ok(dist, found is not None, device):
+                res.skipped = res.skipped or "skipped: the interaction profile failed on another rank"
+            if res.skipped is not None:
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = None
+                res.refined_pos = res.refine = res.refined_metrics = res.refined_scores = None
+                continue
+            res.interactions, res.interaction_reference = found
         if save_visualisation:
             res.lig_traj = ltraj[order].cpu()
             res.atom_traj = atraj[order].cpu() if atraj is not None else None
@@ -404,7 +433,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if not ok:
                 res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = res.clusters = None
                 res.refined_pos = res.refine = res.refined_metrics = res.scores = res.refined_scores = None
-                res.minimized = res.minimized_pos = None
+                res.minimized = res.minimized_pos = res.interactions = res.interaction_reference = None
                 res.files = []
     return out
 
@@ -446,7 +475,8 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
     return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
                            apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order,
                            refine=res.refine, pockets=res.pockets, pockets_docked=row.get("pockets_docked", 0), scores=res.scores,
-                           refined_scores=res.refined_scores, minimized=res.minimized)
+                           refined_scores=res.refined_scores, minimized=res.minimized, interactions=res.interactions,
+                           interaction_reference=res.interaction_reference)
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -481,6 +511,21 @@ def _scorer_row(row, root, g, device, flex, config) -> PoseScorer:
     with open(os.path.join(root, row["experimental_protein"])) as f:
         rec = typed_receptor(f.read(), g.original_center)
     return PoseScorer(g, device, receptor=rec, config=config)
+
+
+def _interactions_row(row, root, g, device, flex, lig, apos, score_config, config, evaluate):
+    """(InteractionProfile of the ranked poses of one row, InteractionProfile of the input pose or None), on the host (see run_csv).  The
+    receptor is the one _scorer_row takes, with its residues."""
+    if flex:
+        pf = InteractionProfiler(g, device, config=config, score_config=score_config)
+    else:
+        with open(os.path.join(root, row["experimental_protein"])) as f:
+            pdb_text = f.read()
+        pf = InteractionProfiler(g, device, receptor=(typed_receptor(pdb_text, g.original_center), receptor_residues(pdb_text)),
+                                 config=config, score_config=score_config)
+    out = pf.profile(lig, apos if flex else None).cpu()
+    ref = pf.profile(torch.as_tensor(g["ligand"].pos).float()[None].to(lig.device)).cpu() if evaluate else None
+    return out, ref
 
 
 def _minimize_row(row, root, g, device, flex, lig, apos, score_config, config) -> MinimizeResult:
@@ -583,6 +628,12 @@ def _parser():
                         "minimized_sidechains.csv are written too; rigid rows are minimised as without the flag (default: off)")
     p.add_argument("--minimize_sidechain_restraint", type=float, default=MinimizeConfig.sidechain_restraint,
                    help="with --minimize_sidechains: weight of the restraint of the moving side-chain atoms to their sampled positions")
+    p.add_argument("--interaction_profile", action="store_true", default=False,
+                   help="say which residues every pose touches and how: the pair terms of the physics score summed per residue, with "
+                        "contact / hydrophobic / hbond bits (not validated against PLIP or ProLIF); writes interactions.csv, "
+                        "interaction_summary.csv and interaction_similarity.csv (default: off)")
+    p.add_argument("--interaction_contact_distance", type=float, default=ProfileConfig.contact_distance,
+                   help="with --interaction_profile: a residue is in contact when its closest atom pair is nearer than this (angstrom)")
     p.add_argument("--find_pockets", action="store_true", default=False,
                    help="complexes without --pocket_center_* / pocket_center columns: find the pocket on the protein's geometry (this "
                         "package's grid buriedness finder, no learned predictor) and dock there; writes pockets.csv (default: off)")
@@ -645,6 +696,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--minimize_sidechain_restraint must not be negative")
     if a.pockets_top_k < 1 or not a.pocket_spacing > 0 or not 0 <= a.pocket_min_lines <= 7 or a.pocket_probe < 0:
         ap.error("--pockets_top_k must be at least 1, --pocket_spacing positive, --pocket_min_lines in 0..7, --pocket_probe not negative")
+    if not (a.interaction_contact_distance > 0 and np.isfinite(a.interaction_contact_distance)):
+        ap.error("--interaction_contact_distance must be positive and finite")
     if a.samples_per_complex < 1 or a.inference_steps < 1:
         ap.error("--samples_per_complex and --inference_steps must be positive")
     device = torch.device(a.device or ("cuda:0" if torch.cuda.is_available() else "cpu"))
@@ -706,7 +759,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       score_poses=ScoreConfig() if (a.score_poses or a.rank_by == "score") else None, rank_by=a.rank_by,
                       minimize_poses=MinimizeConfig(iterations=a.minimize_iterations, restraint=a.minimize_restraint,
                                                     sidechains=a.minimize_sidechains, sidechain_restraint=a.minimize_sidechain_restraint)
-                      if (a.minimize_poses or a.minimize_sidechains or a.rank_by == "minimized_score") else None)
+                      if (a.minimize_poses or a.minimize_sidechains or a.rank_by == "minimized_score") else None,
+                      interaction_profile=ProfileConfig(contact_distance=a.interaction_contact_distance) if a.interaction_profile else None)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

@@ -828,6 +828,47 @@ def pose_score(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, tor
     return energy, grad
 
 
+# ------------------------------------------------------------------------------------------------ interaction profile (csrc/ddp_profile.hip)
+def pose_profile(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, res_ptr, config, contact_distance=4.5, profile=None, bits=None):
+    """ddp_pose_profile: pos, lig_radii, lig_flags, rec ([m, 3] or [S, m, 3]), rec_radii, rec_flags and config as pose_score; res_ptr int32
+    [R + 1]: residue r owns the receptor atoms res_ptr[r] .. res_ptr[r + 1] - 1 (its values are not looked at here: the kernel clamps
+    them to [0, m]).  Returns (profile [S, R, 7] fp64 = gauss, repulsion, hydrophobic, hbond, energy, d_min, pairs; bits [S, R] uint8:
+    bit 0 contact, 1 hydrophobic, 2 hbond).  profile / bits: tensors to write into."""
+    dev = pos.device
+    _eval_arg(pos, torch.float32, dev, "pose_profile pos")
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise L.DdpError("pose_profile: pos [S, n, 3]")
+    S, n = pos.shape[0], pos.shape[1]
+    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
+        raise L.DdpError("pose_profile: rec [m, 3] or [S, m, 3]")
+    m = rec.shape[-2]
+    if res_ptr is None or res_ptr.dim() != 1 or res_ptr.shape[0] < 1:
+        raise L.DdpError("pose_profile: res_ptr [R + 1]")
+    R = res_ptr.shape[0] - 1
+    if profile is None:
+        profile = torch.empty(S, R, 7, dtype=torch.float64, device=dev)
+    if bits is None:
+        bits = torch.empty(S, R, dtype=torch.uint8, device=dev)
+    want = [(lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"), (rec, torch.float32, None, "rec"),
+            (rec_radii, torch.float32, (m,), "rec_radii"), (rec_flags, torch.uint8, (m,), "rec_flags"),
+            (res_ptr, torch.int32, (R + 1,), "res_ptr"), (profile, torch.float64, (S, R, 7), "profile"), (bits, torch.uint8, (S, R), "bits")]
+    for t, dt, shape, what in want:
+        _eval_arg(t, dt, dev, f"pose_profile {what}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise L.DdpError(f"pose_profile {what}: expected {shape}, got {tuple(t.shape)}")
+    c = config
+    a = L.ProfileArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, n_res=R, cutoff=float(c.cutoff),
+                      gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width), hydrophobic_good=float(c.hydrophobic_good),
+                      hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good), hbond_bad=float(c.hbond_bad),
+                      w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion), w_hydrophobic=float(c.w_hydrophobic),
+                      w_hbond=float(c.w_hbond), contact_distance=float(contact_distance))
+    for name, t in (("pos", pos), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_radii", rec_radii),
+                    ("rec_flags", rec_flags), ("res_ptr", res_ptr), ("profile", profile), ("bits", bits)):
+        setattr(a, name, _p(t) or None)
+    L.check(L.load().ddp_pose_profile(C.byref(a), stream()), "ddp_pose_profile")
+    return profile, bits
+
+
 # ------------------------------------------------------------------------------------------------ fused minimiser (csrc/ddp_minimize.hip)
 def pose_minimize(pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate, step, accepted,
                   energy_in, energy_out, iterations, restraint=0.0, grow=2.0, shrink=0.5, step_max=1024.0, history=None, grad=None):

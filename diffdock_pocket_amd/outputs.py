@@ -318,6 +318,72 @@ def write_minimized_sidechains_csv(path: str, minimized, order=None) -> str:
     return path
 
 
+# ---------------------------------------------------------------------------------------------- interaction profile
+INTERACTIONS_COLUMNS = ["rank", "sample", "residue", "gauss", "repulsion", "hydrophobic", "hbond", "energy", "d_min", "contact",
+                        "hydrophobic_bit", "hbond_bit"]
+INTERACTION_SUMMARY_COLUMNS = ["residue", "contact_freq", "hydrophobic_freq", "hbond_freq", "mean_energy"]
+INTERACTION_SIMILARITY_COLUMNS = ["rank", "sample", "tanimoto_to_rank1"]
+INTERACTION_REFERENCE_COLUMNS = ["tanimoto_to_reference", "recovery_of_reference"]
+
+
+def write_interactions_csv(path: str, interactions, order=None) -> str:
+    """interactions.csv of one complex (interactions.InteractionProfile of the ranked poses): one row per pose and residue that have at
+    least one atom pair inside the cutoff (pairs > 0), poses in RANKED order, residues in receptor order.  rank counts from 1, sample is
+    the pose's index before ranking (order [N]; None: rank - 1); gauss ... hbond are the unweighted sums over the residue's pairs,
+    energy the residue's share of the Vinardo-form `inter`, d_min the closest centre distance in angstrom, the last three the bits."""
+    import csv
+    p = interactions.cpu()
+    N = p.bits.shape[0]
+    sample = list(range(N)) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(INTERACTIONS_COLUMNS)
+        for k in range(N):
+            for r in torch.nonzero(p.pairs[k] > 0).flatten().tolist():
+                b = int(p.bits[k, r])
+                w.writerow([k + 1, sample[k], p.labels[r]] + [f"{float(v):.6g}" for v in p.terms[k, r]]
+                           + [f"{float(p.energy[k, r]):.6g}", f"{float(p.d_min[k, r]):.4f}", b & 1, (b >> 1) & 1, (b >> 2) & 1])
+    return path
+
+
+def write_interaction_summary_csv(path: str, interactions) -> str:
+    """interaction_summary.csv of one complex: one row per residue that any pose reaches (pairs > 0), in receptor order: the share of
+    the poses with each bit set and the mean of the residue's energy over the poses (a poisoned pose, NaN, is left out of the mean)."""
+    import csv
+    p = interactions.cpu()
+    freq = p.frequency()
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(INTERACTION_SUMMARY_COLUMNS)
+        for r in torch.nonzero((p.pairs > 0).any(0)).flatten().tolist():
+            w.writerow([p.labels[r]] + [f"{float(v):.4f}" for v in freq[r]] + [f"{float(torch.nanmean(p.energy[:, r])):.6g}"])
+    return path
+
+
+def write_interaction_similarity_csv(path: str, interactions, order=None, reference=None) -> str:
+    """interaction_similarity.csv of one complex: one row per pose in RANKED order with the Tanimoto similarity of its interaction bits
+    to those of the pose ranked first.  reference (the InteractionProfile of the known pose, one row): two more columns, the Tanimoto
+    similarity to the known pose's bits and the share of them that the pose recovers (empty where the known pose sets no bit)."""
+    import csv
+    p = interactions.cpu()
+    N = p.bits.shape[0]
+    sample = list(range(N)) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    first = p.tanimoto_to(p.bits[0]) if N else []
+    to_ref = rec = None
+    if reference is not None:
+        rb = reference.cpu().bits[0]
+        to_ref, rec = p.tanimoto_to(rb), p.recovery(rb)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(INTERACTION_SIMILARITY_COLUMNS + (INTERACTION_REFERENCE_COLUMNS if reference is not None else []))
+        for k in range(N):
+            row = [k + 1, sample[k], f"{float(first[k]):.4f}"]
+            if reference is not None:
+                row += [f"{float(to_ref[k]):.4f}", "" if bool(torch.isnan(rec[k])) else f"{float(rec[k]):.4f}"]
+            w.writerow(row)
+    return path
+
+
 # ---------------------------------------------------------------------------------------------- pockets
 POCKETS_COLUMNS = ["pocket", "score", "size", "center_x", "center_y", "center_z", "ca_center_x", "ca_center_y", "ca_center_z", "docked"]
 
@@ -343,7 +409,8 @@ def complex_dir(out_dir: str, index: int, name: str) -> str:
 
 def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
                   lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None, refine=None, pockets=None,
-                  pockets_docked: int = 1, scores=None, refined_scores=None, minimized=None) -> List[str]:
+                  pockets_docked: int = 1, scores=None, refined_scores=None, minimized=None, interactions=None,
+                  interaction_reference=None) -> List[str]:
     """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
     ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
     lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
@@ -358,7 +425,9 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     scores (scoring.PoseScores of the ranked poses; refined_scores: of the poses after clash relief): also scores.csv.
     minimized (minimize.MinimizeResult of the ranked poses): also rank{k}_minimized.sdf, the pose after the minimisation in the physics
     score, and minimized.csv; a minimize_flex.FlexMinimizeResult: also rank{k}_minimized_protein.pdb, the receptor with the side chains
-    the pose was minimised with (write_receptor), and minimized_sidechains.csv."""
+    the pose was minimised with (write_receptor), and minimized_sidechains.csv.
+    interactions (interactions.InteractionProfile of the ranked poses; interaction_reference: of the known pose): also interactions.csv,
+    interaction_summary.csv and interaction_similarity.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -415,4 +484,9 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
                 write_receptor(put(os.path.join(write_dir, f"rank{k + 1}_minimized_protein.pdb")), pdb_text, graph,
                                [_np(minimized.atom_pos[k])[mv]], remove_hs)
             write_minimized_sidechains_csv(put(os.path.join(write_dir, "minimized_sidechains.csv")), minimized, order)
+    if interactions is not None:
+        write_interactions_csv(put(os.path.join(write_dir, "interactions.csv")), interactions, order)
+        write_interaction_summary_csv(put(os.path.join(write_dir, "interaction_summary.csv")), interactions)
+        write_interaction_similarity_csv(put(os.path.join(write_dir, "interaction_similarity.csv")), interactions, order,
+                                         interaction_reference)
     return written

@@ -878,6 +878,45 @@ typedef struct {
 } ddp_score_args_t;
 int ddp_pose_score(const ddp_score_args_t* args, void* stream);
 
+/* ---- per-residue interaction profile of sampled poses (csrc/ddp_profile.hip; host side diffdock_pocket_amd/interactions.py, which
+ * states the whole definition).  The pair terms, types, cutoff and constants of ddp_pose_score above, summed per residue instead of
+ * over the whole receptor: residue r owns the receptor atoms res_ptr[r] .. res_ptr[r + 1] - 1 (res_ptr [n_res + 1], non-decreasing,
+ * res_ptr[0] = 0, res_ptr[n_res] = m; a residue may be empty; entries are clamped to [0, m] before any read).  Over the pairs (ligand
+ * atom i, atom j of residue r), both typed, d < cutoff (strict), fp64 on the fp32 inputs:
+ *   profile[s][r] = [sum gauss, sum repulsion, sum hydrophobic, sum hbond (unweighted), energy, d_min, pairs]
+ *   energy = w_gauss sum gauss + w_repulsion sum repulsion + w_hydrophobic sum hydrophobic + w_hbond sum hbond: the residue's share of
+ *   inter; d_min = the smallest d of these pairs (+inf: none); pairs = their number (an exact integer held in fp64)
+ *   bits[s][r]: bit 0 CONTACT iff d_min < contact_distance, bit 1 HYDROPHOBIC iff sum hydrophobic > 0, bit 2 HBOND iff sum hbond > 0
+ * Poison rule: a non-finite coordinate of a typed ligand atom of sample s poisons every residue of that sample, a non-finite coordinate
+ * of a typed atom of residue r (in that sample's receptor) poisons that residue of that sample: sums, energy and d_min NaN, pairs 0,
+ * bits 0.  Nothing else is affected.
+ * One 256-thread workgroup per sample, the ligand staged in LDS (n > DDP_EVAL_MAX_ATOMS: DDP_ELIMIT); wave w owns the residues w,
+ * w + 4, ..., its lanes stride over the ligand atoms, one butterfly per residue; a receptor atom farther than cutoff from the ligand's
+ * bounding sphere is passed over (it has no pair).  No atomics: two launches give the same bits, and a sample's result does not
+ * depend on the other samples of the launch.  rec_stride as in ddp_score_args_t.  n_samples = 0 or n_res = 0: no-op.  DDP_EINVAL
+ * without a launch: a NULL struct, pos, lig_radii, lig_flags, res_ptr, profile or bits (m > 0: rec, rec_radii, rec_flags),
+ * n_samples < 0, n <= 0, m < 0, n_res < 0, 0 < rec_stride < 3 m, contact_distance <= 0 or not finite, and the constant checks of
+ * ddp_pose_score. */
+typedef struct {
+  int32_t n_samples, n, m, rec_stride, n_res, reserved;
+  const float* pos;             /* [n_samples][n][3] */
+  const float* lig_radii;       /* [n] */
+  const uint8_t* lig_flags;     /* [n] */
+  const float* rec;
+  const float* rec_radii;       /* [m] */
+  const uint8_t* rec_flags;     /* [m] */
+  const int32_t* res_ptr;       /* [n_res + 1] */
+  double cutoff;
+  double gauss_offset, gauss_width;
+  double hydrophobic_good, hydrophobic_bad;
+  double hbond_good, hbond_bad;
+  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  double contact_distance;
+  double* profile;              /* [n_samples][n_res][7] */
+  uint8_t* bits;                /* [n_samples][n_res] */
+} ddp_profile_args_t;
+int ddp_pose_profile(const ddp_profile_args_t* args, void* stream);
+
 /* ---- local minimisation of sampled poses in the score above, the whole line search in ONE launch (csrc/ddp_minimize.hip; host side
  * diffdock_pocket_amd/minimize.py, which states the whole definition).  Per pose x with start pose x0 = anchor[s], fp64 on the fp32
  * inputs:
