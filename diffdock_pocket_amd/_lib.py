@@ -7,6 +7,7 @@ through PyTorch eager or the CPU oracle.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -122,37 +123,48 @@ class GuidanceArgs(C.Structure):
                 ("max_tr", C.c_double), ("max_rot", C.c_double), ("max_tor", C.c_double), ("upd", _P * 3), ("energy", _P), ("grad", _P)]
 
 
+class ScoreForm(C.Structure):
+    """ddp_score_form_t of include/ddp_hip.h: the eleven constants of the Vinardo-form score, listed here and nowhere else on the
+    Python side.  The four argument structs below embed it as `form` and declare it anonymous, so its fields also read and write
+    under their flat names (a.cutoff is a.form.cutoff)."""
+    _fields_ = [(k, C.c_double) for k in ("cutoff", "gauss_offset", "gauss_width", "hydrophobic_good", "hydrophobic_bad", "hbond_good",
+                                          "hbond_bad", "w_gauss", "w_repulsion", "w_hydrophobic", "w_hbond")]
+    _read = operator.attrgetter(*(k for k, _ in _fields_))
+
+    @classmethod
+    def from_config(cls, config) -> "ScoreForm":
+        """The constants of a scoring.ScoreConfig (anything with the eleven attributes, each a number)."""
+        return cls(*cls._read(config))
+
+
 class ScoreArgs(C.Structure):
     """ddp_score_args_t of include/ddp_hip.h."""
+    _anonymous_ = ("form",)
     _fields_ = [("n_samples", _I), ("n", _I), ("m", _I), ("rec_stride", _I), ("pos", _P), ("lig_radii", _P), ("lig_flags", _P), ("rec", _P),
-                ("rec_radii", _P), ("rec_flags", _P), ("self_pairs", _P), ("cutoff", C.c_double), ("gauss_offset", C.c_double),
-                ("gauss_width", C.c_double), ("hydrophobic_good", C.c_double), ("hydrophobic_bad", C.c_double), ("hbond_good", C.c_double),
-                ("hbond_bad", C.c_double), ("w_gauss", C.c_double), ("w_repulsion", C.c_double), ("w_hydrophobic", C.c_double),
-                ("w_hbond", C.c_double), ("tor_divisor", C.c_double), ("energy", _P), ("grad", _P)]
+                ("rec_radii", _P), ("rec_flags", _P), ("self_pairs", _P), ("form", ScoreForm), ("tor_divisor", C.c_double), ("energy", _P),
+                ("grad", _P)]
 
 
 class ProfileArgs(C.Structure):
     """ddp_profile_args_t of include/ddp_hip.h."""
+    _anonymous_ = ("form",)
     _fields_ = [("n_samples", _I), ("n", _I), ("m", _I), ("rec_stride", _I), ("n_res", _I), ("reserved", _I), ("pos", _P), ("lig_radii", _P),
-                ("lig_flags", _P), ("rec", _P), ("rec_radii", _P), ("rec_flags", _P), ("res_ptr", _P), ("cutoff", C.c_double),
-                ("gauss_offset", C.c_double), ("gauss_width", C.c_double), ("hydrophobic_good", C.c_double), ("hydrophobic_bad", C.c_double),
-                ("hbond_good", C.c_double), ("hbond_bad", C.c_double), ("w_gauss", C.c_double), ("w_repulsion", C.c_double),
-                ("w_hydrophobic", C.c_double), ("w_hbond", C.c_double), ("contact_distance", C.c_double), ("profile", _P), ("bits", _P)]
+                ("lig_flags", _P), ("rec", _P), ("rec_radii", _P), ("rec_flags", _P), ("res_ptr", _P), ("form", ScoreForm),
+                ("contact_distance", C.c_double), ("profile", _P), ("bits", _P)]
 
 
 class MinimizeArgs(C.Structure):
     """ddp_minimize_args_t of include/ddp_hip.h."""
+    _anonymous_ = ("form",)
     _fields_ = [("n_samples", _I), ("n", _I), ("m", _I), ("rec_stride", _I), ("n_tor", _I), ("iterations", _I), ("pos", _P), ("anchor", _P),
                 ("lig_radii", _P), ("lig_flags", _P), ("rec", _P), ("rec_radii", _P), ("rec_flags", _P), ("self_pairs", _P), ("bonds", _P),
-                ("mask_rotate", _P), ("cutoff", C.c_double), ("gauss_offset", C.c_double), ("gauss_width", C.c_double),
-                ("hydrophobic_good", C.c_double), ("hydrophobic_bad", C.c_double), ("hbond_good", C.c_double), ("hbond_bad", C.c_double),
-                ("w_gauss", C.c_double), ("w_repulsion", C.c_double), ("w_hydrophobic", C.c_double), ("w_hbond", C.c_double),
-                ("restraint", C.c_double), ("grow", C.c_double), ("shrink", C.c_double), ("step_max", C.c_double), ("step", _P),
-                ("accepted", _P), ("energy_in", _P), ("energy_out", _P), ("history", _P), ("grad", _P)]
+                ("mask_rotate", _P), ("form", ScoreForm), ("restraint", C.c_double), ("grow", C.c_double), ("shrink", C.c_double),
+                ("step_max", C.c_double), ("step", _P), ("accepted", _P), ("energy_in", _P), ("energy_out", _P), ("history", _P), ("grad", _P)]
 
 
 class MinimizeFlexArgs(C.Structure):
     """ddp_minimize_flex_args_t of include/ddp_hip.h: the fields of ddp_minimize_args_t, then the side chains'."""
+    _anonymous_ = ("form",)
     _fields_ = MinimizeArgs._fields_ + [("rec_anchor", _P), ("n_mov", _I), ("n_sc", _I), ("n_sub", _I), ("reserved", _I), ("mov", _P),
                                         ("sc_edge_idx", _P), ("sc_sub", _P), ("sc_map", _P), ("sc_pairs", _P),
                                         ("restraint_sc", C.c_double), ("grad_mov", _P)]

@@ -2,8 +2,18 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
+#include <stddef.h>
+
 #include "ddp_hip.h"
 #include "ddp_internal.h"
+
+// The layout of ABI version 17.  ddp_score_form_t sits in the four argument structs where their eleven doubles used to be spelled
+// out: a caller compiled against the flat fields and this library agree on every byte.
+static_assert(sizeof(ddp_score_form_t) == 88, "ddp_score_form_t: eleven doubles");
+static_assert(sizeof(ddp_score_args_t) == 184 && offsetof(ddp_score_args_t, form) == 72, "ddp_score_args_t layout");
+static_assert(sizeof(ddp_profile_args_t) == 192 && offsetof(ddp_profile_args_t, form) == 80, "ddp_profile_args_t layout");
+static_assert(sizeof(ddp_minimize_args_t) == 272 && offsetof(ddp_minimize_args_t, form) == 104, "ddp_minimize_args_t layout");
+static_assert(sizeof(ddp_minimize_flex_args_t) == 352 && offsetof(ddp_minimize_flex_args_t, form) == 104, "ddp_minimize_flex_args_t layout");
 
 static thread_local char g_err[256] = "ok";
 

@@ -81,9 +81,8 @@ __global__ __launch_bounds__(DDP_REFINE_THREADS) void ddp_clash_guidance_kernel(
 extern "C" int ddp_clash_guidance(const ddp_clash_guidance_args_t* a, void* stream) {
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_clash_guidance: null argument struct");
   if (a->n_samples == 0) return 0;
-  if (a->n_samples < 0 || a->n <= 0 || a->m < 0 || a->n_tor < 0 || (a->rec_stride != 0 && a->rec_stride < 3 * a->m))
-    return ddp_fail(DDP_EINVAL, "ddp_clash_guidance: shape");
-  if (a->n > DDP_EVAL_MAX_ATOMS) return ddp_fail(DDP_ELIMIT, "ddp_clash_guidance: more than DDP_EVAL_MAX_ATOMS ligand atoms");
+  if (const int rc = ddp_pose_check_shape("ddp_clash_guidance", a->n_samples, a->n, a->m, a->rec_stride, a->n_tor >= 0)) return rc;
+  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_clash_guidance", a->n, DDP_EVAL_MAX_ATOMS)) return rc;
   if (a->n_tor > DDP_GUIDANCE_MAX_TORSIONS) return ddp_fail(DDP_ELIMIT, "ddp_clash_guidance: more than DDP_GUIDANCE_MAX_TORSIONS rotatable bonds");
   if (!a->pos || !a->lig_radii || !a->weight || !a->upd[0] || !a->upd[1] || (a->m > 0 && (!a->rec || !a->rec_radii)) ||
       (a->n_tor > 0 && (!a->bonds || !a->mask_rotate || !a->upd[2])))
@@ -93,7 +92,5 @@ extern "C" int ddp_clash_guidance(const ddp_clash_guidance_args_t* a, void* stre
   // 16 KiB + 40 n + 4 n_tor + 288 bytes: 60.3 KiB at both limits, under the 64 KiB a workgroup gets without opting in to more
   hipLaunchKernelGGL(ddp_clash_guidance_kernel, dim3(a->n_samples), dim3(DDP_REFINE_THREADS), guidance_lds_bytes(a->n, a->n_tor),
                      (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_clash_guidance launch");
-  return 0;
+  return ddp_launch_result("ddp_clash_guidance");
 }

@@ -69,7 +69,7 @@ __device__ __forceinline__ void mz_evaluate(const ddp_minimize_args_t& A, const 
   __syncthreads();
   if (tid == 0) {
     double t[8], inter, intra, er = L.wr[0];
-    score_totals(A, L.we, t, inter, intra);
+    score_totals(A.form, L.we, t, inter, intra);
     for (int w = 1; w < DDP_MZ_WAVES; ++w) er += L.wr[w];
     const double rest = A.restraint * (er / (double)n);
     L.et[0] = inter; L.et[1] = intra; L.et[2] = rest; L.et[3] = (inter + intra) + rest;
@@ -151,20 +151,17 @@ __global__ __launch_bounds__(DDP_MZ_THREADS) void ddp_pose_minimize_kernel(const
 extern "C" int ddp_pose_minimize(const ddp_minimize_args_t* a, void* stream) {
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_pose_minimize: null argument struct");
   if (a->n_samples == 0) return 0;
-  if (a->n_samples < 0 || a->n <= 0 || a->m < 0 || a->n_tor < 0 || (a->rec_stride != 0 && a->rec_stride < 3 * a->m))
-    return ddp_fail(DDP_EINVAL, "ddp_pose_minimize: shape");
-  if (a->n > DDP_MINIMIZE_MAX_ATOMS) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize: more than DDP_MINIMIZE_MAX_ATOMS ligand atoms");
+  if (const int rc = ddp_pose_check_shape("ddp_pose_minimize", a->n_samples, a->n, a->m, a->rec_stride, a->n_tor >= 0)) return rc;
+  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_pose_minimize", a->n, DDP_MINIMIZE_MAX_ATOMS)) return rc;
   if (a->n_tor > DDP_MINIMIZE_MAX_TORSIONS) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize: more than DDP_MINIMIZE_MAX_TORSIONS rotatable bonds");
   if (!a->pos || !a->anchor || !a->lig_radii || !a->lig_flags || !a->step || !a->accepted || !a->energy_in || !a->energy_out ||
       (a->m > 0 && (!a->rec || !a->rec_radii || !a->rec_flags)) || (a->n_tor > 0 && (!a->bonds || !a->mask_rotate)))
     return ddp_fail(DDP_EINVAL, "ddp_pose_minimize: null argument");
   if (a->iterations < 0 || !(a->restraint >= 0.0)) return ddp_fail(DDP_EINVAL, "ddp_pose_minimize: iterations or restraint < 0");
-  if (const int rc = score_check_constants(a, "ddp_pose_minimize")) return rc;
+  if (const int rc = score_check_constants(&a->form, "ddp_pose_minimize")) return rc;
   // the fixed part (receptor tile, its flags, reduction scratch) + two gradients, three coordinate sets, radii and flags per atom:
   // 17.9 KiB + 89 n, 62.4 KiB at the atom limit
   const size_t lds = DDP_MZ_FIXED_BYTES + (size_t)89 * a->n;
   hipLaunchKernelGGL(ddp_pose_minimize_kernel, dim3(a->n_samples), dim3(DDP_MZ_THREADS), lds, (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_pose_minimize launch");
-  return 0;
+  return ddp_launch_result("ddp_pose_minimize");
 }

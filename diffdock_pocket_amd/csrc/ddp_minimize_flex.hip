@@ -114,7 +114,8 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
   }
   if (lane == 0) L.wr[wave] = er_w;
   // ---- the second pass.  d inter / dy_a by gather over the ligand atoms; the assignment also clears gm
-  const double cut2 = A.cutoff * A.cutoff;
+  const ddp_score_form_t& F = A.form;
+  const double cut2 = F.cutoff * F.cutoff;
   for (int r = wave; r < n_mov; r += DDP_FX_WAVES) {
     ScoreAcc acc = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};     // (its energy sums are not used: step 1 has them)
     const double ra = L.mrad[r];
@@ -123,7 +124,7 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
       const unsigned fa = L.mflag[r];
       for (int i = lane; i < n; i += 64) {
         if (L.rad[i] < 0.f) continue;
-        score_pair<true>(A, cut2, xa - (double)x[3 * i], ya - (double)x[3 * i + 1], za - (double)x[3 * i + 2], ra + (double)L.rad[i], fa,
+        score_pair<true>(F, cut2, xa - (double)x[3 * i], ya - (double)x[3 * i + 1], za - (double)x[3 * i + 2], ra + (double)L.rad[i], fa,
                          L.lflag[i], acc);
       }
     }
@@ -160,8 +161,8 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
           if (q.w < 0.f) continue;                 // an untyped receptor atom
           const unsigned fj = L.tflag[j];
           const double dx = xa - (double)q.x, dy = ya - (double)q.y, dz = za - (double)q.z, rsum = ra + (double)q.w;
-          if (fj & DDP_FX_MOVING) score_pair<true>(A, cut2, dx, dy, dz, rsum, fa, fj, mv);
-          else score_pair<true>(A, cut2, dx, dy, dz, rsum, fa, fj, st);
+          if (fj & DDP_FX_MOVING) score_pair<true>(F, cut2, dx, dy, dz, rsum, fa, fj, mv);
+          else score_pair<true>(F, cut2, dx, dy, dz, rsum, fa, fj, st);
         }
       }
       const double gx = wave_sum(st.gx + mv.gx), gy = wave_sum(st.gy + mv.gy), gz = wave_sum(st.gz + mv.gz);
@@ -188,13 +189,13 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
   __syncthreads();
   if (tid == 0) {
     double t[8], inter, intra, er = L.wr[0], er2 = L.wr2[0], c[4];
-    score_totals(A, L.we, t, inter, intra);
+    score_totals(A.form, L.we, t, inter, intra);
     for (int w = 1; w < DDP_FX_WAVES; ++w) { er += L.wr[w]; er2 += L.wr2[w]; }
     for (int k = 0; k < 4; ++k) {
       c[k] = L.we2[0][k];
       for (int w = 1; w < DDP_FX_WAVES; ++w) c[k] += L.we2[w][k];
     }
-    const double sc = A.w_gauss * c[0] + A.w_repulsion * c[1] + A.w_hydrophobic * c[2] + A.w_hbond * c[3];
+    const double sc = F.w_gauss * c[0] + F.w_repulsion * c[1] + F.w_hydrophobic * c[2] + F.w_hbond * c[3];
     const double rest = A.restraint * (er / (double)n);
     const double rest2 = n_mov > 0 ? A.restraint_sc * (er2 / (double)n_mov) : 0.0;
     L.et[0] = inter; L.et[1] = intra; L.et[2] = sc; L.et[3] = rest; L.et[4] = rest2;
@@ -373,11 +374,10 @@ __global__ __launch_bounds__(DDP_FX_THREADS) void ddp_pose_minimize_flex_kernel(
 extern "C" int ddp_pose_minimize_flex(const ddp_minimize_flex_args_t* a, void* stream) {
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: null argument struct");
   if (a->n_samples == 0) return 0;
-  if (a->n_samples < 0 || a->n <= 0 || a->m < 0 || a->n_tor < 0 || a->n_mov < 0 || a->n_sc < 0 || a->n_sub < 0)
-    return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: shape");
-  if (a->rec_stride < 3 * a->m || (a->m > 0 && a->rec_stride == 0))
-    return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: rec is per sample, rec_stride >= 3 m");
-  if (a->n > DDP_MINIMIZE_MAX_ATOMS) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: more than DDP_MINIMIZE_MAX_ATOMS ligand atoms");
+  if (const int rc = ddp_pose_check_shape("ddp_pose_minimize_flex", a->n_samples, a->n, a->m, a->rec_stride,
+                                          a->n_tor >= 0 && a->n_mov >= 0 && a->n_sc >= 0 && a->n_sub >= 0, true))
+    return rc;
+  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_pose_minimize_flex", a->n, DDP_MINIMIZE_MAX_ATOMS)) return rc;
   if (a->n_tor > DDP_MINIMIZE_MAX_TORSIONS) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: more than DDP_MINIMIZE_MAX_TORSIONS rotatable bonds");
   if (a->n_mov > DDP_MINIMIZE_FLEX_MAX_MOVING) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: more than DDP_MINIMIZE_FLEX_MAX_MOVING moving atoms");
   if (a->n_sc > DDP_MINIMIZE_FLEX_MAX_BONDS) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: more than DDP_MINIMIZE_FLEX_MAX_BONDS side-chain bonds");
@@ -391,11 +391,9 @@ extern "C" int ddp_pose_minimize_flex(const ddp_minimize_flex_args_t* a, void* s
     return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: null argument");
   if (a->iterations < 0 || !(a->restraint >= 0.0) || !(a->restraint_sc >= 0.0))
     return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: iterations or a restraint < 0");
-  if (const int rc = score_check_constants(a, "ddp_pose_minimize_flex")) return rc;
+  if (const int rc = score_check_constants(&a->form, "ddp_pose_minimize_flex")) return rc;
   // 18496 bytes fixed + 89 per ligand atom + 81 per moving atom + 4 per side-chain bond: at most 64 KiB
   const size_t lds = DDP_FX_FIXED_BYTES + state;
   hipLaunchKernelGGL(ddp_pose_minimize_flex_kernel, dim3(a->n_samples), dim3(DDP_FX_THREADS), lds, (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_pose_minimize_flex launch");
-  return 0;
+  return ddp_launch_result("ddp_pose_minimize_flex");
 }

@@ -185,7 +185,8 @@ __device__ __forceinline__ void descent_pose_update(const Args& A, const float* 
   __syncthreads();
 }
 
-// ---- the Vinardo-form score of one pose.  x [n][3], rad [n], lflag [n]: the ligand in LDS, visible to all threads no later than the
+// ---- the Vinardo-form score of one pose.  A: the kernel's arguments, of which n, m, rec_radii, rec_flags, self_pairs and the constants
+// A.form (ddp_score_form_t, handed down to score_pair) are read.  x [n][3], rad [n], lflag [n]: the ligand in LDS, visible to all threads no later than the
 // first barrier inside (the caller may stage it right before the call); rs: the sample's receptor in global memory, streamed through
 // tile / tflag (LDS, DDP_SCORE_TILE atoms) that all 256 threads fill with coalesced reads.  Wave w owns the ligand atoms w, w + 4, ...;
 // its lanes stride over the tile, then over the ligand atoms j with self_pairs[min(i, j)][max(i, j)].  The energy sums stay in
@@ -207,7 +208,8 @@ __device__ __forceinline__ void score_evaluate(const Args& A, const float* __res
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m;
   if (GRAD)
     for (int i = tid; i < 3 * n; i += DDP_DESCENT_THREADS) gacc[i] = 0.0;
-  const double cut2 = A.cutoff * A.cutoff;
+  const ddp_score_form_t& F = A.form;
+  const double cut2 = F.cutoff * F.cutoff;
   ScoreAcc cross = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};  // this lane's share, over every atom and tile it meets
   for (int j0 = 0; j0 < m; j0 += DDP_SCORE_TILE) {
     const int mt = min(DDP_SCORE_TILE, m - j0);
@@ -229,7 +231,7 @@ __device__ __forceinline__ void score_evaluate(const Args& A, const float* __res
       for (int j = lane; j < mt; j += 64) {
         const float4 r = tile[j];
         if (r.w < 0.f) continue;                 // an untyped receptor atom
-        score_pair<GRAD>(A, cut2, xi - (double)r.x, yi - (double)r.y, zi - (double)r.z, ri + (double)r.w, fi, tflag[j], cross);
+        score_pair<GRAD>(F, cut2, xi - (double)r.x, yi - (double)r.y, zi - (double)r.z, ri + (double)r.w, fi, tflag[j], cross);
       }
       if (GRAD) {
         const double gx = wave_sum(cross.gx), gy = wave_sum(cross.gy), gz = wave_sum(cross.gz);
@@ -247,7 +249,7 @@ __device__ __forceinline__ void score_evaluate(const Args& A, const float* __res
       const unsigned fi = lflag[i];
       for (int j = lane; j < n; j += 64) {
         if (j == i || rad[j] < 0.f || !A.self_pairs[(size_t)min(i, j) * n + max(i, j)]) continue;
-        score_pair<GRAD>(A, cut2, xi - (double)x[3 * j], yi - (double)x[3 * j + 1], zi - (double)x[3 * j + 2], ri + (double)rad[j], fi,
+        score_pair<GRAD>(F, cut2, xi - (double)x[3 * j], yi - (double)x[3 * j + 1], zi - (double)x[3 * j + 2], ri + (double)rad[j], fi,
                          lflag[j], self);
       }
     }
@@ -265,8 +267,7 @@ __device__ __forceinline__ void score_evaluate(const Args& A, const float* __res
 }
 
 // by one thread, after score_evaluate: t[8] = the eight sums over the waves in wave order, inter and intra = the weighted energies
-template <class Args>
-__device__ __forceinline__ void score_totals(const Args& A, const double (*we)[8], double* t, double& inter, double& intra) {
+__device__ __forceinline__ void score_totals(const ddp_score_form_t& A, const double (*we)[8], double* t, double& inter, double& intra) {
   for (int k = 0; k < 8; ++k) {
     t[k] = we[0][k];
     for (int w = 1; w < DDP_DESCENT_WAVES; ++w) t[k] += we[w][k];
@@ -276,9 +277,8 @@ __device__ __forceinline__ void score_totals(const Args& A, const double (*we)[8
   intra = A.w_gauss * (0.5 * t[4]) + A.w_repulsion * (0.5 * t[5]) + A.w_hydrophobic * (0.5 * t[6]) + A.w_hbond * (0.5 * t[7]);
 }
 
-// host: the constants of the form that ddp_pose_score and ddp_pose_minimize both take; 0, or DDP_EINVAL with a text that names `who`
-template <class Args>
-static inline int score_check_constants(const Args* a, const char* who) {
+// host: the constant checks of ddp_score_form_t, for every entry that takes a form; 0, or DDP_EINVAL with a text that names `who`
+static inline int score_check_constants(const ddp_score_form_t* a, const char* who) {
   char msg[128];
   const char* what = nullptr;
   if (!(a->cutoff > 0.0) || !isfinite(a->cutoff)) what = "cutoff must be positive and finite";

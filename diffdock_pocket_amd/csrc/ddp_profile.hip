@@ -67,8 +67,9 @@ __global__ __launch_bounds__(DDP_DESCENT_THREADS) void ddp_pose_profile_kernel(c
   // a receptor atom at more than `reach` from the centre has every ligand atom at cutoff or more: |r - x_i| >= |r - c| - |x_i - c|.
   // The factor covers the rounding of the three distances (a few 2^-53 each) with room to spare, so the pairs passed over are
   // exactly pairs that score_pair would have rejected.
-  const double reach = (A.cutoff + sqrt(rho2)) * (1.0 + 0x1p-40), reach2 = reach * reach;
-  const double cut2 = A.cutoff * A.cutoff;
+  const ddp_score_form_t& F = A.form;
+  const double reach = (F.cutoff + sqrt(rho2)) * (1.0 + 0x1p-40), reach2 = reach * reach;
+  const double cut2 = F.cutoff * F.cutoff;
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   const float* __restrict__ rs = A.rec + (size_t)s * A.rec_stride;
   double* __restrict__ prof = A.profile + (size_t)s * R * 7;
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(DDP_DESCENT_THREADS) void ddp_pose_profile_kernel(c
     auto pair = [&](double dx, double dy, double dz, double rsum, unsigned fi, unsigned fj) {
       const double d2 = dx * dx + dy * dy + dz * dz;
       if (d2 < cut2) { count += 1; dmin2 = fmin(dmin2, d2); }
-      score_pair<false>(A, cut2, dx, dy, dz, rsum, fi, fj, acc);
+      score_pair<false>(F, cut2, dx, dy, dz, rsum, fi, fj, acc);
     };
     for (int c0 = j0; c0 < j1 && !lig_bad; c0 += 64) {
       const Chunk cur = load_chunk(c0, j1);
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(DDP_DESCENT_THREADS) void ddp_pose_profile_kernel(c
       } else {
         const double dmin = sqrt(dmin2);
         p[0] = t[0]; p[1] = t[1]; p[2] = t[2]; p[3] = t[3];
-        p[4] = A.w_gauss * t[0] + A.w_repulsion * t[1] + A.w_hydrophobic * t[2] + A.w_hbond * t[3];
+        p[4] = F.w_gauss * t[0] + F.w_repulsion * t[1] + F.w_hydrophobic * t[2] + F.w_hbond * t[3];
         p[5] = dmin;
         p[6] = (double)count;
         bits[r] = (uint8_t)((dmin < A.contact_distance ? 1 : 0) | (t[2] > 0.0 ? 2 : 0) | (t[3] > 0.0 ? 4 : 0));
@@ -153,18 +154,15 @@ __global__ __launch_bounds__(DDP_DESCENT_THREADS) void ddp_pose_profile_kernel(c
 extern "C" int ddp_pose_profile(const ddp_profile_args_t* a, void* stream) {
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_pose_profile: null argument struct");
   if (a->n_samples == 0 || a->n_res == 0) return 0;
-  if (a->n_samples < 0 || a->n <= 0 || a->m < 0 || a->n_res < 0 || (a->rec_stride != 0 && a->rec_stride < 3 * a->m))
-    return ddp_fail(DDP_EINVAL, "ddp_pose_profile: shape");
-  if (a->n > DDP_EVAL_MAX_ATOMS) return ddp_fail(DDP_ELIMIT, "ddp_pose_profile: more than DDP_EVAL_MAX_ATOMS ligand atoms");
+  if (const int rc = ddp_pose_check_shape("ddp_pose_profile", a->n_samples, a->n, a->m, a->rec_stride, a->n_res >= 0)) return rc;
+  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_pose_profile", a->n, DDP_EVAL_MAX_ATOMS)) return rc;
   if (!a->pos || !a->lig_radii || !a->lig_flags || !a->res_ptr || !a->profile || !a->bits ||
       (a->m > 0 && (!a->rec || !a->rec_radii || !a->rec_flags)))
     return ddp_fail(DDP_EINVAL, "ddp_pose_profile: null argument");
-  if (const int rc = score_check_constants(a, "ddp_pose_profile")) return rc;
+  if (const int rc = score_check_constants(&a->form, "ddp_pose_profile")) return rc;
   if (!(a->contact_distance > 0.0) || !isfinite(a->contact_distance))
     return ddp_fail(DDP_EINVAL, "ddp_pose_profile: contact_distance must be positive and finite");
   const size_t lds = (size_t)a->n * (4 * sizeof(float) + 1);
   hipLaunchKernelGGL(ddp_pose_profile_kernel, dim3(a->n_samples), dim3(DDP_DESCENT_THREADS), lds, (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_pose_profile launch");
-  return 0;
+  return ddp_launch_result("ddp_pose_profile");
 }

@@ -45,20 +45,11 @@ __global__ __launch_bounds__(DDP_REFINE_THREADS) void ddp_refine_energy_kernel(c
 
 static int refine_common(const ddp_refine_args_t* a, const char* who, int* rc) {
   // shared shape checks; returns 1 when the call is a no-op or failed (*rc holds the result)
-  static thread_local char msg[96];
   *rc = 0;
   if (!a) { *rc = ddp_fail(DDP_EINVAL, "ddp_refine: null argument struct"); return 1; }
   if (a->n_samples == 0) return 1;
-  if (a->n_samples < 0 || a->n <= 0 || a->m < 0 || a->n_tor < 0 || (a->rec_stride != 0 && a->rec_stride < 3 * a->m)) {
-    snprintf(msg, sizeof msg, "%s: shape", who);
-    *rc = ddp_fail(DDP_EINVAL, msg);
-    return 1;
-  }
-  if (a->n > DDP_EVAL_MAX_ATOMS) {
-    snprintf(msg, sizeof msg, "%s: more than DDP_EVAL_MAX_ATOMS ligand atoms", who);
-    *rc = ddp_fail(DDP_ELIMIT, msg);
-    return 1;
-  }
+  if ((*rc = ddp_pose_check_shape(who, a->n_samples, a->n, a->m, a->rec_stride, a->n_tor >= 0))) return 1;
+  if ((*rc = DDP_POSE_CHECK_ATOMS(who, a->n, DDP_EVAL_MAX_ATOMS))) return 1;
   return 0;
 }
 
@@ -71,9 +62,7 @@ extern "C" int ddp_refine_energy(const ddp_refine_args_t* a, void* stream) {
   // the receptor tile + gradient accumulators + ligand coordinates and radii: 16 KiB + 40 n, 56 KiB at the atom limit
   const size_t lds = DDP_REFINE_TILE * sizeof(float4) + (size_t)3 * a->n * sizeof(double) + (size_t)4 * a->n * sizeof(float);
   hipLaunchKernelGGL(ddp_refine_energy_kernel, dim3(a->n_samples), dim3(DDP_REFINE_THREADS), lds, (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_refine_energy launch");
-  return 0;
+  return ddp_launch_result("ddp_refine_energy");
 }
 
 // ---- search direction of sample s: descent_direction (ddp_pose_descent.h) on the pose and the gradient in global memory
@@ -90,9 +79,7 @@ extern "C" int ddp_refine_direction(const ddp_refine_args_t* a, void* stream) {
   if (!a->pos || !a->grad || !a->step || !a->tr || !a->rot || (a->n_tor > 0 && (!a->tor || !a->bonds || !a->mask_rotate)))
     return ddp_fail(DDP_EINVAL, "ddp_refine_direction: null argument");
   hipLaunchKernelGGL(ddp_refine_direction_kernel, dim3(a->n_samples), dim3(DDP_REFINE_THREADS), 0, (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_refine_direction launch");
-  return 0;
+  return ddp_launch_result("ddp_refine_direction");
 }
 
 // ---- the line search's decision, per sample: trial_energy[s][3] < energy[s][3] (strict, fp64; false for NaN) takes the trial pose,
@@ -127,7 +114,5 @@ extern "C" int ddp_refine_accept(const ddp_refine_args_t* a, void* stream) {
   if (!a->pos || !a->trial || !a->energy || !a->trial_energy || !a->step || !a->accepted || (!a->grad) != (!a->trial_grad))
     return ddp_fail(DDP_EINVAL, "ddp_refine_accept: null argument");
   hipLaunchKernelGGL(ddp_refine_accept_kernel, dim3(a->n_samples), dim3(DDP_REFINE_THREADS), 0, (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_refine_accept launch");
-  return 0;
+  return ddp_launch_result("ddp_refine_accept");
 }

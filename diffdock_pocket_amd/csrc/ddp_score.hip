@@ -38,7 +38,7 @@ __global__ __launch_bounds__(DDP_DESCENT_THREADS) void ddp_pose_score_kernel(con
   }
   if (tid == 0) {
     double t[8], inter, intra;
-    score_totals(A, we, t, inter, intra);
+    score_totals(A.form, we, t, inter, intra);
     double* e = A.energy + 7 * (size_t)s;
     e[0] = t[0]; e[1] = t[1]; e[2] = t[2]; e[3] = t[3]; e[4] = inter; e[5] = intra; e[6] = inter / A.tor_divisor;
   }
@@ -47,12 +47,11 @@ __global__ __launch_bounds__(DDP_DESCENT_THREADS) void ddp_pose_score_kernel(con
 extern "C" int ddp_pose_score(const ddp_score_args_t* a, void* stream) {
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_pose_score: null argument struct");
   if (a->n_samples == 0) return 0;
-  if (a->n_samples < 0 || a->n <= 0 || a->m < 0 || (a->rec_stride != 0 && a->rec_stride < 3 * a->m))
-    return ddp_fail(DDP_EINVAL, "ddp_pose_score: shape");
-  if (a->n > DDP_EVAL_MAX_ATOMS) return ddp_fail(DDP_ELIMIT, "ddp_pose_score: more than DDP_EVAL_MAX_ATOMS ligand atoms");
+  if (const int rc = ddp_pose_check_shape("ddp_pose_score", a->n_samples, a->n, a->m, a->rec_stride, true)) return rc;
+  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_pose_score", a->n, DDP_EVAL_MAX_ATOMS)) return rc;
   if (!a->pos || !a->lig_radii || !a->lig_flags || !a->energy || (a->m > 0 && (!a->rec || !a->rec_radii || !a->rec_flags)))
     return ddp_fail(DDP_EINVAL, "ddp_pose_score: null argument");
-  if (const int rc = score_check_constants(a, "ddp_pose_score")) return rc;
+  if (const int rc = score_check_constants(&a->form, "ddp_pose_score")) return rc;
   if (!(a->tor_divisor > 0.0)) return ddp_fail(DDP_EINVAL, "ddp_pose_score: tor_divisor must be positive");
   // the receptor tile and its flags + the ligand's coordinates, radii and flags (+ the gradient accumulators): 17 KiB + 17 n (+ 24 n),
   // 58 KiB at the atom limit
@@ -61,7 +60,5 @@ extern "C" int ddp_pose_score(const ddp_score_args_t* a, void* stream) {
     hipLaunchKernelGGL(ddp_pose_score_kernel<true>, dim3(a->n_samples), dim3(DDP_DESCENT_THREADS), lds, (hipStream_t)stream, *a);
   else
     hipLaunchKernelGGL(ddp_pose_score_kernel<false>, dim3(a->n_samples), dim3(DDP_DESCENT_THREADS), lds, (hipStream_t)stream, *a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ddp_fail_hip(err, "ddp_pose_score launch");
-  return 0;
+  return ddp_launch_result("ddp_pose_score");
 }

@@ -1,9 +1,12 @@
 // ddp_score_pair.h - the pair arithmetic of the Vinardo-form score, used by score_evaluate (ddp_pose_descent.h) for ddp_pose_score and
-// the fused minimiser.  Args is any struct that carries the constants of the form under the names of ddp_score_args_t.
+// the two minimisers, and by the interaction profile (ddp_profile.hip).  The constants come in ddp_score_form_t (include/ddp_hip.h,
+// which states the form): the `form` member of every entry's argument struct.
 #ifndef DDP_SCORE_PAIR_H
 #define DDP_SCORE_PAIR_H
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include "ddp_hip.h"
 
 // The four unweighted sums (gauss, repulsion, hydrophobic, hbond) and, with GRAD, the gradient of the weighted energy with respect to
 // the first atom.
@@ -15,8 +18,8 @@ struct ScoreAcc {
 // One typed pair at centre offset (dx, dy, dz) = x_first - x_second, rsum = R_first + R_second, flag bytes fi and fj.  d^2 is tested
 // against cutoff^2 before the square root and the exponential; the comparison is written so that a NaN distance goes through and
 // poisons the sums.  The ramps have their slope on the open interval only; d = 0 adds the energy and no gradient.
-template <bool GRAD, class Args>
-__device__ __forceinline__ void score_pair(const Args& A, double cut2, double dx, double dy, double dz, double rsum, unsigned fi,
+template <bool GRAD>
+__device__ __forceinline__ void score_pair(const ddp_score_form_t& A, double cut2, double dx, double dy, double dz, double rsum, unsigned fi,
                                            unsigned fj, ScoreAcc& acc) {
   const double d2 = dx * dx + dy * dy + dz * dz;
   if (d2 >= cut2) return;

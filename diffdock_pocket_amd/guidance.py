@@ -134,11 +134,7 @@ class GuidanceWorkspace:
                 (rec, torch.float32, (S, self.m, 3), "rec"), (energy, torch.float64, (S, 2), "energy"), (grad, torch.float64, (S, self.n, 3), "grad")]
         if self.T:
             want.append((upd[2], torch.float32, (S, self.T), "upd tor"))
-        for t, dt, shape, what in want:
-            if t is None and what in ("rec", "energy", "grad"):
-                continue
-            if t is None or t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape:
-                raise ValueError(f"GuidanceWorkspace.launch: {what}: a contiguous {dt} tensor of shape {shape} on {self.device} expected")
+        LA.check_tensors("GuidanceWorkspace.launch", self.device, want, ("rec", "energy", "grad"), error=ValueError)
         if weight.dtype != torch.float32 or weight.device != self.device or weight.numel() < 1 or not weight.is_contiguous():
             raise ValueError("GuidanceWorkspace.launch: weight = one fp32 value in device memory")
         a = self.args

@@ -707,6 +707,51 @@ def pose_cluster(dist, order=None, cutoff=2.0):
     return labels, reps, sizes, count
 
 
+# ------------------------------------------------------------------------------------------------ the pose entries: shared argument handling
+# Clash relief, the physics score, the interaction profile and the two minimisers all work on S poses of one ligand against a receptor.
+# Each wrapper below is a table of (tensor, dtype, shape or None, name of the struct's pointer field) plus its scalars; the three
+# functions here do the rest.  Nothing in them downloads a device tensor.
+def pose_dims(who, pos, rec, per_sample=False):
+    """(dev, S, n, m, rec_stride) of pos [S, n, 3] fp32 and rec [m, 3] (one receptor for all samples: rec_stride 0) or [S, m, 3] (one per
+    sample: rec_stride 3 m; per_sample: the only form allowed, as the joint minimiser writes to it)."""
+    dev = pos.device
+    _eval_arg(pos, torch.float32, dev, f"{who} pos")
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise L.DdpError(f"{who}: pos [S, n, 3]")
+    S, n = pos.shape[0], pos.shape[1]
+    if rec.dim() not in ((3,) if per_sample else (2, 3)) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
+        raise L.DdpError(f"{who}: rec [S, m, 3], one receptor per sample" if per_sample else f"{who}: rec [m, 3] or [S, m, 3]")
+    m = rec.shape[-2]
+    return dev, S, n, m, 3 * m if rec.dim() == 3 else 0
+
+
+def check_tensors(who, dev, want, optional=(), error=L.DdpError):
+    """Every row (tensor, dtype, shape or None, name) of `want` is a contiguous tensor of that dtype on `dev` and, where a shape (a tuple)
+    is given, of that shape; a row whose tensor is None passes if its name is in `optional` (optional=None: every row may be None) and
+    raises otherwise.  The message carries `who` and the row's name."""
+    for t, dt, shape, name in want:
+        if t is None:
+            if optional is None or name in optional:
+                continue
+            raise error(f"{who} {name}: missing")
+        if t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise error(f"{who} {name}: expected a contiguous {dt} tensor on {dev}, got {t.dtype} on {t.device}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise error(f"{who} {name}: expected {shape}, got {tuple(t.shape)}")
+
+
+def _pose_args(cls, who, dev, want, optional, config=None, **scalars):
+    """The checked argument struct: cls(**scalars), `form` from config (a scoring.ScoreConfig; None: the struct has no form), and the
+    address of every row's tensor under the row's name.  The struct holds raw addresses: the caller keeps the tensors alive."""
+    check_tensors(who, dev, want, optional)
+    a = cls(**scalars)
+    if config is not None:
+        a.form = L.ScoreForm.from_config(config)
+    for t, _, _, name in want:
+        setattr(a, name, _p(t) or None)
+    return a
+
+
 # ------------------------------------------------------------------------------------------------ clash relief (csrc/ddp_refine.hip)
 def refine_args(pos, anchor, lig_radii, rec, rec_radii, self_pairs=None, overlap=0.4, restraint=0.0, energy=None, grad=None,
                 bonds=None, mask_rotate=None, step=None, tr=None, rot=None, tor=None, trial=None, trial_energy=None, trial_grad=None,
@@ -717,38 +762,18 @@ def refine_args(pos, anchor, lig_radii, rec, rec_radii, self_pairs=None, overlap
     here: that would be a device-to-host copy, i.e. a synchronisation, per call), mask_rotate uint8 [T, n]; tr, rot
     [S, 3], tor [S, T] fp32; accepted int32 [S].  Tensors an entry does not use may be None.  The struct holds raw addresses: the
     caller keeps the tensors alive while it is in use."""
-    dev = pos.device
-    _eval_arg(pos, torch.float32, dev, "refine pos")
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise L.DdpError("refine: pos [S, n, 3]")
-    S, n = pos.shape[0], pos.shape[1]
-    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
-        raise L.DdpError("refine: rec [m, 3] or [S, m, 3]")
-    m = rec.shape[-2]
+    dev, S, n, m, rec_stride = pose_dims("refine", pos, rec)
     T = 0 if bonds is None else int(bonds.shape[0])
-    want = [(anchor, torch.float32, (S, n, 3), "anchor"), (lig_radii, torch.float32, (n,), "lig_radii"), (rec, torch.float32, None, "rec"),
-            (rec_radii, torch.float32, (m,), "rec_radii"), (self_pairs, torch.uint8, (n, n), "self_pairs"),
-            (energy, torch.float64, (S, 4), "energy"), (grad, torch.float64, (S, n, 3), "grad"), (bonds, torch.int32, (T, 2), "bonds"),
-            (mask_rotate, torch.uint8, (T, n), "mask_rotate"), (step, torch.float64, (S,), "step"), (tr, torch.float32, (S, 3), "tr"),
-            (rot, torch.float32, (S, 3), "rot"), (tor, torch.float32, (S, T), "tor"), (trial, torch.float32, (S, n, 3), "trial"),
-            (trial_energy, torch.float64, (S, 4), "trial_energy"), (trial_grad, torch.float64, (S, n, 3), "trial_grad"),
-            (accepted, torch.int32, (S,), "accepted")]
-    for t, dt, shape, what in want:
-        if t is None:
-            continue
-        _eval_arg(t, dt, dev, f"refine {what}")
-        if shape is not None and tuple(t.shape) != shape:
-            raise L.DdpError(f"refine {what}: expected {shape}, got {tuple(t.shape)}")
+    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+    want = [(pos, f32, (S, n, 3), "pos"), (anchor, f32, (S, n, 3), "anchor"), (lig_radii, f32, (n,), "lig_radii"), (rec, f32, None, "rec"),
+            (rec_radii, f32, (m,), "rec_radii"), (self_pairs, u8, (n, n), "self_pairs"), (energy, f64, (S, 4), "energy"),
+            (grad, f64, (S, n, 3), "grad"), (bonds, i32, (T, 2), "bonds"), (mask_rotate, u8, (T, n), "mask_rotate"), (step, f64, (S,), "step"),
+            (tr, f32, (S, 3), "tr"), (rot, f32, (S, 3), "rot"), (tor, f32, (S, T), "tor"), (trial, f32, (S, n, 3), "trial"),
+            (trial_energy, f64, (S, 4), "trial_energy"), (trial_grad, f64, (S, n, 3), "trial_grad"), (accepted, i32, (S,), "accepted")]
     if T > 0 and mask_rotate is None:
         raise L.DdpError("refine: bonds without mask_rotate")
-    a = L.RefineArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, n_tor=T, overlap=float(overlap),
-                     restraint=float(restraint), grow=float(grow), shrink=float(shrink), step_max=float(step_max))
-    for name, t in (("pos", pos), ("anchor", anchor), ("lig_radii", lig_radii), ("rec", rec), ("rec_radii", rec_radii),
-                    ("self_pairs", self_pairs), ("energy", energy), ("grad", grad), ("bonds", bonds), ("mask_rotate", mask_rotate),
-                    ("step", step), ("tr", tr), ("rot", rot), ("tor", tor), ("trial", trial), ("trial_energy", trial_energy),
-                    ("trial_grad", trial_grad), ("accepted", accepted)):
-        setattr(a, name, _p(t) or None)
-    return a
+    return _pose_args(L.RefineArgs, "refine", dev, want, None, n_samples=S, n=n, m=m, rec_stride=rec_stride, n_tor=T, overlap=float(overlap),
+                      restraint=float(restraint), grow=float(grow), shrink=float(shrink), step_max=float(step_max))
 
 
 def refine_bonds(bonds, n: int, device) -> torch.Tensor:
@@ -794,36 +819,17 @@ def pose_score(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, tor
     None; config: scoring.ScoreConfig (the constants of the form).  Returns (energy [S, 7] fp64 = gauss, repulsion, hydrophobic, hbond,
     inter, intra, total; grad [S, n, 3] fp64 or None).  energy / grad: tensors to write into (grad given, or with_grad: the gradient is
     computed)."""
-    dev = pos.device
-    _eval_arg(pos, torch.float32, dev, "pose_score pos")
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise L.DdpError("pose_score: pos [S, n, 3]")
-    S, n = pos.shape[0], pos.shape[1]
-    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
-        raise L.DdpError("pose_score: rec [m, 3] or [S, m, 3]")
-    m = rec.shape[-2]
+    dev, S, n, m, rec_stride = pose_dims("pose_score", pos, rec)
     if energy is None:
         energy = torch.empty(S, 7, dtype=torch.float64, device=dev)
     if grad is None and with_grad:
         grad = torch.empty(S, n, 3, dtype=torch.float64, device=dev)
-    want = [(lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"), (rec, torch.float32, None, "rec"),
-            (rec_radii, torch.float32, (m,), "rec_radii"), (rec_flags, torch.uint8, (m,), "rec_flags"),
-            (self_pairs, torch.uint8, (n, n), "self_pairs"), (energy, torch.float64, (S, 7), "energy"), (grad, torch.float64, (S, n, 3), "grad")]
-    for t, dt, shape, what in want:
-        if t is None:
-            continue
-        _eval_arg(t, dt, dev, f"pose_score {what}")
-        if shape is not None and tuple(t.shape) != shape:
-            raise L.DdpError(f"pose_score {what}: expected {shape}, got {tuple(t.shape)}")
-    c = config
-    a = L.ScoreArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, cutoff=float(c.cutoff),
-                    gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width), hydrophobic_good=float(c.hydrophobic_good),
-                    hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good), hbond_bad=float(c.hbond_bad),
-                    w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion), w_hydrophobic=float(c.w_hydrophobic),
-                    w_hbond=float(c.w_hbond), tor_divisor=float(tor_divisor))
-    for name, t in (("pos", pos), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_radii", rec_radii),
-                    ("rec_flags", rec_flags), ("self_pairs", self_pairs), ("energy", energy), ("grad", grad)):
-        setattr(a, name, _p(t) or None)
+    f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+    want = [(pos, f32, (S, n, 3), "pos"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"), (rec, f32, None, "rec"),
+            (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (self_pairs, u8, (n, n), "self_pairs"),
+            (energy, f64, (S, 7), "energy"), (grad, f64, (S, n, 3), "grad")]
+    a = _pose_args(L.ScoreArgs, "pose_score", dev, want, ("self_pairs", "grad"), config, n_samples=S, n=n, m=m, rec_stride=rec_stride,
+                   tor_divisor=float(tor_divisor))
     L.check(L.load().ddp_pose_score(C.byref(a), stream()), "ddp_pose_score")
     return energy, grad
 
@@ -834,14 +840,7 @@ def pose_profile(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, res_ptr, 
     [R + 1]: residue r owns the receptor atoms res_ptr[r] .. res_ptr[r + 1] - 1 (its values are not looked at here: the kernel clamps
     them to [0, m]).  Returns (profile [S, R, 7] fp64 = gauss, repulsion, hydrophobic, hbond, energy, d_min, pairs; bits [S, R] uint8:
     bit 0 contact, 1 hydrophobic, 2 hbond).  profile / bits: tensors to write into."""
-    dev = pos.device
-    _eval_arg(pos, torch.float32, dev, "pose_profile pos")
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise L.DdpError("pose_profile: pos [S, n, 3]")
-    S, n = pos.shape[0], pos.shape[1]
-    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
-        raise L.DdpError("pose_profile: rec [m, 3] or [S, m, 3]")
-    m = rec.shape[-2]
+    dev, S, n, m, rec_stride = pose_dims("pose_profile", pos, rec)
     if res_ptr is None or res_ptr.dim() != 1 or res_ptr.shape[0] < 1:
         raise L.DdpError("pose_profile: res_ptr [R + 1]")
     R = res_ptr.shape[0] - 1
@@ -849,27 +848,39 @@ def pose_profile(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, res_ptr, 
         profile = torch.empty(S, R, 7, dtype=torch.float64, device=dev)
     if bits is None:
         bits = torch.empty(S, R, dtype=torch.uint8, device=dev)
-    want = [(lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"), (rec, torch.float32, None, "rec"),
-            (rec_radii, torch.float32, (m,), "rec_radii"), (rec_flags, torch.uint8, (m,), "rec_flags"),
-            (res_ptr, torch.int32, (R + 1,), "res_ptr"), (profile, torch.float64, (S, R, 7), "profile"), (bits, torch.uint8, (S, R), "bits")]
-    for t, dt, shape, what in want:
-        _eval_arg(t, dt, dev, f"pose_profile {what}")
-        if shape is not None and tuple(t.shape) != shape:
-            raise L.DdpError(f"pose_profile {what}: expected {shape}, got {tuple(t.shape)}")
-    c = config
-    a = L.ProfileArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, n_res=R, cutoff=float(c.cutoff),
-                      gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width), hydrophobic_good=float(c.hydrophobic_good),
-                      hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good), hbond_bad=float(c.hbond_bad),
-                      w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion), w_hydrophobic=float(c.w_hydrophobic),
-                      w_hbond=float(c.w_hbond), contact_distance=float(contact_distance))
-    for name, t in (("pos", pos), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_radii", rec_radii),
-                    ("rec_flags", rec_flags), ("res_ptr", res_ptr), ("profile", profile), ("bits", bits)):
-        setattr(a, name, _p(t) or None)
+    f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+    want = [(pos, f32, (S, n, 3), "pos"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"), (rec, f32, None, "rec"),
+            (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (res_ptr, torch.int32, (R + 1,), "res_ptr"),
+            (profile, f64, (S, R, 7), "profile"), (bits, u8, (S, R), "bits")]
+    a = _pose_args(L.ProfileArgs, "pose_profile", dev, want, (), config, n_samples=S, n=n, m=m, rec_stride=rec_stride, n_res=R,
+                   contact_distance=float(contact_distance))
     L.check(L.load().ddp_pose_profile(C.byref(a), stream()), "ddp_pose_profile")
     return profile, bits
 
 
 # ------------------------------------------------------------------------------------------------ fused minimiser (csrc/ddp_minimize.hip)
+def _minimize(who, cls, width, pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate, step,
+              accepted, energy_in, energy_out, iterations, restraint, grow, shrink, step_max, history, grad, side=None):
+    """The call of both minimisers: the ligand's table and scalars, energies [S, width].  side (the joint minimiser): a function of
+    (S, m) that gives the side chains' rows, those of their names that may be None, and their scalars; with it rec is per sample."""
+    dev, S, n, m, rec_stride = pose_dims(who, pos, rec, per_sample=side is not None)
+    T = 0 if bonds is None else int(bonds.shape[0])
+    iterations = int(iterations)
+    if iterations < 0:
+        raise L.DdpError(f"{who}: iterations < 0")
+    rows, optional, scalars = side(S, m) if side is not None else ([], (), {})
+    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+    want = [(pos, f32, (S, n, 3), "pos"), (anchor, f32, (S, n, 3), "anchor"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"),
+            (rec, f32, None, "rec"), (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (self_pairs, u8, (n, n), "self_pairs"),
+            (bonds, i32, (T, 2), "bonds"), (mask_rotate, u8, (T, n), "mask_rotate")] + rows + \
+           [(step, f64, (S,), "step"), (accepted, i32, (S,), "accepted"), (energy_in, f64, (S, width), "energy_in"),
+            (energy_out, f64, (S, width), "energy_out"), (history, f64, (iterations + 1, S), "history"), (grad, f64, (S, n, 3), "grad")]
+    optional = ("self_pairs", "history", "grad") + tuple(optional) + (("bonds", "mask_rotate") if T == 0 else ())
+    a = _pose_args(cls, who, dev, want, optional, config, n_samples=S, n=n, m=m, rec_stride=rec_stride, n_tor=T, iterations=iterations,
+                   restraint=float(restraint), grow=float(grow), shrink=float(shrink), step_max=float(step_max), **scalars)
+    L.check(getattr(L.load(), "ddp_" + who)(C.byref(a), stream()), "ddp_" + who)
+
+
 def pose_minimize(pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate, step, accepted,
                   energy_in, energy_out, iterations, restraint=0.0, grow=2.0, shrink=0.5, step_max=1024.0, history=None, grad=None):
     """ddp_pose_minimize: `iterations` iterations of the line search of minimize.py on every pose, in one launch.  pos (in/out), anchor
@@ -877,44 +888,8 @@ def pose_minimize(pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, 
     or None; config: scoring.ScoreConfig; bonds int32 [T, 2] as refine_bonds returns it (its values are not looked at here), mask_rotate
     uint8 [T, n]; step [S] fp64 and accepted [S] int32 (in/out); energy_in, energy_out [S, 4], history [iterations + 1, S] or None,
     grad [S, n, 3] or None, fp64.  Shapes and dtypes are checked here; no device tensor is downloaded."""
-    dev = pos.device
-    _eval_arg(pos, torch.float32, dev, "pose_minimize pos")
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise L.DdpError("pose_minimize: pos [S, n, 3]")
-    S, n = pos.shape[0], pos.shape[1]
-    if rec.dim() not in (2, 3) or rec.shape[-1] != 3 or (rec.dim() == 3 and rec.shape[0] != S):
-        raise L.DdpError("pose_minimize: rec [m, 3] or [S, m, 3]")
-    m = rec.shape[-2]
-    T = 0 if bonds is None else int(bonds.shape[0])
-    iterations = int(iterations)
-    if iterations < 0:
-        raise L.DdpError("pose_minimize: iterations < 0")
-    want = [(anchor, torch.float32, (S, n, 3), "anchor"), (lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"),
-            (rec, torch.float32, None, "rec"), (rec_radii, torch.float32, (m,), "rec_radii"), (rec_flags, torch.uint8, (m,), "rec_flags"),
-            (self_pairs, torch.uint8, (n, n), "self_pairs"), (bonds, torch.int32, (T, 2), "bonds"), (mask_rotate, torch.uint8, (T, n), "mask_rotate"),
-            (step, torch.float64, (S,), "step"), (accepted, torch.int32, (S,), "accepted"), (energy_in, torch.float64, (S, 4), "energy_in"),
-            (energy_out, torch.float64, (S, 4), "energy_out"), (history, torch.float64, (iterations + 1, S), "history"),
-            (grad, torch.float64, (S, n, 3), "grad")]
-    for t, dt, shape, what in want:
-        if t is None:
-            if what in ("self_pairs", "history", "grad") or (what in ("bonds", "mask_rotate") and T == 0):
-                continue
-            raise L.DdpError(f"pose_minimize {what}: missing")
-        _eval_arg(t, dt, dev, f"pose_minimize {what}")
-        if shape is not None and tuple(t.shape) != shape:
-            raise L.DdpError(f"pose_minimize {what}: expected {shape}, got {tuple(t.shape)}")
-    c = config
-    a = L.MinimizeArgs(n_samples=S, n=n, m=m, rec_stride=3 * m if rec.dim() == 3 else 0, n_tor=T, iterations=iterations,
-                       cutoff=float(c.cutoff), gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width),
-                       hydrophobic_good=float(c.hydrophobic_good), hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good),
-                       hbond_bad=float(c.hbond_bad), w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion),
-                       w_hydrophobic=float(c.w_hydrophobic), w_hbond=float(c.w_hbond), restraint=float(restraint), grow=float(grow),
-                       shrink=float(shrink), step_max=float(step_max))
-    for name, t in (("pos", pos), ("anchor", anchor), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_radii", rec_radii),
-                    ("rec_flags", rec_flags), ("self_pairs", self_pairs), ("bonds", bonds), ("mask_rotate", mask_rotate), ("step", step),
-                    ("accepted", accepted), ("energy_in", energy_in), ("energy_out", energy_out), ("history", history), ("grad", grad)):
-        setattr(a, name, _p(t) or None)
-    L.check(L.load().ddp_pose_minimize(C.byref(a), stream()), "ddp_pose_minimize")
+    _minimize("pose_minimize", L.MinimizeArgs, 4, pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds,
+              mask_rotate, step, accepted, energy_in, energy_out, iterations, restraint, grow, shrink, step_max, history, grad)
 
 
 # ------------------------------------------------------------------------------------------------ joint minimiser (csrc/ddp_minimize_flex.hip)
@@ -948,50 +923,18 @@ def pose_minimize_flex(pos, anchor, lig_radii, lig_flags, rec, rec_anchor, rec_r
     pose_minimize, with: rec (in/out) and rec_anchor [S, m, 3] fp32, one receptor per sample; tables: what flex_tables returns (its
     values are not looked at here); energy_in, energy_out [S, 6]; grad_mov [S, n_mov, 3] fp64 or None.  Shapes and dtypes are checked
     here; no device tensor is downloaded."""
-    dev = pos.device
-    _eval_arg(pos, torch.float32, dev, "pose_minimize_flex pos")
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise L.DdpError("pose_minimize_flex: pos [S, n, 3]")
-    S, n = pos.shape[0], pos.shape[1]
-    if rec.dim() != 3 or rec.shape[-1] != 3 or rec.shape[0] != S:
-        raise L.DdpError("pose_minimize_flex: rec [S, m, 3], one receptor per sample")
-    m = rec.shape[1]
-    T = 0 if bonds is None else int(bonds.shape[0])
     mov, edge, sub, mapping, pairs = (tables[k] for k in ("mov", "edge_idx", "sub", "mapping", "pairs"))
     n_mov, n_sc, n_sub = int(mov.shape[0]), int(edge.shape[0]), int(sub.shape[0])
-    iterations = int(iterations)
-    if iterations < 0:
-        raise L.DdpError("pose_minimize_flex: iterations < 0")
-    want = [(anchor, torch.float32, (S, n, 3), "anchor"), (lig_radii, torch.float32, (n,), "lig_radii"), (lig_flags, torch.uint8, (n,), "lig_flags"),
-            (rec, torch.float32, (S, m, 3), "rec"), (rec_anchor, torch.float32, (S, m, 3), "rec_anchor"), (rec_radii, torch.float32, (m,), "rec_radii"),
-            (rec_flags, torch.uint8, (m,), "rec_flags"), (self_pairs, torch.uint8, (n, n), "self_pairs"), (bonds, torch.int32, (T, 2), "bonds"),
-            (mask_rotate, torch.uint8, (T, n), "mask_rotate"), (mov, torch.int32, (n_mov,), "mov"), (edge, torch.int32, (n_sc, 2), "edge_idx"),
-            (sub, torch.int32, (n_sub,), "sub"), (mapping, torch.int32, (n_sc, 2), "mapping"), (pairs, torch.uint8, (n_mov, m), "pairs"),
-            (step, torch.float64, (S,), "step"), (accepted, torch.int32, (S,), "accepted"), (energy_in, torch.float64, (S, 6), "energy_in"),
-            (energy_out, torch.float64, (S, 6), "energy_out"), (history, torch.float64, (iterations + 1, S), "history"),
-            (grad, torch.float64, (S, n, 3), "grad"), (grad_mov, torch.float64, (S, n_mov, 3), "grad_mov")]
-    for t, dt, shape, what in want:
-        if t is None:
-            if what in ("self_pairs", "history", "grad", "grad_mov") or (what in ("bonds", "mask_rotate") and T == 0):
-                continue
-            raise L.DdpError(f"pose_minimize_flex {what}: missing")
-        _eval_arg(t, dt, dev, f"pose_minimize_flex {what}")
-        if tuple(t.shape) != shape:
-            raise L.DdpError(f"pose_minimize_flex {what}: expected {shape}, got {tuple(t.shape)}")
-    c = config
-    a = L.MinimizeFlexArgs(n_samples=S, n=n, m=m, rec_stride=3 * m, n_tor=T, iterations=iterations, cutoff=float(c.cutoff),
-                           gauss_offset=float(c.gauss_offset), gauss_width=float(c.gauss_width), hydrophobic_good=float(c.hydrophobic_good),
-                           hydrophobic_bad=float(c.hydrophobic_bad), hbond_good=float(c.hbond_good), hbond_bad=float(c.hbond_bad),
-                           w_gauss=float(c.w_gauss), w_repulsion=float(c.w_repulsion), w_hydrophobic=float(c.w_hydrophobic),
-                           w_hbond=float(c.w_hbond), restraint=float(restraint), grow=float(grow), shrink=float(shrink),
-                           step_max=float(step_max), n_mov=n_mov, n_sc=n_sc, n_sub=n_sub, restraint_sc=float(restraint_sc))
-    for name, t in (("pos", pos), ("anchor", anchor), ("lig_radii", lig_radii), ("lig_flags", lig_flags), ("rec", rec), ("rec_anchor", rec_anchor),
-                    ("rec_radii", rec_radii), ("rec_flags", rec_flags), ("self_pairs", self_pairs), ("bonds", bonds), ("mask_rotate", mask_rotate),
-                    ("mov", mov), ("sc_edge_idx", edge), ("sc_sub", sub), ("sc_map", mapping), ("sc_pairs", pairs), ("step", step),
-                    ("accepted", accepted), ("energy_in", energy_in), ("energy_out", energy_out), ("history", history), ("grad", grad),
-                    ("grad_mov", grad_mov)):
-        setattr(a, name, _p(t) or None)
-    L.check(L.load().ddp_pose_minimize_flex(C.byref(a), stream()), "ddp_pose_minimize_flex")
+
+    def side(S, m):
+        i32 = torch.int32
+        rows = [(rec_anchor, torch.float32, (S, m, 3), "rec_anchor"), (mov, i32, (n_mov,), "mov"), (edge, i32, (n_sc, 2), "sc_edge_idx"),
+                (sub, i32, (n_sub,), "sc_sub"), (mapping, i32, (n_sc, 2), "sc_map"), (pairs, torch.uint8, (n_mov, m), "sc_pairs"),
+                (grad_mov, torch.float64, (S, n_mov, 3), "grad_mov")]
+        return rows, ("grad_mov",), dict(n_mov=n_mov, n_sc=n_sc, n_sub=n_sub, restraint_sc=float(restraint_sc))
+
+    _minimize("pose_minimize_flex", L.MinimizeFlexArgs, 6, pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs,
+              bonds, mask_rotate, step, accepted, energy_in, energy_out, iterations, restraint, grow, shrink, step_max, history, grad, side)
 
 
 # ------------------------------------------------------------------------------------------------ pocket finder (csrc/ddp_pockets.hip)

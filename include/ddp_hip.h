@@ -835,29 +835,45 @@ int ddp_refine_energy(const ddp_refine_args_t* args, void* stream);
 int ddp_refine_direction(const ddp_refine_args_t* args, void* stream);
 int ddp_refine_accept(const ddp_refine_args_t* args, void* stream);
 
-/* ---- a Vinardo-form empirical score of sampled poses (csrc/ddp_score.hip; host side diffdock_pocket_amd/scoring.py, which states the
- * whole definition and the atom typing).  The functional form of Vinardo (Quiroga & Villarreal 2016); NOT validated against smina or
- * Vina.  n_samples poses of one complex, pos [n_samples][n][3] fp32; rec, m, rec_stride as ddp_pose_contacts (rec_stride 0: one receptor
- * [m][3] for all samples; >= 3 m: sample s reads rec + s rec_stride).  Every atom carries a radius (fp32; negative: untyped, the atom
- * takes part in nothing) and a flag byte (bit 0 hydrophobic, bit 1 hydrogen-bond donor, bit 2 acceptor).  self_pairs uint8 [n][n], upper
- * triangle (NULL: no ligand-ligand term).  All arithmetic is fp64 on the fp32 inputs.  For a typed pair with centre distance
- * d < cutoff (strict) and s = d - R_i - R_j:
+/* ---- the Vinardo-form pair score that ddp_pose_score, ddp_pose_profile, ddp_pose_minimize and ddp_pose_minimize_flex share: its
+ * definition and its eleven constants, stated here once.  The four argument structs embed the struct as their member `form`.  For a
+ * pair of typed atoms (radius >= 0) with centre distance d < cutoff (strict) and s = d - R_i - R_j, with the atoms' flag bytes (bit 0
+ * hydrophobic, bit 1 hydrogen-bond donor, bit 2 acceptor):
  *   gauss       = exp(-((s - gauss_offset) / gauss_width)^2)
  *   repulsion   = s^2 if s < 0, else 0
  *   hydrophobic = (both atoms hydrophobic)  1 if s <= hydrophobic_good, (hydrophobic_bad - s) / (hydrophobic_bad - hydrophobic_good) if
  *                 s < hydrophobic_bad, else 0
  *   hbond       = (one atom a donor, the other an acceptor)  the same ramp between hbond_good and hbond_bad
+ * and over a set of pairs
+ *   weighted sum = w_gauss sum gauss + w_repulsion sum repulsion + w_hydrophobic sum hydrophobic + w_hbond sum hbond
+ * (the weights carry their signs).  The ramps have their slope on the open interval only.  The constant checks of every entry that
+ * takes a form, DDP_EINVAL without a launch: cutoff <= 0 or not finite, gauss_width <= 0, a ramp without good < bad. */
+typedef struct {
+  double cutoff;
+  double gauss_offset, gauss_width;
+  double hydrophobic_good, hydrophobic_bad;
+  double hbond_good, hbond_bad;
+  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+} ddp_score_form_t;
+
+/* ---- a Vinardo-form empirical score of sampled poses (csrc/ddp_score.hip; host side diffdock_pocket_amd/scoring.py, which states the
+ * whole definition and the atom typing).  The functional form of Vinardo (Quiroga & Villarreal 2016); NOT validated against smina or
+ * Vina.  n_samples poses of one complex, pos [n_samples][n][3] fp32; rec, m, rec_stride as ddp_pose_contacts (rec_stride 0: one receptor
+ * [m][3] for all samples; >= 3 m: sample s reads rec + s rec_stride).  Every atom carries a radius (fp32; negative: untyped, the atom
+ * takes part in nothing) and a flag byte (bit 0 hydrophobic, bit 1 hydrogen-bond donor, bit 2 acceptor).  self_pairs uint8 [n][n], upper
+ * triangle (NULL: no ligand-ligand term).  All arithmetic is fp64 on the fp32 inputs.  The pair terms and the weighted sum are those of
+ * ddp_score_form_t above, with the constants of `form`.
  * energy[s] = [sum gauss, sum repulsion, sum hydrophobic, sum hbond (ligand-receptor pairs, unweighted), inter, intra, total]:
- *   inter = w_gauss sum gauss + w_repulsion sum repulsion + w_hydrophobic sum hydrophobic + w_hbond sum hbond (the weights carry their
- *   signs), intra = the same weighted sum over the pairs of self_pairs, total = inter / tor_divisor (intra is not part of it).
+ *   inter = the weighted sum over the ligand-receptor pairs, intra = the weighted sum over the pairs of self_pairs, total = inter /
+ *   tor_divisor (intra is not part of it).
  * grad[s][i] = d(inter + intra)/dx_i (NULL: not computed; the energies are the same bits either way), not divided by tor_divisor.  The
  * ramps have their slope on the open interval only; a pair with d = 0 adds its energy and no gradient; the gradient of an untyped
  * atom is 0.  A NaN coordinate of a typed atom gives NaN energies for that sample only.
  * One workgroup per sample, the ligand staged in LDS (n > DDP_EVAL_MAX_ATOMS: DDP_ELIMIT), the receptor streamed through an LDS tile,
  * every sum in a fixed order, no atomics: two launches give the same bits, and a sample's result does not depend on the other samples
  * of the launch.  n_samples = 0: no-op; m = 0: zeros for the ligand-receptor terms.  DDP_EINVAL without a launch: a NULL struct, pos,
- * lig_radii, lig_flags or energy (m > 0: rec, rec_radii, rec_flags), n_samples < 0, n <= 0, m < 0, 0 < rec_stride < 3 m, cutoff <= 0 or
- * not finite, gauss_width <= 0, tor_divisor <= 0, a ramp without good < bad. */
+ * lig_radii, lig_flags or energy (m > 0: rec, rec_radii, rec_flags), n_samples < 0, n <= 0, m < 0, 0 < rec_stride < 3 m, tor_divisor <= 0,
+ * and the constant checks of ddp_score_form_t. */
 typedef struct {
   int32_t n_samples, n, m, rec_stride;
   const float* pos;             /* [n_samples][n][3] */
@@ -867,11 +883,7 @@ typedef struct {
   const float* rec_radii;       /* [m] */
   const uint8_t* rec_flags;     /* [m] */
   const uint8_t* self_pairs;
-  double cutoff;
-  double gauss_offset, gauss_width;
-  double hydrophobic_good, hydrophobic_bad;
-  double hbond_good, hbond_bad;
-  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  ddp_score_form_t form;        /* the constants of the score form */
   double tor_divisor;
   double* energy;               /* [n_samples][7] */
   double* grad;                 /* [n_samples][n][3] */
@@ -896,7 +908,7 @@ int ddp_pose_score(const ddp_score_args_t* args, void* stream);
  * depend on the other samples of the launch.  rec_stride as in ddp_score_args_t.  n_samples = 0 or n_res = 0: no-op.  DDP_EINVAL
  * without a launch: a NULL struct, pos, lig_radii, lig_flags, res_ptr, profile or bits (m > 0: rec, rec_radii, rec_flags),
  * n_samples < 0, n <= 0, m < 0, n_res < 0, 0 < rec_stride < 3 m, contact_distance <= 0 or not finite, and the constant checks of
- * ddp_pose_score. */
+ * ddp_score_form_t. */
 typedef struct {
   int32_t n_samples, n, m, rec_stride, n_res, reserved;
   const float* pos;             /* [n_samples][n][3] */
@@ -906,11 +918,7 @@ typedef struct {
   const float* rec_radii;       /* [m] */
   const uint8_t* rec_flags;     /* [m] */
   const int32_t* res_ptr;       /* [n_res + 1] */
-  double cutoff;
-  double gauss_offset, gauss_width;
-  double hydrophobic_good, hydrophobic_bad;
-  double hbond_good, hbond_bad;
-  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  ddp_score_form_t form;        /* the constants of the score form */
   double contact_distance;
   double* profile;              /* [n_samples][n_res][7] */
   uint8_t* bits;                /* [n_samples][n_res] */
@@ -938,7 +946,7 @@ int ddp_pose_profile(const ddp_profile_args_t* args, void* stream);
  * n_samples = 0: no-op.  iterations = 0: energy_in = energy_out, history[0] and grad are written, pos, step and accepted are not.
  * DDP_EINVAL without a launch: a NULL struct or required pointer (pos, anchor, lig_radii, lig_flags, step, accepted, energy_in,
  * energy_out; m > 0: rec, rec_radii, rec_flags; n_tor > 0: bonds, mask_rotate), n_samples < 0, n <= 0, m < 0, n_tor < 0, 0 < rec_stride
- * < 3 m, iterations < 0, restraint < 0 (or NaN), and the constant checks of ddp_pose_score.  DDP_ELIMIT: n > DDP_MINIMIZE_MAX_ATOMS
+ * < 3 m, iterations < 0, restraint < 0 (or NaN), and the constant checks of ddp_score_form_t.  DDP_ELIMIT: n > DDP_MINIMIZE_MAX_ATOMS
  * (the LDS plan is 17.9 KiB + 89 n bytes: 62.4 KiB at the limit), n_tor > DDP_MINIMIZE_MAX_TORSIONS. */
 #define DDP_MINIMIZE_MAX_ATOMS 512
 #define DDP_MINIMIZE_MAX_TORSIONS 4096
@@ -954,11 +962,7 @@ typedef struct {
   const uint8_t* self_pairs;
   const int32_t* bonds;         /* [n_tor][2] */
   const uint8_t* mask_rotate;   /* [n_tor][n] */
-  double cutoff;
-  double gauss_offset, gauss_width;
-  double hydrophobic_good, hydrophobic_bad;
-  double hbond_good, hbond_bad;
-  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  ddp_score_form_t form;        /* the constants of the score form */
   double restraint, grow, shrink, step_max;
   double* step;                 /* [n_samples], in/out */
   int32_t* accepted;            /* [n_samples], in/out */
@@ -1020,11 +1024,7 @@ typedef struct {
   const uint8_t* self_pairs;
   const int32_t* bonds;         /* [n_tor][2] */
   const uint8_t* mask_rotate;   /* [n_tor][n] */
-  double cutoff;
-  double gauss_offset, gauss_width;
-  double hydrophobic_good, hydrophobic_bad;
-  double hbond_good, hbond_bad;
-  double w_gauss, w_repulsion, w_hydrophobic, w_hbond;
+  ddp_score_form_t form;        /* the constants of the score form */
   double restraint, grow, shrink, step_max;
   double* step;                 /* [n_samples], in/out */
   int32_t* accepted;            /* [n_samples], in/out */

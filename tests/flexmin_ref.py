@@ -29,7 +29,7 @@ def sc_pair_list(mov, sc_pairs, rec_r):
     return out
 
 
-def energy(x, y, x0, y0, lig_r, lig_f, rec_r, rec_f, pairs, mov, sc_pairs, k=0.0, k_sc=0.0):
+def energy(x, y, x0, y0, lig_r, lig_f, rec_r, rec_f, pairs, mov, sc_pairs, k=0.0, k_sc=0.0, c=None):
     """x, x0 [S, n, 3], y, y0 [S, m, 3] (any float type: converted to fp64 first).  Returns a dict:
       energy [S, 6] = inter, intra, sc, ligand restraint term, side-chain restraint term, E
       grad_x [S, n, 3], grad_y [S, n_mov, 3]
@@ -37,14 +37,16 @@ def energy(x, y, x0, y0, lig_r, lig_f, rec_r, rec_f, pairs, mov, sc_pairs, k=0.0
         weighted pair terms for inter, intra and sc; 3 n and 3 n_mov squares for the restraints; E: the sums of the others)
       n_pairs_gx [S], max_gx [S], n_pairs_gy [S], max_gy [S]: summands of a gradient component (pairs inside the cutoff that touch
         the molecule, + 1 for the restraint) and the largest of them
-      cutoff_gap: min over all pairs met, cross, self or sc, of |d - cutoff|."""
+      cutoff_gap: min over all pairs met, cross, self or sc, of |d - cutoff|.
+    c: a vinardo_ref.Constants (None: the defaults)."""
+    c = c or V.DEFAULT
     x, y, x0, y0 = (np.asarray(a, dtype=np.float64) for a in (x, y, x0, y0))
     S, n = x.shape[:2]
     mov = np.asarray(mov, dtype=np.int64).reshape(-1)
     n_mov = len(mov)
     rec_r64 = np.asarray(rec_r, dtype=np.float64)
     rec_f64 = np.asarray(rec_f).astype(np.int64)
-    ref = V.score(x, lig_r, lig_f, y, rec_r, rec_f, pairs, 1.0)
+    ref = V.score(x, lig_r, lig_f, y, rec_r, rec_f, pairs, 1.0, c)
     out = {"energy": np.zeros((S, 6)), "grad_x": ref["grad"].copy(), "grad_y": np.zeros((S, n_mov, 3)), "n_pairs": np.zeros((S, 6)),
            "max_term": np.zeros((S, 6)), "n_pairs_gx": ref["n_pairs_grad"] + 1.0, "max_gx": ref["max_grad"].copy(),
            "n_pairs_gy": np.zeros(S), "max_gy": np.zeros(S), "cutoff_gap": ref["cutoff_gap"]}
@@ -62,7 +64,7 @@ def energy(x, y, x0, y0, lig_r, lig_f, rec_r, rec_f, pairs, mov, sc_pairs, k=0.0
         ia = np.array([(r, a, i) for r, a in enumerate(mov.tolist()) if rec_r64[a] >= 0 for i in range(n) if lig_r64[i] >= 0],
                       dtype=np.int64).reshape(-1, 3)
         if len(ia):
-            inside, _, pg, _ = V.pair_terms(y[s, ia[:, 1]] - x[s, ia[:, 2]], rec_r64[ia[:, 1]] + lig_r64[ia[:, 2]], rec_f64[ia[:, 1]], lig_f64[ia[:, 2]])
+            inside, _, pg, _ = V.pair_terms(y[s, ia[:, 1]] - x[s, ia[:, 2]], rec_r64[ia[:, 1]] + lig_r64[ia[:, 2]], rec_f64[ia[:, 1]], lig_f64[ia[:, 2]], c)
             np.add.at(gy, ia[:, 0], pg)
             n_gy += int(inside.sum())
             max_gy = max(max_gy, float(np.sqrt((pg ** 2).sum(-1)).max()))
@@ -70,16 +72,16 @@ def energy(x, y, x0, y0, lig_r, lig_f, rec_r, rec_f, pairs, mov, sc_pairs, k=0.0
         t_sum, n_sc_pairs, max_w = np.zeros(4), 0, 0.0
         if plist:
             pa, pb = np.array(plist, dtype=np.int64).T
-            inside, t, pg, d = V.pair_terms(y[s, pa] - y[s, pb], rec_r64[pa] + rec_r64[pb], rec_f64[pa], rec_f64[pb])
+            inside, t, pg, d = V.pair_terms(y[s, pa] - y[s, pb], rec_r64[pa] + rec_r64[pb], rec_f64[pa], rec_f64[pb], c)
             if np.isfinite(d).any():
-                out["cutoff_gap"] = min(out["cutoff_gap"], float(np.nanmin(np.abs(d - V.CUTOFF))))
-            t_sum, n_sc_pairs, max_w = t.sum(0), int(inside.sum()), float(np.abs(t @ V.WEIGHTS).max())
+                out["cutoff_gap"] = min(out["cutoff_gap"], float(np.nanmin(np.abs(d - c.cutoff))))
+            t_sum, n_sc_pairs, max_w = t.sum(0), int(inside.sum()), float(np.abs(t @ V.weights(c)).max())
             np.add.at(gy, np.array([slot[int(a)] for a in pa]), pg)
             second = np.array([slot.get(int(b), -1) for b in pb])
             np.add.at(gy, second[second >= 0], -pg[second >= 0])
             n_gy += n_sc_pairs
             max_gy = max(max_gy, float(np.sqrt((pg ** 2).sum(-1)).max()))
-        e[2] = V.WEIGHTS @ t_sum
+        e[2] = V.weights(c) @ t_sum
         out["n_pairs"][s, 2], out["max_term"][s, 2] = n_sc_pairs, max_w
         # restraints
         dx = x[s] - x0[s]
@@ -127,18 +129,19 @@ def apply_sidechains(y, edge, sub, mapping, angles):
     return y
 
 
-def random_case(S, n, m, n_mov, n_sc, seed, with_pairs=True, untyped_moving=False, moving_at=None, kink_gap=0.0):
+def random_case(S, n, m, n_mov, n_sc, seed, with_pairs=True, untyped_moving=False, moving_at=None, kink_gap=0.0, c=None):
     """vinardo_ref.random_case with per-sample receptors, plus random side-chain tables: mov (sorted; `moving_at`: these receptor indices
     are among them; untyped_moving: the first moving atom is untyped, otherwise every moving atom is typed), n_sc bonds (u, v: two
     receptor atoms outside the bond's subcomponent, which is a random non-empty subset of mov), sc_pairs [n_mov, m] (random, symmetric
     among the moving atoms, never an atom with itself).  Start state x0, y0: the state plus noise (y0 differs on the moving atoms only).
     Redrawn until no pair, cross, self or sc, lies within 1e-6 A of the cutoff and, with kink_gap > 0, no pair inside the cutoff has
     its surface distance s within kink_gap of a kink of the ramps (0, 2.5, -0.6).  Returns a dict of fp32 / integer NumPy arrays and
-    `ref`, the restatement's result with k = 0.7, k_sc = 0.3 (the keys `k`, `k_sc`)."""
+    `ref`, the restatement's result with k = 0.7, k_sc = 0.3 (the keys `k`, `k_sc`).  c: the constants of the reference, the cutoff and
+    the kinks (None: the defaults, to which the numbers above belong)."""
     assert n_mov <= m and (n_sc == 0 or (n_mov >= 1 and m >= 3))
     for t in range(256):
         sd = seed + 7919 * t
-        x, lig_r, lig_f, y, rec_r, rec_f, pairs, _ = V.random_case(S, n, m, sd, True, with_pairs)
+        x, lig_r, lig_f, y, rec_r, rec_f, pairs, _ = V.random_case(S, n, m, sd, True, with_pairs, c)
         rng = np.random.default_rng(sd + 1)
         fixed = sorted(set(moving_at or []))
         rest = [a for a in rng.permutation(m).tolist() if a not in fixed][:n_mov - len(fixed)]
@@ -170,28 +173,31 @@ def random_case(S, n, m, n_mov, n_sc, seed, with_pairs=True, untyped_moving=Fals
         case = {"x": x, "y": y, "x0": x0, "y0": y0, "lig_r": lig_r, "lig_f": lig_f, "rec_r": rec_r, "rec_f": rec_f, "pairs": pairs, "mov": mov,
                 "edge": np.array(edge, dtype=np.int64).reshape(-1, 2), "sub": np.array(sub, dtype=np.int64),
                 "mapping": np.array(mapping, dtype=np.int64).reshape(-1, 2), "sc_pairs": sc_pairs, "k": 0.7, "k_sc": 0.3}
-        ref = energy(x, y, x0, y0, lig_r, lig_f, rec_r, rec_f, pairs, mov, sc_pairs, 0.7, 0.3)
+        ref = energy(x, y, x0, y0, lig_r, lig_f, rec_r, rec_f, pairs, mov, sc_pairs, 0.7, 0.3, c)
         if ref["cutoff_gap"] < 1e-6:
             continue
-        if kink_gap > 0 and kink_distance(case) < kink_gap:
+        if kink_gap > 0 and kink_distance(case, c) < kink_gap:
             continue
         case["ref"] = ref
         return case
     raise AssertionError("no draw clear of the cutoff and the kinks")
 
 
-def kink_distance(case):
+def kink_distance(case, c=None):
     """min over all typed pairs of the case inside cutoff + 0.1 of the distance of s = d - R_a - R_b to a kink of the ramps and of the
-    repulsion (0, 2.5, -0.6) and of d to the cutoff: how far a finite-difference step may reach."""
+    repulsion (0, 2.5, -0.6) and of d to the cutoff: how far a finite-difference step may reach.  c: a vinardo_ref.Constants (None: the
+    defaults, to which the numbers above belong): the kinks are 0 and the four ends of its ramps."""
+    c = c or V.DEFAULT
+    kinks = (0.0, c.hydrophobic_good, c.hydrophobic_bad, c.hbond_good, c.hbond_bad)
     x, y = case["x"].astype(np.float64), case["y"].astype(np.float64)
     lig_r, rec_r = case["lig_r"].astype(np.float64), case["rec_r"].astype(np.float64)
     worst = np.inf
 
     def visit(d, rsum):
         nonlocal worst
-        if d < V.CUTOFF + 0.1:
+        if d < c.cutoff + 0.1:
             s = d - rsum
-            worst = min(worst, abs(s), abs(s - V.HYDROPHOBIC_BAD), abs(s - V.HBOND_GOOD), abs(d - V.CUTOFF))
+            worst = min(worst, abs(d - c.cutoff), *(abs(s - k) for k in kinks))
 
     for s in range(x.shape[0]):
         for i in np.nonzero(lig_r >= 0)[0]:

@@ -11,13 +11,12 @@ typed pair to one of the thresholds) is returned with the result.
     of the sample; a poisoned entry: terms, energy, d_min NaN, pairs 0, bits 0"""
 import numpy as np
 
-from vinardo_ref import CUTOFF, EPS, HYDROPHOBIC_BAD, RADII, WEIGHTS, pair_terms
+from vinardo_ref import DEFAULT, EPS, RADII, pair_terms, weights
 
 CONTACT_DISTANCE = 4.5
-HBOND_BAD = 0.0
 
 
-def profile(x, lig_r, lig_f, rec, rec_r, rec_f, res_ptr, contact_distance=CONTACT_DISTANCE):
+def profile(x, lig_r, lig_f, rec, rec_r, rec_f, res_ptr, contact_distance=CONTACT_DISTANCE, c=None):
     """x [S, n, 3], rec [m, 3] or [S, m, 3] (any float type: converted to fp64 first), radii (negative: untyped), uint8 flags, res_ptr
     [R + 1].  Returns a dict:
       terms [S, R, 4], energy [S, R], d_min [S, R], pairs [S, R] (int64), bits [S, R] (uint8)
@@ -25,7 +24,11 @@ def profile(x, lig_r, lig_f, rec, rec_r, rec_f, res_ptr, contact_distance=CONTAC
       grad_l1 [S, R]: the sum over the entry's pairs of the 1-norm of the pair energy's gradient: what a unit shift of every coordinate
       can move `energy` by, to first order
       gap [S]: per sample, the smallest of |d - cutoff|, |d - contact_distance| over all typed pairs, |s - 2.5| over the hydrophobic
-      pairs and |s - 0| over the donor-acceptor pairs (the thresholds are the only discontinuities); threshold_gap: its minimum."""
+      pairs and |s - 0| over the donor-acceptor pairs (the thresholds are the only discontinuities); threshold_gap: its minimum.
+    c: a vinardo_ref.Constants (None: the defaults, to which the numbers above belong; the thresholds follow c: cutoff,
+    hydrophobic_bad, hbond_bad)."""
+    c = c or DEFAULT
+    WEIGHTS, CUTOFF, HYDROPHOBIC_BAD, HBOND_BAD = weights(c), c.cutoff, c.hydrophobic_bad, c.hbond_bad
     x = np.asarray(x, dtype=np.float64)
     S = x.shape[0]
     rec = np.asarray(rec, dtype=np.float64)
@@ -48,7 +51,7 @@ def profile(x, lig_r, lig_f, rec, rec_r, rec_f, res_ptr, contact_distance=CONTAC
             ci, cj = (a.reshape(-1) for a in np.meshgrid(li, rj, indexing="ij"))
             if len(ci) == 0:
                 continue
-            inside, t, pg, d = pair_terms(x[s, ci] - r[cj], lig_r[ci] + rec_r[cj], lig_f[ci], rec_f[cj])
+            inside, t, pg, d = pair_terms(x[s, ci] - r[cj], lig_r[ci] + rec_r[cj], lig_f[ci], rec_f[cj], c)
             out["terms"][s, k] = t.sum(0)
             out["energy"][s, k] = WEIGHTS @ out["terms"][s, k]
             out["pairs"][s, k] = inside.sum()
@@ -108,13 +111,15 @@ def check(got_terms, got_energy, got_d_min, got_pairs, got_bits, ref, what="", b
         assert np.array_equal(gb[bits_where], ref["bits"][bits_where]), what
 
 
-def random_case(S, n, sizes, seed, per_sample_rec=False, untyped_residue=None, ligand_untyped=False, contact_distance=CONTACT_DISTANCE):
+def random_case(S, n, sizes, seed, per_sample_rec=False, untyped_residue=None, ligand_untyped=False, contact_distance=CONTACT_DISTANCE,
+                c=None):
     """Random poses and a receptor of residues with the given sizes (atoms per residue, zeros allowed), drawn as
     vinardo_ref.random_case draws them: a box crowded enough that pairs overlap, sit on the ramps and lie outside the cutoff; radii from
     the table with untyped atoms (-1) among them; every flag combination 0 .. 7.  With two or more atoms on a side, one of them is
     made untyped whatever the draw gave (the last ligand atom, the first receptor atom); untyped_residue: that residue's atoms are all
     untyped; ligand_untyped: every ligand atom is.  Redrawn (seed + 7919 k) until no typed pair lies within 1e-6 of a threshold;
-    raises after 64 draws.  fp32 inputs as the package takes them; returns (x, lig_r, lig_f, rec, rec_r, rec_f, res_ptr, ref)."""
+    raises after 64 draws.  fp32 inputs as the package takes them; returns (x, lig_r, lig_f, rec, rec_r, rec_f, res_ptr, ref).  c: the
+    constants of that reference (None: the defaults)."""
     table = np.array(list(RADII.values()) + [-1.0, -1.0], dtype=np.float32)
     sizes = np.asarray(sizes, dtype=np.int64)
     m = int(sizes.sum())
@@ -134,7 +139,7 @@ def random_case(S, n, sizes, seed, per_sample_rec=False, untyped_residue=None, l
             rec_r[ptr[untyped_residue]:ptr[untyped_residue + 1]] = -1.0
         if ligand_untyped:
             lig_r[:] = -1.0
-        ref = profile(x, lig_r, lig_f, rec, rec_r, rec_f, ptr, contact_distance)
+        ref = profile(x, lig_r, lig_f, rec, rec_r, rec_f, ptr, contact_distance, c)
         if ref["threshold_gap"] >= 1e-6:
             return x, lig_r, lig_f, rec, rec_r, rec_f, ptr, ref
     raise AssertionError("no draw clear of the thresholds")

@@ -1,7 +1,9 @@
-"""python tools/descent_bits.py [out.json]  (needs an MI355X; profiles/descent_bits.json)
-SHA-256 of every output tensor's bytes of the entries that share csrc/ddp_pose_descent.h and csrc/ddp_horn.h, on seeded inputs only:
-the 3dpf fixture of tests/golden and synthetic ragged shapes.  Run once per library (DDP_HIP_LIB selects one) in a fresh process; two
-libraries compute the same bits iff their digest lists are equal."""
+"""python tools/descent_bits.py [out.json]  (needs an MI355X; profiles/descent_bits.json and profiles/pose_family_bits.json, DESIGN.md
+4.16 and 4.23)
+SHA-256 of every output tensor's bytes of the entries that share csrc/ddp_pose_descent.h and csrc/ddp_horn.h, and of the rest of the
+pose family (ddp_pose_profile, ddp_pose_minimize_flex, ddp_clash_guidance), on seeded inputs only: the 3dpf fixture of tests/golden,
+synthetic ragged shapes and the small cases of tests/pose_form_cases.py at the default and at a non-default score form.  Run once per
+library (DDP_HIP_LIB selects one) in a fresh process; two libraries compute the same bits iff their digest lists are equal."""
 import hashlib
 import json
 import os
@@ -11,7 +13,9 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import pose_form_cases as P       # NumPy only: the seeded inputs of tests/test_gpu_pose_form.py
+from diffdock_pocket_amd import guidance as G
 from diffdock_pocket_amd import inputs as I
 from diffdock_pocket_amd import launch as LA
 from diffdock_pocket_amd import minimize as M
@@ -77,6 +81,44 @@ for S, n, m, T, per_sample in ((3, 1, 0, 0, False), (3, 5, 1, 1, False), (2, 37,
                                  c["bonds"][:Tm].contiguous() if Tm else None, c["mask"][:Tm].contiguous() if Tm else None, step, acc, e0, e1,
                                  iterations, restraint=k, history=h, grad=gm)
                 put(f"pose_minimize {tag} it={iterations} T={Tm} k={k}", x, step, acc, e0, e1, h, gm)
+
+# ---- the rest of the pose family, at the default form and at the non-default one of the tests
+forms = {"default": SC.ScoreConfig(), "form": SC.ScoreConfig(**P.FORM)}
+dv = lambda a: None if a is None else torch.from_numpy(np.asarray(a)).to(dev)
+# ddp_pose_profile: residues of 0, 1, 12 and 65 atoms, a ligand inside one wave's lanes and one beyond them
+for n in (37, 70):
+    x, lig_r, lig_f, rec, rec_r, rec_f, ptr = (dv(a) for a in P.profile_case(n)[:7])
+    for tag, cfg in forms.items():
+        put(f"pose_profile n{n} {tag}", *LA.pose_profile(x, lig_r, lig_f, rec, rec_r, rec_f, ptr, cfg, 4.5))
+# ddp_pose_minimize_flex: S = 2, n = 37, m = 70, 9 moving atoms, 3 side-chain bonds
+fc = P.flex_case()
+ft = {k: dv(fc[k]) for k in ("x", "y", "x0", "y0", "lig_r", "lig_f", "rec_r", "rec_f", "pairs")}
+
+
+class _Tables:
+    mov, pairs, edge_idx, mapping, sub = (torch.from_numpy(fc[k]) for k in ("mov", "sc_pairs", "edge", "mapping", "sub"))
+
+
+tables = LA.flex_tables(_Tables, fc["y"].shape[1], dev)
+for tag, cfg in forms.items():
+    for iterations in (0, 1, 12):
+        S, n = fc["x"].shape[:2]
+        x, y, step, acc = ft["x"].clone(), ft["y"].clone(), torch.ones(S, **f64), torch.zeros(S, dtype=torch.int32, device=dev)
+        e0, e1, h = torch.empty(S, 6, **f64), torch.empty(S, 6, **f64), torch.empty(iterations + 1, S, **f64)
+        gx, gy = torch.empty(S, n, 3, **f64), torch.empty(S, len(fc["mov"]), 3, **f64)
+        LA.pose_minimize_flex(x, ft["x0"], ft["lig_r"], ft["lig_f"], y, ft["y0"], ft["rec_r"], ft["rec_f"], cfg, ft["pairs"], None, None, tables,
+                              step, acc, e0, e1, iterations, restraint=fc["k"], restraint_sc=fc["k_sc"], history=h, grad=gx, grad_mov=gy)
+        put(f"pose_minimize_flex {tag} it={iterations}", x, y, step, acc, e0, e1, h, gx, gy)
+# ddp_clash_guidance (no score form: the shared host checks only): S = 2, n = 37, m = 1025, 5 torsions, shared and per-sample receptor
+c = synthetic(2, 37, 1025, 5, 2087, True)
+gt = G.GuidanceTables(c["lig_r"].abs().cpu(), c["rec"][0].cpu(), c["rec_r"].cpu(), c["pairs"].cpu(), c["bonds"].cpu().long(), c["mask"].cpu().bool())
+ws = G.GuidanceWorkspace(gt, dev)
+weight = torch.tensor([0.75], dtype=torch.float32, device=dev)
+for rec in (None, c["rec"]):
+    upd = (torch.full((2, 3), 0.125, device=dev), torch.full((2, 3), -0.25, device=dev), torch.full((2, 5), 0.5, device=dev))
+    ge, gg = torch.empty(2, 2, **f64), torch.empty(2, 37, 3, **f64)
+    ws.launch(c["x"], rec, upd, weight, ge, gg)
+    put(f"clash_guidance per_sample={rec is not None}", *upd, ge, gg)
 
 # ddp_sidechain_update: two bonds, the second turning a subset of the first's atoms
 gen = torch.Generator().manual_seed(3)
