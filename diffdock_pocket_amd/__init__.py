@@ -7,7 +7,8 @@ from .diffusion import SigmaRanges, get_t_schedule, get_timestep_embedding, sinu
 __all__ = ["HeteroBatch", "Store", "collate", "set_time", "SigmaRanges", "get_t_schedule", "get_timestep_embedding",
            "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize", "PoseRefiner",
            "RefineConfig", "RefineResult", "PoseScorer", "ScoreConfig", "PoseScores", "PoseMinimizer", "MinimizeConfig",
-           "MinimizeResult", "FlexPoseMinimizer", "FlexMinimizeResult", "InteractionProfiler", "ProfileConfig", "InteractionProfile"]
+           "MinimizeResult", "FlexPoseMinimizer", "FlexMinimizeResult", "InteractionProfiler", "ProfileConfig", "InteractionProfile",
+           "PoseSearcher", "SearchConfig", "SearchResult"]
 
 
 def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ctypes binding
@@ -35,4 +36,7 @@ def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ct
     if name in ("InteractionProfiler", "ProfileConfig", "InteractionProfile"):
         from . import interactions
         return getattr(interactions, name)
+    if name in ("PoseSearcher", "SearchConfig", "SearchResult"):
+        from . import search
+        return getattr(search, name)
     raise AttributeError(name)

@@ -25,7 +25,7 @@ DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS, DDP_MINIMIZE_FLEX_MAX
 DDP_PAIRWISE_MAX_SAMPLES, DDP_CLUSTER_MAX_SAMPLES = 32768, 1024
 EXPORTS = ["ddp_conv_messages", "ddp_conv_rows", "ddp_stage_a_gh", "ddp_stage_a_gh3", "ddp_segment_reduce", "ddp_edge_featurize", "ddp_edge_featurize_jobs", "ddp_torsion_sh", "ddp_stage_a", "ddp_stage_a_h2",
            "ddp_pose_update", "ddp_sidechain_update", "ddp_sde_update", "ddp_radius_count", "ddp_radius_fill", "ddp_knn", "ddp_group_by_key", "ddp_node_linear", "ddp_scan_jobs", "ddp_mark_jobs", "ddp_rowcopy_jobs", "ddp_select_jobs",
-           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
+           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pose_search", "ddp_pose_search_select", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
 
 
 class Seg(C.Structure):
@@ -168,6 +168,19 @@ class MinimizeFlexArgs(C.Structure):
     _fields_ = MinimizeArgs._fields_ + [("rec_anchor", _P), ("n_mov", _I), ("n_sc", _I), ("n_sub", _I), ("reserved", _I), ("mov", _P),
                                         ("sc_edge_idx", _P), ("sc_sub", _P), ("sc_map", _P), ("sc_pairs", _P),
                                         ("restraint_sc", C.c_double), ("grad_mov", _P)]
+
+
+class SearchArgs(C.Structure):
+    """ddp_search_args_t of include/ddp_hip.h: a ddp_minimize_args_t (the score and the line search), then the chain's."""
+    _fields_ = [("min", MinimizeArgs), ("replicas", _I), ("cycles", _I), ("cycle0", _I), ("reserved", _I), ("step_init", C.c_double),
+                ("temperature", C.c_double), ("perturb", _P), ("u", _P), ("cur_pos", _P), ("cur_e", _P), ("best_pos", _P), ("best_e", _P),
+                ("best_cycle", _P), ("accepted", _P), ("trace", _P), ("flags", _P), ("starts", _P)]
+
+
+class SearchSelectArgs(C.Structure):
+    """ddp_search_select_args_t of include/ddp_hip.h."""
+    _fields_ = [("n_samples", _I), ("n", _I), ("replicas", _I), ("reserved", _I), ("best_pos", _P), ("best_e", _P), ("best_cycle", _P),
+                ("pos_out", _P), ("energy_out", _P), ("replica_out", _P), ("cycle_out", _P)]
 
 
 def flex_state_bytes(n: int, n_mov: int, n_sc: int) -> int:
@@ -351,6 +364,10 @@ def load():
     lib.ddp_pose_minimize.restype = C.c_int
     lib.ddp_pose_minimize_flex.argtypes = [C.POINTER(MinimizeFlexArgs), C.c_void_p]
     lib.ddp_pose_minimize_flex.restype = C.c_int
+    lib.ddp_pose_search.argtypes = [C.POINTER(SearchArgs), C.c_void_p]
+    lib.ddp_pose_search.restype = C.c_int
+    lib.ddp_pose_search_select.argtypes = [C.POINTER(SearchSelectArgs), C.c_void_p]
+    lib.ddp_pose_search_select.restype = C.c_int
     lib.ddp_pocket_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p]
     lib.ddp_pocket_occupancy.restype = C.c_int

@@ -103,7 +103,7 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m, n_mov = A.n_mov;
   const FxPatch patch = {L.mov, n_mov, ym};
   score_evaluate<true>(A, rs, L.tile, L.tflag, x, L.rad, L.lflag, g, L.we, patch);
-  // the ligand restraint, as mz_evaluate of ddp_minimize.hip
+  // the ligand restraint, as mz_evaluate of ddp_minimize_loop.h
   const double krest = 2.0 * A.restraint / (double)n;
   double er_w = 0.0;
   for (int i = wave; i < n; i += DDP_FX_WAVES) {

@@ -37,6 +37,7 @@ from .pockets import Pocket, PocketConfig, find_pockets as _find_pockets  # noqa
 from .interactions import InteractionProfile, InteractionProfiler, ProfileConfig, receptor_residues  # noqa: F401
 from .minimize import MinimizeConfig, MinimizeResult, PoseMinimizer  # noqa: F401
 from .minimize_flex import FlexMinimizeResult, FlexPoseMinimizer  # noqa: F401
+from .search import PoseSearcher, SearchConfig, SearchResult  # noqa: F401
 from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 from .scoring import PoseScorer, PoseScores, ScoreConfig, rank_order, typed_receptor  # noqa: F401
@@ -64,6 +65,8 @@ class ComplexResult:
     minimized: Optional["MinimizeResult"] = None   # run_csv(minimize_poses=cfg): minimize.MinimizeResult of the ranked poses (host tensors);
     #                                                a flexible row with cfg.sidechains: minimize_flex.FlexMinimizeResult
     minimized_pos: Optional[torch.Tensor] = None   # run_csv(minimize_poses=cfg): [N, n_lig, 3] the ranked poses after the minimisation
+    searched: Optional["SearchResult"] = None      # run_csv(search_poses=cfg): search.SearchResult of the ranked poses (host tensors)
+    searched_pos: Optional[torch.Tensor] = None    # run_csv(search_poses=cfg): [N, n_lig, 3] the ranked poses after the search
     interactions: Optional["InteractionProfile"] = None  # run_csv(interaction_profile=cfg): interactions.InteractionProfile of the ranked
     #                                                      poses (host tensors)
     interaction_reference: Optional["InteractionProfile"] = None  # interaction_profile with evaluate=True: the profile of the input pose
@@ -133,7 +136,8 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
             save_visualisation: bool = False, cluster_rmsd: Optional[float] = None,
             resolve_clashes: Optional[RefineConfig] = None, find_pockets: Optional[PocketConfig] = None,
             pockets_top_k: int = 1, score_poses: Optional[ScoreConfig] = None, rank_by: str = "confidence",
-            minimize_poses: Optional[MinimizeConfig] = None, interaction_profile: Optional[ProfileConfig] = None) -> List[ComplexResult]:
+            minimize_poses: Optional[MinimizeConfig] = None, interaction_profile: Optional[ProfileConfig] = None,
+            search_poses: Optional[SearchConfig] = None) -> List[ComplexResult]:
     """See the module docstring.  `dist`: an initialised torch.distributed module (world > 1 and shard == "samples").
     Returns one ComplexResult per csv row (on every rank; with shard == "complexes" only this rank's rows are filled).
 
@@ -207,9 +211,23 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     graph's.  evaluate=True: `interaction_reference` is the profile of the input ligand pose through the same profiler, and
     interaction_similarity.csv also says how similar every pose's bits are to it and how many of them the pose recovers.  It changes
     nothing else; a failure skips the row like a failure of the evaluation.  None: nothing is computed, allocated, launched or
-    written."""
-    if rank_by not in ("confidence", "score", "minimized_score"):
-        raise ValueError(f"rank_by: 'confidence', 'score' or 'minimized_score', got {rank_by!r}")
+    written.
+
+    search_poses=SearchConfig(...): the gathered poses, in sample order and right after the minimisation block, also go through
+    search.PoseSearcher: every pose seeds `replicas` chains of random move, local descent and Metropolis decision in the physics score
+    (score_poses' constants, else the default ScoreConfig), and the best minimum over the chains is the result - never worse in E than
+    the minimiser's with the same iteration count, but not Vina's search, without receptor or side-chain motion, and in a score that
+    is not validated against smina or Vina (search.py states what it is and is not).  `searched` (a SearchResult) and `searched_pos`
+    in ranked order; with out_dir also rank{k}_searched.sdf per pose and searched.csv (outputs.write_searched_csv).  The receptor is
+    the scoring's: the row's full typed PDB for rigid rows, each sample's own atom nodes for flexible rows.  It is independent of
+    minimize_poses and resolve_clashes: all of them start from the sampled poses.  rank_by="searched_score" (implies the search with the
+    default SearchConfig) orders the poses by ascending `scores_after.total` through scoring.rank_order, and everything downstream
+    follows that order.  None: nothing is computed, allocated, launched or written.  A failure skips the row like a failure of the
+    evaluation."""
+    if rank_by not in ("confidence", "score", "minimized_score", "searched_score"):
+        raise ValueError(f"rank_by: 'confidence', 'score', 'minimized_score' or 'searched_score', got {rank_by!r}")
+    if rank_by == "searched_score" and search_poses is None:
+        search_poses = SearchConfig()
     if rank_by == "score" and score_poses is None:
         score_poses = ScoreConfig()
     if rank_by == "minimized_score" and minimize_poses is None:
@@ -226,7 +244,7 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     dev = torch.device(device)
     args = (csv_path, model, dev, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank, world,
             shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate, out_dir, save_visualisation, cluster_rmsd, resolve_clashes,
-            find_pockets, pockets_top_k, score_poses, rank_by, minimize_poses, interaction_profile)
+            find_pockets, pockets_top_k, score_poses, rank_by, minimize_poses, interaction_profile, search_poses)
     if dev.type == "cuda":      # kernels are queued on the CURRENT device's stream: make `device` current for the whole run
         with torch.cuda.device(dev):
             return _run_csv(*args)
@@ -244,7 +262,7 @@ def _all_ok(dist, ok: bool, device) -> bool:
 def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inference_steps, esm_embeddings, root, seed, rank,
              world, shard, dist, sampler_cfg, graph_kwargs, allow_zero_esm, evaluate=False, out_dir=None,
              save_visualisation=False, cluster_rmsd=None, resolve_clashes=None, find_pockets=None, pockets_top_k=1, score_poses=None,
-             rank_by="confidence", minimize_poses=None, interaction_profile=None) -> List[ComplexResult]:
+             rank_by="confidence", minimize_poses=None, interaction_profile=None, search_poses=None) -> List[ComplexResult]:
     rows = load_protein_ligand_csv(csv_path)
     if find_pockets is not None:
         rows = expand_pocket_rows(rows, root, device, find_pockets, pockets_top_k)
@@ -290,7 +308,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             smp.run(schedule)
             lig = smp.lig_pos
             if ((evaluate or resolve_clashes is not None or score_poses is not None or minimize_poses is not None
-                 or interaction_profile is not None) and flex) or (out_dir is not None and moved):
+                 or interaction_profile is not None or search_poses is not None) and flex) or (out_dir is not None and moved):
                 apos = smp.atom_pos.clone()
             if save_visualisation:
                 ltraj = smp.lig_traj.clone()
@@ -342,8 +360,20 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 res.skipped = res.skipped or "skipped: minimisation failed on another rank"
             if res.skipped is not None:
                 continue
+        searched = None
+        if search_poses is not None:      # on the gathered poses, in sample order: the ranking below may depend on it
+            try:
+                searched = _search_row(row, root, g, device, flex, lig, apos, score_poses, search_poses)
+            except Exception as e:      # noqa: BLE001
+                res.skipped = f"search: {type(e).__name__}: {e}"
+            if split and not _all_ok(dist, searched is not None, device):
+                res.skipped = res.skipped or "skipped: the search failed on another rank"
+            if res.skipped is not None:
+                continue
         if rank_by == "score":
             order = rank_order(scores.total)
+        elif rank_by == "searched_score":
+            order = rank_order(searched.scores_after.total).to(lig.device)
         elif rank_by == "minimized_score":
             order = rank_order(minimized.scores_after.total).to(lig.device)
         elif conf is not None:      # reference inference.py:212-219: descending confidence (first column of a multi-output head)
@@ -360,6 +390,9 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
         if minimized is not None:
             res.minimized = minimized.index(order.cpu())
             res.minimized_pos = res.minimized.lig_pos
+        if searched is not None:
+            res.searched = searched.index(order.cpu())
+            res.searched_pos = res.searched.lig_pos
         if evaluate:
             metrics = None
             try:
@@ -369,7 +402,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, metrics is not None, device):
                 res.skipped = res.skipped or "skipped: evaluation failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.scores = res.minimized = res.minimized_pos = None
+                res.ligand_pos = res.confidence = res.order = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
                 continue
             res.metrics = metrics
         if cluster_rmsd is not None:
@@ -381,7 +414,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, clusters is not None, device):
                 res.skipped = res.skipped or "skipped: clustering failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.scores = res.minimized = res.minimized_pos = None
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
                 continue
             res.clusters = clusters
         if resolve_clashes is not None:
@@ -397,7 +430,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, refined is not None, device):
                 res.skipped = res.skipped or "skipped: clash relief failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = None
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
                 continue
             res.refine, res.refined_metrics = refined
             res.refined_pos = res.refine.lig_pos
@@ -412,7 +445,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if split and not _all_ok(dist, found is not None, device):
                 res.skipped = res.skipped or "skipped: the interaction profile failed on another rank"
             if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = None
+                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
                 res.refined_pos = res.refine = res.refined_metrics = res.refined_scores = None
                 continue
             res.interactions, res.interaction_reference = found
@@ -433,7 +466,7 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
             if not ok:
                 res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = res.clusters = None
                 res.refined_pos = res.refine = res.refined_metrics = res.scores = res.refined_scores = None
-                res.minimized = res.minimized_pos = res.interactions = res.interaction_reference = None
+                res.minimized = res.minimized_pos = res.searched = res.searched_pos = res.interactions = res.interaction_reference = None
                 res.files = []
     return out
 
@@ -476,7 +509,7 @@ def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) ->
                            apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order,
                            refine=res.refine, pockets=res.pockets, pockets_docked=row.get("pockets_docked", 0), scores=res.scores,
                            refined_scores=res.refined_scores, minimized=res.minimized, interactions=res.interactions,
-                           interaction_reference=res.interaction_reference)
+                           interaction_reference=res.interaction_reference, searched=res.searched)
 
 
 def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
@@ -540,6 +573,17 @@ def _minimize_row(row, root, g, device, flex, lig, apos, score_config, config) -
             rec = typed_receptor(f.read(), g.original_center)
         mz = PoseMinimizer(g, device, receptor=rec, score_config=score_config, config=config)
     return mz.minimize(lig, apos if flex else None).cpu()
+
+
+def _search_row(row, root, g, device, flex, lig, apos, score_config, config) -> SearchResult:
+    """SearchResult of the poses of one row in sample order (see run_csv), on the host.  The receptor is the one _scorer_row takes."""
+    if flex:
+        ps = PoseSearcher(g, device, score_config=score_config, config=config)
+    else:
+        with open(os.path.join(root, row["experimental_protein"])) as f:
+            rec = typed_receptor(f.read(), g.original_center)
+        ps = PoseSearcher(g, device, receptor=rec, score_config=score_config, config=config)
+    return ps.search(lig, apos if flex else None).cpu()
 
 
 def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
@@ -613,9 +657,10 @@ def _parser():
     p.add_argument("--score_poses", action="store_true", default=False,
                    help="score every pose with this package's Vinardo-form empirical function (not validated against smina or Vina) and "
                         "write scores.csv (default: off)")
-    p.add_argument("--rank_by", type=str, choices=("confidence", "score", "minimized_score"), default="confidence",
+    p.add_argument("--rank_by", type=str, choices=("confidence", "score", "minimized_score", "searched_score"), default="confidence",
                    help="order of the written poses: the confidence model's (without one: sample order), ascending physics score "
-                        "(implies --score_poses), or ascending physics score after the minimisation (implies --minimize_poses)")
+                        "(implies --score_poses), ascending physics score after the minimisation (implies --minimize_poses), or after the search (implies "
+                        "--search_poses)")
     p.add_argument("--minimize_poses", action="store_true", default=False,
                    help="minimise every pose locally in the physics score along translation, rotation and torsions (no receptor motion, "
                         "no global search) and write rank{k}_minimized.sdf and minimized.csv beside the unchanged poses (default: off)")
@@ -628,6 +673,17 @@ def _parser():
                         "minimized_sidechains.csv are written too; rigid rows are minimised as without the flag (default: off)")
     p.add_argument("--minimize_sidechain_restraint", type=float, default=MinimizeConfig.sidechain_restraint,
                    help="with --minimize_sidechains: weight of the restraint of the moving side-chain atoms to their sampled positions")
+    p.add_argument("--search_poses", action="store_true", default=False,
+                   help="search around every pose in the physics score: replicas of random move, local descent and Metropolis decision "
+                        "(not Vina's search, no receptor motion, a score not validated against smina or Vina); writes rank{k}_searched.sdf "
+                        "and searched.csv beside the unchanged poses (default: off)")
+    p.add_argument("--search_replicas", type=int, default=SearchConfig.replicas, help="with --search_poses: independent chains per pose")
+    p.add_argument("--search_cycles", type=int, default=SearchConfig.cycles, help="with --search_poses: cycles per chain")
+    p.add_argument("--search_iterations", type=int, default=SearchConfig.iterations,
+                   help="with --search_poses: line-search iterations of the local descent of one cycle")
+    p.add_argument("--search_temperature", type=float, default=SearchConfig.temperature,
+                   help="with --search_poses: temperature of the Metropolis rule, in units of the score")
+    p.add_argument("--search_seed", type=int, default=SearchConfig.seed, help="with --search_poses: seed of the random moves")
     p.add_argument("--interaction_profile", action="store_true", default=False,
                    help="say which residues every pose touches and how: the pair terms of the physics score summed per residue, with "
                         "contact / hydrophobic / hbond bits (not validated against PLIP or ProLIF); writes interactions.csv, "
@@ -694,6 +750,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--minimize_iterations and --minimize_restraint must not be negative")
     if not a.minimize_sidechain_restraint >= 0:
         ap.error("--minimize_sidechain_restraint must not be negative")
+    if a.search_replicas < 1 or a.search_cycles < 0 or a.search_iterations < 0 or not (0 < a.search_temperature < float("inf")):
+        ap.error("--search_replicas must be at least 1, --search_cycles and --search_iterations not negative, --search_temperature "
+                 "positive and finite")
     if a.pockets_top_k < 1 or not a.pocket_spacing > 0 or not 0 <= a.pocket_min_lines <= 7 or a.pocket_probe < 0:
         ap.error("--pockets_top_k must be at least 1, --pocket_spacing positive, --pocket_min_lines in 0..7, --pocket_probe not negative")
     if not (a.interaction_contact_distance > 0 and np.isfinite(a.interaction_contact_distance)):
@@ -760,7 +819,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       minimize_poses=MinimizeConfig(iterations=a.minimize_iterations, restraint=a.minimize_restraint,
                                                     sidechains=a.minimize_sidechains, sidechain_restraint=a.minimize_sidechain_restraint)
                       if (a.minimize_poses or a.minimize_sidechains or a.rank_by == "minimized_score") else None,
-                      interaction_profile=ProfileConfig(contact_distance=a.interaction_contact_distance) if a.interaction_profile else None)
+                      interaction_profile=ProfileConfig(contact_distance=a.interaction_contact_distance) if a.interaction_profile else None,
+                      search_poses=SearchConfig(replicas=a.search_replicas, cycles=a.search_cycles, iterations=a.search_iterations,
+                                                temperature=a.search_temperature, seed=a.search_seed)
+                      if (a.search_poses or a.rank_by == "searched_score") else None)
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

@@ -892,6 +892,65 @@ def pose_minimize(pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, 
               mask_rotate, step, accepted, energy_in, energy_out, iterations, restraint, grow, shrink, step_max, history, grad)
 
 
+# ------------------------------------------------------------------------------------------------ pose search (csrc/ddp_search.hip)
+def pose_search(anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate, replicas, cycle0, perturb, u,
+                cur_pos, cur_e, best_pos, best_e, best_cycle, accepted, trace, flags, iterations, temperature, step_init=1.0, restraint=0.0,
+                grow=2.0, shrink=0.5, step_max=1024.0, starts=None):
+    """ddp_pose_search: C cycles of the iterated local search of search.py on the replicas * S rows of the S poses `anchor` [S, n, 3]
+    fp32, in one launch.  lig_radii ... mask_rotate as pose_minimize; perturb [C, rows, 6 + T] fp32 and u [C, rows] fp64 (C, the cycles
+    of this call, is read off their shape); the row state cur_pos, best_pos [rows, n, 3] fp32, cur_e, best_e [rows, 4] fp64, best_cycle,
+    accepted int32 [rows] (in/out; cycle0 = 0: written fresh by the kernel); trace [C, rows, 2] fp64, flags uint8 [C, rows]; starts
+    [C, rows, n, 3] fp32 or None; iterations: of one descent.  Shapes and dtypes are checked here; no device tensor is downloaded."""
+    who = "pose_search"
+    dev, S, n, m, rec_stride = pose_dims(who, anchor, rec)
+    T = 0 if bonds is None else int(bonds.shape[0])
+    replicas, cycle0, iterations = int(replicas), int(cycle0), int(iterations)
+    if replicas < 1 or cycle0 < 0 or iterations < 0:
+        raise L.DdpError(f"{who}: replicas < 1, cycle0 < 0 or iterations < 0")
+    if u is None or u.dim() != 2:
+        raise L.DdpError(f"{who}: u [cycles, rows]")
+    Cn, rows = int(u.shape[0]), S * replicas
+    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+    ligand = [(anchor, f32, (S, n, 3), "anchor"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"), (rec, f32, None, "rec"),
+              (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (self_pairs, u8, (n, n), "self_pairs"),
+              (bonds, i32, (T, 2), "bonds"), (mask_rotate, u8, (T, n), "mask_rotate")]
+    chain = [(perturb, f32, (Cn, rows, 6 + T), "perturb"), (u, f64, (Cn, rows), "u"), (cur_pos, f32, (rows, n, 3), "cur_pos"),
+             (cur_e, f64, (rows, 4), "cur_e"), (best_pos, f32, (rows, n, 3), "best_pos"), (best_e, f64, (rows, 4), "best_e"),
+             (best_cycle, i32, (rows,), "best_cycle"), (accepted, i32, (rows,), "accepted"), (trace, f64, (Cn, rows, 2), "trace"),
+             (flags, u8, (Cn, rows), "flags"), (starts, f32, (Cn, rows, n, 3), "starts")]
+    a = L.SearchArgs(replicas=replicas, cycles=Cn, cycle0=cycle0, step_init=float(step_init), temperature=float(temperature))
+    a.min = _pose_args(L.MinimizeArgs, who, dev, ligand, ("self_pairs",) + (("bonds", "mask_rotate") if T == 0 else ()), config, n_samples=S, n=n,
+                       m=m, rec_stride=rec_stride, n_tor=T, iterations=iterations, restraint=float(restraint), grow=float(grow),
+                       shrink=float(shrink), step_max=float(step_max))
+    check_tensors(who, dev, chain, ("starts",))
+    for t, _, _, name in chain:
+        setattr(a, name, _p(t) or None)
+    L.check(L.load().ddp_pose_search(C.byref(a), stream()), "ddp_pose_search")
+
+
+def pose_search_select(best_pos, best_e, best_cycle, replicas, pos_out=None, energy_out=None, replica_out=None, cycle_out=None):
+    """ddp_pose_search_select: per pose the replica with the smallest best_e[:, 3] (strict <, in replica order: ties go to the lower
+    replica, NaN and +inf are never smaller, none below +inf gives replica 0).  best_pos [S * replicas, n, 3] fp32, best_e [S * replicas,
+    4] fp64, best_cycle int32 [S * replicas].  Returns (pos_out [S, n, 3], energy_out [S, 4], replica_out [S], cycle_out [S])."""
+    who = "pose_search_select"
+    replicas = int(replicas)
+    if best_pos.dim() != 3 or best_pos.shape[2] != 3 or replicas < 1 or best_pos.shape[0] % replicas:
+        raise L.DdpError(f"{who}: best_pos [S * replicas, n, 3], replicas >= 1")
+    dev, rows, n = best_pos.device, best_pos.shape[0], best_pos.shape[1]
+    S = rows // replicas
+    f32, f64, i32 = torch.float32, torch.float64, torch.int32
+    pos_out = torch.empty(S, n, 3, dtype=f32, device=dev) if pos_out is None else pos_out
+    energy_out = torch.empty(S, 4, dtype=f64, device=dev) if energy_out is None else energy_out
+    replica_out = torch.empty(S, dtype=i32, device=dev) if replica_out is None else replica_out
+    cycle_out = torch.empty(S, dtype=i32, device=dev) if cycle_out is None else cycle_out
+    want = [(best_pos, f32, (rows, n, 3), "best_pos"), (best_e, f64, (rows, 4), "best_e"), (best_cycle, i32, (rows,), "best_cycle"),
+            (pos_out, f32, (S, n, 3), "pos_out"), (energy_out, f64, (S, 4), "energy_out"), (replica_out, i32, (S,), "replica_out"),
+            (cycle_out, i32, (S,), "cycle_out")]
+    a = _pose_args(L.SearchSelectArgs, who, dev, want, (), None, n_samples=S, n=n, replicas=replicas)
+    L.check(L.load().ddp_pose_search_select(C.byref(a), stream()), "ddp_pose_search_select")
+    return pos_out, energy_out, replica_out, cycle_out
+
+
 # ------------------------------------------------------------------------------------------------ joint minimiser (csrc/ddp_minimize_flex.hip)
 def flex_tables(sc, m: int, device) -> dict:
     """The side-chain tables of ddp_pose_minimize_flex: HOST tensors (a minimize_flex.SidechainTables, or anything with its fields mov,

@@ -17,7 +17,8 @@ What it does not do:
   - no receptor or side-chain motion: flexible rows are minimised against each sample's own, fixed side chains (the joint form,
     in which the chi angles of the flexible residues descend with the ligand, is minimize_flex.py);
   - no hydrogens;
-  - no global search: it is a local descent from the sampled pose;
+  - no global search: it is a local descent from the sampled pose (search.py runs Monte Carlo moves around it, each followed by
+    this descent);
   - the score is not validated against smina or Vina (see scoring.py), so neither is its minimum: on the 3dpf fixture the crystal
     pose itself moves 0.47 A and goes from E = -10.97 to -13.65, the score's minimum is NOT the crystal pose;
   - E is only C0 at the kinks of the ramps and has a jump of about 1e-11 at the cutoff; the pose map re-aligns the conformer after

@@ -298,6 +298,29 @@ def write_minimized_csv(path: str, minimized, order=None) -> str:
     return path
 
 
+# ---------------------------------------------------------------------------------------------- search in the physics score
+SEARCHED_COLUMNS = ["rank", "sample", "total_before", "total_after", "energy_before", "energy_minimized", "energy_after", "best_replica",
+                    "best_cycle", "moves", "rmsd_moved"]
+
+
+def write_searched_csv(path: str, searched, order=None) -> str:
+    """searched.csv of one complex: one row per pose in RANKED order (search.SearchResult of the ranked poses).  rank and sample as
+    minimized.csv; total_* are scoring.PoseScores.total of the pose before and after (comparable with scores.csv); energy_* the E of
+    search.py of the sampled pose, after the plain descent of replica 0 and of the result; best_replica and best_cycle say which chain
+    found the result and when (-1: the sampled pose itself), moves counts that chain's Metropolis moves, rmsd_moved is in angstrom."""
+    import csv
+    r = searched.cpu()
+    sample = list(range(r.lig_pos.shape[0])) if order is None else [int(v) for v in _np(order).reshape(-1)]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(SEARCHED_COLUMNS)
+        for k in range(r.lig_pos.shape[0]):
+            w.writerow([k + 1, sample[k], f"{float(r.scores_before.total[k]):.6g}", f"{float(r.scores_after.total[k]):.6g}",
+                        f"{float(r.energy_before[k, 3]):.6g}", f"{float(r.energy_minimized[k, 3]):.6g}", f"{float(r.energy_after[k, 3]):.6g}",
+                        int(r.replica[k]), int(r.cycle[k]), int(r.moves[k]), f"{float(r.rmsd_moved[k]):.4f}"])
+    return path
+
+
 MINIMIZED_SIDECHAINS_COLUMNS = ["rank", "sample", "sc_before", "sc_after", "sidechain_restraint_after", "sidechain_rmsd_moved"]
 
 
@@ -410,7 +433,7 @@ def complex_dir(out_dir: str, index: int, name: str) -> str:
 def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph, ligand_pos, confidence=None, atom_pos=None,
                   lig_traj=None, atom_traj=None, remove_hs: bool = True, clusters=None, order=None, refine=None, pockets=None,
                   pockets_docked: int = 1, scores=None, refined_scores=None, minimized=None, interactions=None,
-                  interaction_reference=None) -> List[str]:
+                  interaction_reference=None, searched=None) -> List[str]:
     """Files of one complex (reference inference.py:240-280), all inputs in RANKED order, pocket-centred:
     ligand_pos [N, n_lig, 3]; confidence [N] or [N, k] (first column) or None; atom_pos [N, n_atoms, 3] of a flexible run or None;
     lig_traj [N, n_slots, n_lig, 3] / atom_traj [N, n_slots, n_moving, 3] with save_visualisation.  Returns the paths written.
@@ -427,7 +450,9 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     score, and minimized.csv; a minimize_flex.FlexMinimizeResult: also rank{k}_minimized_protein.pdb, the receptor with the side chains
     the pose was minimised with (write_receptor), and minimized_sidechains.csv.
     interactions (interactions.InteractionProfile of the ranked poses; interaction_reference: of the known pose): also interactions.csv,
-    interaction_summary.csv and interaction_similarity.csv."""
+    interaction_summary.csv and interaction_similarity.csv.
+    searched (search.SearchResult of the ranked poses): also rank{k}_searched.sdf, the pose after the search in the physics score, and
+    searched.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -484,6 +509,10 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
                 write_receptor(put(os.path.join(write_dir, f"rank{k + 1}_minimized_protein.pdb")), pdb_text, graph,
                                [_np(minimized.atom_pos[k])[mv]], remove_hs)
             write_minimized_sidechains_csv(put(os.path.join(write_dir, "minimized_sidechains.csv")), minimized, order)
+    if searched is not None:
+        for k in range(searched.lig_pos.shape[0]):
+            write_sdf(put(os.path.join(write_dir, f"rank{k + 1}_searched.sdf")), mol, searched.lig_pos[k], name, oc)
+        write_searched_csv(put(os.path.join(write_dir, "searched.csv")), searched, order)
     if interactions is not None:
         write_interactions_csv(put(os.path.join(write_dir, "interactions.csv")), interactions, order)
         write_interaction_summary_csv(put(os.path.join(write_dir, "interaction_summary.csv")), interactions)

@@ -1044,6 +1044,66 @@ typedef struct {
 } ddp_minimize_flex_args_t;
 int ddp_pose_minimize_flex(const ddp_minimize_flex_args_t* args, void* stream);
 
+/* ---- iterated local search around sampled poses in the same score: Monte Carlo moves in pose space, each followed by the line search
+ * of ddp_pose_minimize and a Metropolis decision (csrc/ddp_search.hip; host side diffdock_pocket_amd/search.py, whose module docstring
+ * states the whole definition: the state of a row, the five steps of a cycle, the selection rule).  Pose s < n_samples seeds `replicas`
+ * independent rows q = s replicas + r; one 256-thread workgroup per row runs `cycles` cycles, n_samples replicas workgroups in one
+ * launch.  The random numbers are inputs: perturb [cycles][rows][6 + n_tor] fp32 (tr, rot, then the torsions in bond order) and u
+ * [cycles][rows] fp64 in [0, 1), indexed by the cycle OF THIS CALL (a resuming caller hands in the slices of the cycles it runs), as
+ * are trace [cycles][rows][2] = (E of the start pose, E of the local minimum), flags [cycles][rows] = move | improved << 1 and the
+ * optional starts [cycles][rows][n][3] = the start pose of every cycle (or NULL).
+ * `min` carries the score and the line search as for ddp_pose_minimize: n_samples, n, m, rec_stride, n_tor, iterations (of one descent),
+ * anchor (the sampled poses x0 [n_samples][n][3]: start and restraint anchor of every replica of pose s), lig_radii, lig_flags, rec,
+ * rec_radii, rec_flags, self_pairs, bonds, mask_rotate, form, restraint, grow, shrink, step_max.  Its pos, step, accepted, energy_in,
+ * energy_out, history and grad are not read and may be NULL.  Every descent starts with step = step_init.
+ * Row state, in and out: cur_pos, best_pos [rows][n][3] fp32, cur_e, best_e [rows][4] fp64 (inter, intra, restraint term, E),
+ * best_cycle int32 [rows] (global cycle index), accepted int32 [rows] (accepted descent trials).  cycle0 = the number of cycles done
+ * before this call; cycle0 = 0: the state is not read, the kernel itself writes the fresh state (cur_pos = best_pos = x0, every energy
+ * +inf, best_cycle -1, accepted 0) and replica 0 starts its first cycle at x0 bit for bit, its perturb entries ignored.
+ * Invariants: two launches give the same bits.  The rows of pose s in a batch equal the launch of that pose alone.  a + b cycles equal
+ * a cycles followed by b cycles with cycle0 = a on the state left in memory, bit for bit.  The local descent of a cycle equals
+ * ddp_pose_minimize from starts[c][q] with anchor x0[s], step_init and `iterations` iterations, bit for bit (one loop,
+ * csrc/ddp_minimize_loop.h).  No data-dependent control flow around a barrier: every decision is taken by all threads from the same
+ * LDS or global words.  A NaN pose takes the same path and never moves: beyond the fresh state it writes only its trace and flags
+ * (and the unchanged scalars of its state).  cur_pos / best_pos of a row are written only on a move / an improvement.
+ * LDS plan and limits: those of ddp_pose_minimize (17.9 KiB + 89 n; DDP_MINIMIZE_MAX_ATOMS, DDP_MINIMIZE_MAX_TORSIONS: DDP_ELIMIT).
+ * n_samples = 0 or cycles = 0: no-op.  DDP_EINVAL without a launch: what ddp_pose_minimize rejects (of the pointers: those read
+ * here), replicas < 1, cycles < 0, cycle0 < 0, temperature not positive and finite, step_init not positive, a NULL perturb, u, state
+ * pointer, trace or flags, n_samples replicas >= 2^31. */
+typedef struct {
+  ddp_minimize_args_t min;      /* the score and the line search, see above */
+  int32_t replicas, cycles, cycle0, reserved;
+  double step_init, temperature;
+  const float* perturb;         /* [cycles][rows][6 + n_tor] */
+  const double* u;              /* [cycles][rows] */
+  float* cur_pos;               /* [rows][n][3], in/out */
+  double* cur_e;                /* [rows][4], in/out */
+  float* best_pos;              /* [rows][n][3], in/out */
+  double* best_e;               /* [rows][4], in/out */
+  int32_t* best_cycle;          /* [rows], in/out */
+  int32_t* accepted;            /* [rows], in/out */
+  double* trace;                /* [cycles][rows][2] */
+  uint8_t* flags;               /* [cycles][rows] */
+  float* starts;                /* [cycles][rows][n][3] or NULL */
+} ddp_search_args_t;
+int ddp_pose_search(const ddp_search_args_t* args, void* stream);
+
+/* ---- the result of a search per pose: the replica with the smallest best_e[s replicas + r][3], compared with strict < in replica order
+ * from replica 0 (a tie goes to the lower replica; NaN and +inf are never smaller; if no replica is below +inf, replica 0).  One block
+ * per pose: pos_out[s] = best_pos of that row (copied bit for bit), energy_out[s] = its best_e, replica_out[s] = r, cycle_out[s] = its
+ * best_cycle.  n_samples = 0: no-op.  DDP_EINVAL without a launch: a NULL struct or pointer, n_samples < 0, n <= 0, replicas < 1. */
+typedef struct {
+  int32_t n_samples, n, replicas, reserved;
+  const float* best_pos;        /* [n_samples replicas][n][3] */
+  const double* best_e;         /* [n_samples replicas][4] */
+  const int32_t* best_cycle;    /* [n_samples replicas] */
+  float* pos_out;               /* [n_samples][n][3] */
+  double* energy_out;           /* [n_samples][4] */
+  int32_t* replica_out;         /* [n_samples] */
+  int32_t* cycle_out;           /* [n_samples] */
+} ddp_search_select_args_t;
+int ddp_pose_search_select(const ddp_search_select_args_t* args, void* stream);
+
 /* ---- geometric pocket finder: LIGSITE-style buriedness on a grid (csrc/ddp_pockets.hip; host side diffdock_pocket_amd/pockets.py, which
  * states the whole definition).  This project's own method, no learned predictor.  Grid point (i, j, k), 0 <= i < nx ..., has the flat
  * index g = (i ny + j) nz + k and sits at lo + (i, j, k) spacing; everything outside the grid is free space.  nx ny nz < 2^31.
