@@ -462,6 +462,44 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 #define DDP_SAH_CT 4   // column tiles per wave: 2 planes x 4 k-steps x 4 registers each = 32 weight registers per tile
 #endif
 
+// One 32 x 32 block of plane form 1, the ONE definition both G3 kernels below use (their bytes are equal because of it): the transposed
+// product on the wave's weights `w` and the tile's operand fragments `a` (12 MFMAs at K = 60, one accumulator), then this lane's four
+// accumulator quads (row r, product columns 8 q + 4 hh + 0..3 of the block: half of group q) into the row's image at `tl`: 8 bytes of
+// hi words at 24 q + 8 hh, 4 continuation bytes at 24 q + 16 + 4 hh.  sp4: bit q = group q is a plane group (wave-uniform).
+template <int NS>
+__device__ __forceinline__ void sa_g3_block(const h8 (&w)[2][NS], const h8 (&a)[2][NS], char* tl, unsigned sp4, int hh, float& gh_max) {
+  f32x16 am;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) am[i] = 0.f;
+#pragma unroll
+  for (int s2 = 0; s2 < NS; ++s2) {
+    am = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][s2], a[0][s2], am, 0, 0, 0);
+    am = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1][s2], a[0][s2], am, 0, 0, 0);
+    am = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][s2], a[1][s2], am, 0, 0, 0);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const bool sp = ((sp4 >> q) & 1u) != 0u;
+    const float v0 = am[4 * q], v1 = am[4 * q + 1], v2 = am[4 * q + 2], v3 = am[4 * q + 3];
+    gh_max = fmaxf(gh_max, sp ? fmaxf(fmaxf(fabsf(v0), fabsf(v1)), fmaxf(fabsf(v2), fabsf(v3))) : 0.f);
+    // V rounded to 19 significant bits (half of bit 5 of the fp32 mantissa added to the bit pattern: magnitude rounding, carries into the
+    // exponent where it must), hi = its truncation to fp16, byte = mantissa bits 12 .. 5 (below the fp16 normal range the byte means
+    // nothing and the reader multiplies it by the hi word's zero exponent)
+    const uint32_t b0 = __builtin_bit_cast(uint32_t, v0) + 0x10u, b1 = __builtin_bit_cast(uint32_t, v1) + 0x10u;
+    const uint32_t b2 = __builtin_bit_cast(uint32_t, v2) + 0x10u, b3 = __builtin_bit_cast(uint32_t, v3) + 0x10u;
+    typedef __fp16 pk2 __attribute__((ext_vector_type(2)));
+    const pk2 h01 = __builtin_amdgcn_cvt_pkrtz(__builtin_bit_cast(float, b0), __builtin_bit_cast(float, b1));
+    const pk2 h23 = __builtin_amdgcn_cvt_pkrtz(__builtin_bit_cast(float, b2), __builtin_bit_cast(float, b3));
+    const uint32_t lo = ((b0 >> 5) & 0xffu) | (((b1 >> 5) & 0xffu) << 8) | (((b2 >> 5) & 0xffu) << 16) | ((b3 >> 5) << 24);
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 w8;
+    w8[0] = sp ? __builtin_bit_cast(uint32_t, h01) : __builtin_bit_cast(uint32_t, v0);
+    w8[1] = sp ? __builtin_bit_cast(uint32_t, h23) : __builtin_bit_cast(uint32_t, v1);
+    *reinterpret_cast<u32x2*>(tl + 24 * q + 8 * hh) = w8;
+    *reinterpret_cast<uint32_t*>(tl + 24 * q + 16 + 4 * hh) = sp ? lo : __builtin_bit_cast(uint32_t, v2);
+  }
+}
+
 // GH (round 5): the G part of a row leaves as fp16 hi/lo operand planes - the layout ddp_conv_rows reads G in
 // (include/ddp_hip.h, ddp_conv_task_t::gh): a lane then drains 8 consecutive columns of a parked row (one 8-k group of one G column)
 // as two 16-byte pieces, hi plane and lo plane, where the fp32 form stores two 16-byte quads - the same bytes, the same number of
@@ -477,6 +515,7 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 // the row tile in LDS (32 rows x the 384 bytes of the wave's 16 groups: no fp32 park, no re-read for the conversion), and behind the row
 // tile's fourth block the wave copies the image out with twelve 16-byte store instructions of WHOLE 128-byte lines (8 rows x 384 bytes per
 // three instructions).  Needs ncols % 128 == 0 (a wave's four blocks are all there or none is) and ldo = 6 ncols / 8.
+// (Long products - 4096 rows and more - run ddp_stage_a_g3dw_kernel below: three MFMA waves beside a store wave, the same bytes.)
 // (Measured and dropped: the waves running FREE - every wave fetching and splitting its own operand fragments, no shared x tile, no barrier
 // in the loop - 1.05 instead of 0.89 ms on the atom stack, the step 15.2 instead of 14.3 ms: four times the split work, 22 spilled registers;
 // the image leaving one row group behind each k-step of the NEXT tile's first block instead of as a burst - 0.92 ms, the step 14.7 ms.)
@@ -709,37 +748,7 @@ __global__ __launch_bounds__(DDP_GEMM_THREADS, 2) void ddp_stage_a_h2_kernel(con
   // G3: block t of the row tile - the transposed product, then this lane's four accumulator quads (row r, product columns 32 t + 8 q + 4 hh
   // + 0..3: half of group q) into the wave's image: 8 bytes of hi words at 24 (4 t + q) + 8 hh, 4 continuation bytes at + 16 + 4 hh
   auto block3 = [&](int t, const h8 (&a)[2][NS]) {
-    f32x16 am;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) am[i] = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < NS; ++s2) {
-      am = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[t][0][s2], a[0][s2], am, 0, 0, 0);
-      am = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[t][1][s2], a[0][s2], am, 0, 0, 0);
-      am = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[t][0][s2], a[1][s2], am, 0, 0, 0);
-    }
-    char* tl = g3t[G3 ? wave : 0] + r * RS3 + 96 * t;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const bool sp = ((sp3 >> (4 * t + q)) & 1u) != 0u;      // (wave-uniform)
-      const float v0 = am[4 * q], v1 = am[4 * q + 1], v2 = am[4 * q + 2], v3 = am[4 * q + 3];
-      gh_max = fmaxf(gh_max, sp ? fmaxf(fmaxf(fabsf(v0), fabsf(v1)), fmaxf(fabsf(v2), fabsf(v3))) : 0.f);
-      // V rounded to 19 significant bits (half of bit 5 of the fp32 mantissa added to the bit pattern: magnitude rounding, carries into the
-      // exponent where it must), hi = its truncation to fp16, byte = mantissa bits 12 .. 5 (below the fp16 normal range the byte means
-      // nothing and the reader multiplies it by the hi word's zero exponent)
-      const uint32_t b0 = __builtin_bit_cast(uint32_t, v0) + 0x10u, b1 = __builtin_bit_cast(uint32_t, v1) + 0x10u;
-      const uint32_t b2 = __builtin_bit_cast(uint32_t, v2) + 0x10u, b3 = __builtin_bit_cast(uint32_t, v3) + 0x10u;
-      typedef __fp16 pk2 __attribute__((ext_vector_type(2)));
-      const pk2 h01 = __builtin_amdgcn_cvt_pkrtz(__builtin_bit_cast(float, b0), __builtin_bit_cast(float, b1));
-      const pk2 h23 = __builtin_amdgcn_cvt_pkrtz(__builtin_bit_cast(float, b2), __builtin_bit_cast(float, b3));
-      const uint32_t lo = ((b0 >> 5) & 0xffu) | (((b1 >> 5) & 0xffu) << 8) | (((b2 >> 5) & 0xffu) << 16) | ((b3 >> 5) << 24);
-      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-      u32x2 w8;
-      w8[0] = sp ? __builtin_bit_cast(uint32_t, h01) : __builtin_bit_cast(uint32_t, v0);
-      w8[1] = sp ? __builtin_bit_cast(uint32_t, h23) : __builtin_bit_cast(uint32_t, v1);
-      *reinterpret_cast<u32x2*>(tl + 24 * q + 8 * hh) = w8;
-      *reinterpret_cast<uint32_t*>(tl + 24 * q + 16 + 4 * hh) = sp ? lo : __builtin_bit_cast(uint32_t, v2);
-    }
+    sa_g3_block<NS>(wr[t], a, g3t[G3 ? wave : 0] + r * RS3 + 96 * t, (sp3 >> (4 * t)) & 0xfu, hh, gh_max);
   };
   // G3: the row tile's image leaves - twelve 16-byte stores of whole lines; rows behind the tile's last repeat it (identical data)
   auto drain3 = [&](int myrow, int nr) {
@@ -824,6 +833,246 @@ __global__ __launch_bounds__(DDP_GEMM_THREADS, 2) void ddp_stage_a_h2_kernel(con
   }
 }
 
+// ---- G3 with a STORE WAVE (plane form 1 only; the form above stays for short products and behind DDP_SA_DRAINWAVE=0).  In the form above a
+// wave multiplies OR stores: its twelve stores of a row tile wait behind 48 MFMAs, and the per-tile barrier lines the four bursts up.  Here a
+// workgroup is 3 MFMA waves + 1 store wave over 384 product columns = twelve 32-column blocks = THREE 384-byte row groups.  MFMA wave w
+// computes block 3 j + w in round j = 0 .. 3 of a 32-row tile - sa_g3_block, the other form's own block - into the image of the block's group
+// (32 rows x 384 bytes in LDS, one image per group); group g = blocks 4 g .. 4 g + 3 is complete behind round g + 1.  One bare barrier
+// (lgkmcnt(0) in front, no vmcnt: stores stay in flight across it) ends every round.  The store wave copies group 0 out in round 2, group 1
+// in round 3 and group 2 in round 0 of the next tile - drain3's twelve stores of whole 128-byte lines per group, a group every round instead
+// of four bursts per tile - and computes the tile's store addresses in round 1; an image is rewritten two rounds after it was read.  The
+// store wave issues NO loads: the MFMA waves fetch the next x tile in round 0 and split it into the other x buffer behind round 3 (with the
+// tile's row indices, which the store wave reads from LDS).  With the split on the store wave hipcc's in-order vmcnt makes it wait for its
+// own stores in front of the split, and the stores stop: 4.0 - 4.1 instead of 4.4 - 4.5 TB/s in tools/micro/store_g3.hip (D0 / D1,
+// profiles/stage_a_drainwave_micro.txt).  54.75 KB of LDS, 252 registers, two workgroups per CU as before.  4 MFMA waves + 1 store wave
+// would need ten waves on a CU's four SIMDs = three on one = 168 registers, and the weights, the fragments and one accumulator are 176.
+// Measured (profiles/stage_a_drainwave_ab.txt): the atom stack 0.867 -> 0.828 ms (4.1 -> 4.3 TB/s; the micro-benchmark's 4.5 is not
+// reached), the receptor stack 0.344 -> 0.321 ms.
+#define DDP_SA_BAR()                                   \
+  do {                                                 \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
+    __builtin_amdgcn_s_barrier();                      \
+    asm volatile("" ::: "memory");                     \
+  } while (0)
+template <int KT>
+__global__ __launch_bounds__(DDP_GEMM_THREADS, 2) void ddp_stage_a_g3dw_kernel(const float* __restrict__ x, int ldx, int nrows,
+                                                                                const int32_t* __restrict__ rows,
+                                                                                const int32_t* __restrict__ nrows_dev, int out_rows,
+                                                                                int mrows, const GemmOffs offs,
+                                                                                const _Float16* __restrict__ wh, int ncols,
+                                                                                float* __restrict__ out, int ldo, int32_t* range_flag,
+                                                                                const int32_t* __restrict__ gh_dest) {
+  static_assert(DDP_GEMM_THREADS == 256, "3 MFMA waves + 1 store wave");
+  if (nrows_dev) nrows = min(nrows, *nrows_dev);
+  if ((int)blockIdx.y * mrows >= nrows) return;
+  constexpr int KP = (KT + 15) / 16 * 16, NS = KP / 16;
+  constexpr int XS = KP + 8, RS3 = 392;                        // as in ddp_stage_a_h2_kernel
+  constexpr int NP = 32 * (KT / 4);                            // 16-byte pieces of an x tile
+  constexpr int NMT = 192, NV = (NP + NMT - 1) / NMT;          // threads of the MFMA waves, pieces per thread
+  __shared__ __attribute__((aligned(16))) _Float16 xt[2][2][32 * XS];
+  __shared__ __attribute__((aligned(16))) char img[3][32 * RS3];
+  __shared__ int32_t rowid[2][32];                             // out rows of the tile in xt[buf]
+  const int z = (int)blockIdx.z, tid = (int)threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, hh = lane >> 5;
+  const int colw = (int)blockIdx.x * 384;                      // (< ncols by the grid; ncols % 128 == 0)
+  const int ngr = min(3, (ncols - colw) >> 7);                 // row groups of this workgroup that exist
+  if constexpr (KP > KT) {
+    for (int i = tid; i < 2 * 2 * 32 * (KP - KT); i += DDP_GEMM_THREADS) {
+      const int kk = i % (KP - KT), rr = (i / (KP - KT)) % 32, bp = i / ((KP - KT) * 32);
+      xt[bp / 2][bp % 2][rr * XS + KT + kk] = (_Float16)0.f;
+    }
+  }
+  // The workgroup's tiles, in order: the 32-row tiles of its row ranges blockIdx.y, + gridDim.y, ... (mrows rows each, a multiple of 32).
+  // The tile pipeline runs THROUGH the ends of the ranges, so a grid of one workgroup per slot of the chip can walk a long product in
+  // short ranges: weights loaded once, an even share of the rows for every workgroup, no tail.  row0 >= nrows: behind the last tile.
+  struct Tile { int R0, R1, row0; };
+  const int ystep = (int)gridDim.y * mrows;
+  auto tile_next = [&](Tile t) {
+    t.row0 += 32;
+    if (t.row0 >= t.R1) {
+      t.R0 += ystep;
+      t.row0 = t.R0;
+      t.R1 = min(nrows, t.R0 + mrows);
+    }
+    return t;
+  };
+  const Tile tile0 = {(int)blockIdx.y * mrows, min(nrows, (int)blockIdx.y * mrows + mrows), (int)blockIdx.y * mrows};
+  if (wave == 3) {
+    // ---- the store wave
+    float* __restrict__ ob = out + (size_t)z * out_rows * ldo + 6 * (colw >> 3);
+    int dl[12];                                                // where lane's piece of store k sits in an image / in the array
+    size_t doff[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { dl[k] = 0; doff[k] = 0; }
+    auto drain = [&](int g) {
+      const char* im = img[g];
+      float* __restrict__ og = ob + 96 * g;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x2 lo8 = *reinterpret_cast<const u32x2*>(im + dl[k]);
+        const u32x2 hi8 = *reinterpret_cast<const u32x2*>(im + dl[k] + 8);
+        *reinterpret_cast<u32x4*>(og + doff[k]) = u32x4{lo8[0], lo8[1], hi8[0], hi8[1]};
+      }
+    };
+    Tile t = tile0;
+    DDP_SA_BAR();                                              // the first x tile and its rows are parked
+    for (int n = 0;; ++n) {
+      if (n > 0 && ngr > 2) drain(2);                          // round 0: the previous tile's last group
+      DDP_SA_BAR();
+      {                                                        // round 1: this tile's addresses; rows behind its range's last repeat it
+        const int nr = t.R1 - t.row0;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+          const int i = 64 * (k % 3) + lane, rl = min(8 * (k / 3) + i / 24, nr - 1);
+          dl[k] = rl * RS3 + 16 * (i % 24);
+          doff[k] = (size_t)rowid[n & 1][rl] * ldo + 4 * (i % 24);
+        }
+      }
+      DDP_SA_BAR();
+      drain(0);                                                // round 2
+      DDP_SA_BAR();
+      if (ngr > 1) drain(1);                                   // round 3
+      DDP_SA_BAR();
+      t = tile_next(t);
+      if (t.row0 >= nrows) break;
+    }
+    if (ngr > 2) drain(2);
+    return;
+  }
+  // ---- an MFMA wave: blocks b = 3 j + wave, j = 0 .. 3 (weights of block j in wr[j])
+  h8 wr[4][2][NS];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = min(colw + 32 * (3 * j + wave) + r, ncols - 1);
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int s2 = 0; s2 < NS; ++s2)
+        wr[j][p][s2] = *reinterpret_cast<const h8*>(wh + (((((size_t)z * 2 + p) * NS + s2) * 2 + hh) * ncols + c) * 8);
+  }
+  // which of the wave's 16 groups are plane groups (bit 4 j + q)
+  unsigned sp3;
+  {
+    const int l = lane & 15;
+    const int g = min(((colw + 32 * (3 * (l >> 2) + wave)) >> 3) + (l & 3), (ncols >> 3) - 1);
+    sp3 = (unsigned)__ballot((gh_dest[((size_t)z * (ncols >> 3) + g) * 2] & 1) != 0) & 0xffffu;
+  }
+  float gh_max = 0.f;
+  const float* __restrict__ xb = x + offs.off[z];
+  const bool al4 = ((ldx | offs.off[z]) & 3) == 0 && (reinterpret_cast<size_t>(x) & 15) == 0;
+  // The row list and the alignment of x are compile-time constants of the loop: under `rows ? rows[ri] : ri` hipcc puts every load of a
+  // tile behind a branch and a vmcnt(0) - three memory latencies in a row in front of the tile's MFMAs, behind a full store queue (1.07
+  // instead of 0.85 ms on the atom stack).  A list's rows are requested a tile ahead of the x loads that need them.
+  auto run = [&](auto listed_tag, auto al4_tag) {
+  constexpr bool LISTED = decltype(listed_tag)::value, AL4 = decltype(al4_tag)::value;
+  f32x4 xv[NV];
+  int xrow[NV], xnext[NV];
+  auto rows_of = [&](int row0, int (&dst)[NV]) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int i = min(tid + v * NMT, NP - 1);
+      const int ri = min(row0 + i / (KT / 4), nrows - 1);
+      if constexpr (LISTED)
+        dst[v] = rows[ri];
+      else
+        dst[v] = ri;
+    }
+  };
+  auto fetch = [&]() {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int i = min(tid + v * NMT, NP - 1);
+      const float* __restrict__ p = xb + (size_t)xrow[v] * ldx + 4 * (i % (KT / 4));
+      if constexpr (AL4)
+        xv[v] = *reinterpret_cast<const f32x4*>(p);
+      else
+        xv[v] = f32x4{p[0], p[1], p[2], p[3]};
+    }
+  };
+  auto park = [&](int buf) {   // the split of ddp_stage_a_h2_kernel's park (unified planes at DDP_GH_SX), + the tile's rows
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int i = tid + v * NMT;
+      if (i < NP) {
+        const int rr = i / (KT / 4), q = i % (KT / 4);
+        h4 h, l;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float f = xv[v][e] * (float)DDP_GH_SX;
+          if (!(fabsf(f) <= 65504.f) && range_flag) *range_flag = 1;
+          h[e] = (_Float16)f;
+          l[e] = (_Float16)(f - (float)h[e]);
+        }
+        *reinterpret_cast<h4*>(&xt[buf][0][rr * XS + 4 * q]) = h;
+        *reinterpret_cast<h4*>(&xt[buf][1][rr * XS + 4 * q]) = l;
+        if (q == 0) rowid[buf][rr] = xrow[v];
+      }
+    }
+  };
+  {
+    Tile t1 = tile_next(tile0), t2 = tile_next(t1);            // the next tile and the one behind it
+    rows_of(tile0.row0, xrow);
+    fetch();
+    park(0);
+    rows_of(t1.row0, xnext);
+    DDP_SA_BAR();
+    for (int n = 0;; ++n) {
+      const int buf = n & 1;
+      const bool more = t1.row0 < nrows;
+      if (more) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) xrow[v] = xnext[v];
+        fetch();
+        rows_of(t2.row0, xnext);
+      }
+      h8 a[2][NS];
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int s2 = 0; s2 < NS; ++s2) a[p][s2] = *reinterpret_cast<const h8*>(&xt[buf][p][r * XS + 16 * s2 + 8 * hh]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int b = 3 * j + wave;
+        if ((b >> 2) < ngr)                                    // (wave-uniform)
+          sa_g3_block<NS>(wr[j], a, img[b >> 2] + r * RS3 + 96 * (b & 3), (sp3 >> (4 * j)) & 0xfu, hh, gh_max);
+        if (j == 3 && more) park(buf ^ 1);
+        DDP_SA_BAR();
+      }
+      if (!more) break;
+      t1 = t2;
+      t2 = tile_next(t2);
+    }
+  }
+  };
+  if (rows) {
+    if (al4)
+      run(std::true_type{}, std::true_type{});
+    else
+      run(std::true_type{}, std::false_type{});
+  } else {
+    if (al4)
+      run(std::false_type{}, std::true_type{});
+    else
+      run(std::false_type{}, std::false_type{});
+  }
+  if (!(gh_max <= 65504.f) && range_flag) *range_flag = 1;
+}
+
+// DDP_SA_DRAINWAVE in the environment (read at the first launch), or the value written here (tests, A/B tools): 0 = plane form 1 keeps the
+// four symmetric waves for every product, 1 (default) = the store-wave form where it is faster, 2 = the store-wave form for every product.
+// Results do not depend on it.
+extern "C" int ddp_sa_drainwave;
+int ddp_sa_drainwave = -1;
+static int stage_a_drainwave() {
+  if (ddp_sa_drainwave < 0) {
+    const char* e = getenv("DDP_SA_DRAINWAVE");
+    ddp_sa_drainwave = (e && e[0] == '0') ? 0 : (e && e[0] == '2') ? 2 : 1;
+  }
+  return ddp_sa_drainwave;
+}
+
 static int stage_a_impl(const float* x, int ldx, int nrows, const int32_t* rows, const int32_t* nrows_dev, int out_rows,
                         const int32_t* offs, int nbatch, const float* w, const void* w_bf16x3, const void* w_h2, int k, int ncols, float* out,
                         int ldo, int32_t* range_flag, void* stream, const int32_t* gh_dest = nullptr, int gh_fmt = 0) {
@@ -872,15 +1121,55 @@ static int stage_a_impl(const float* x, int ldx, int nrows, const int32_t* rows,
   static const bool no_mfma = getenv("DDP_STAGE_A_VALU") != nullptr;   // diagnostic: force the VALU form
   // h2 form (fp16 hi/lo split of both operands): wide, 16-byte aligned outputs only, K = 60 / 32 / 24 / 16 (KP = 64 / 32 / 32 / 16)
   if (gh_dest) {
-    if (!(w_h2 && wide && (k == 60 || k == 32 || k == 24 || k == 16) && (reinterpret_cast<size_t>(w_h2) & 15) == 0 && (ncols & 31) == 0 &&
+    // (plane form 1 has no narrow fall-back to keep away from: its kernels take any whole number of 128-column groups)
+    const bool wide_gh = gh_fmt == 1 ? (((ncols | ldo) & 3) == 0 && (reinterpret_cast<size_t>(out) & 15) == 0) : wide;
+    if (!(w_h2 && wide_gh && (k == 60 || k == 32 || k == 24 || k == 16) && (reinterpret_cast<size_t>(w_h2) & 15) == 0 && (ncols & 31) == 0 &&
           (reinterpret_cast<size_t>(gh_dest) & 7) == 0))
       return ddp_fail(DDP_EINVAL, "ddp_stage_a_gh: plane output needs the h2 path (w_h2, k in {60, 32, 24, 16}) and ncols % 32 == 0");
-    const dim3 grid((ncols + 128 * DDP_SAH_CT_GH - 1) / (128 * DDP_SAH_CT_GH), gy, nbatch);
+    // plane form 1 with a store wave (ddp_stage_a_g3dw_kernel) for dense products from 4096 rows on (profiles/stage_a_drainwave_ab.txt, pairs):
+    // 44440 x 2 0.867 -> 0.828 ms, 5560 x 6 0.344 -> 0.321 ms; 1480 x 6 is 1 - 2 % slower with it (0.094 -> 0.095 ms), and the 185- and 363-row products
+    // do not differ (0.022 / 0.018 ms either way): below 4096 rows the four symmetric waves stay.
+    const int dw_mode = gh_fmt == 1 ? stage_a_drainwave() : 0;
+    // (a row list is dispatched by its capacity, which says little about its length: lists of the short arrays stay on the symmetric waves -
+    // 1500 listed rows of 5560 are 4.5 % slower on the store wave, 5000 of them 2 % faster; lists of the 44440-row array 0 - 8 % faster)
+    const bool dw = dw_mode == 2 || (dw_mode == 1 && nrows >= (listed ? 16384 : 4096));
+    if (dw && !listed) {
+      // dense: ranges of 128 rows and a grid of one workgroup per slot of the chip (two per CU), or of the smallest multiple of that
+      // which fills 95 % of its last round (5560 x 6 at the layer-3 width: 210 workgroups per range, 7 ranges a time = 2.87 rounds)
+      // (the CU count of the device that is current at the first such launch, kept for the process: the devices of a node are alike, and
+      // a race between two first launches writes the same value twice; another count would change the grid, not the result)
+      static int slots = 0;
+      if (!slots) {
+        int dev = 0, ncu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1)
+          return ddp_fail(DDP_EINVAL, "ddp_stage_a_gh3: hipDeviceGetAttribute(multiprocessor count)");
+        slots = 2 * ncu;
+      }
+      mrows = 128;
+      gy = (nrows + mrows - 1) / mrows;
+      const int per_y = (int)((ncols + 383) / 384) * nbatch;
+      int best = 0;
+      double best_fill = 0.;
+      for (int kk = 1; kk <= 6 && best_fill < 0.95; ++kk) {
+        const int g = kk * slots / per_y;
+        const double fill = (double)g * per_y / ((double)kk * slots);
+        if (g >= 1 && fill > best_fill) { best = g; best_fill = fill; }
+      }
+      if (best >= 1 && gy > best) gy = best;
+    }
+    const dim3 grid(dw ? (ncols + 383) / 384 : (ncols + 128 * DDP_SAH_CT_GH - 1) / (128 * DDP_SAH_CT_GH), gy, nbatch);
     // occupancy shaping (ddp_set_occupancy_shaping): extra dynamic LDS on top of the kernel's static 55 KB = one workgroup per CU
     const int pad = ddp_shape_stage_a_pad;
-    static int pad_have[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    static int pad_have[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define DDP_GEMM_GH(KT, I)                                                                                       \
-    {                                                                                                            \
+    if (dw) {                                                                                                    \
+      if (pad > 0) {                                                                                             \
+        const hipError_t ep = ddp_need_lds(reinterpret_cast<const void*>(ddp_stage_a_g3dw_kernel<KT>), pad, &pad_have[8 + I]); \
+        if (ep != hipSuccess) return ddp_fail_hip(ep, "hipFuncSetAttribute(stage A)");                           \
+      }                                                                                                          \
+      hipLaunchKernelGGL((ddp_stage_a_g3dw_kernel<KT>), grid, dim3(DDP_GEMM_THREADS), pad, s, x, ldx, nrows, rows, nrows_dev, out_rows, mrows, O, \
+                         reinterpret_cast<const _Float16*>(w_h2), ncols, out, ldo, range_flag, gh_dest);         \
+    } else {                                                                                                     \
       if (pad > 0) {                                                                                             \
         const hipError_t ep = (gh_fmt == 1) ? ddp_need_lds(reinterpret_cast<const void*>(ddp_stage_a_h2_kernel<KT, true, true>), pad, &pad_have[4 + I]) \
                                             : ddp_need_lds(reinterpret_cast<const void*>(ddp_stage_a_h2_kernel<KT, true>), pad, &pad_have[I]); \

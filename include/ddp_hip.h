@@ -449,6 +449,12 @@ int ddp_stage_a_gh3(const float* x, int ldx, int nrows, const int32_t* rows, con
  * Process-wide, read when a launch is enqueued (captured launches keep what they were captured with); results do not depend on it. */
 int ddp_set_occupancy_shaping(int rows_min_lds_bytes, int stage_a_lds_pad_bytes);
 
+/* ddp_stage_a_gh3 has two kernels that write the same bytes: four symmetric waves per workgroup, and three MFMA waves beside a store wave.
+ * 0 = the symmetric form for every product, 1 = the store-wave form for dense products of 4096 rows and more and row lists of a capacity of 16384 and more (default), 2 = the store-wave form for every product.
+ * -1 (initial): the first launch reads DDP_SA_DRAINWAVE ("0" / "1" / "2") from the environment and stores the value here; tests and A/B
+ * tools may write it themselves.  Process-wide, read when a launch is enqueued. */
+extern int ddp_sa_drainwave;
+
 /* The pose update between two score-model calls, for all samples of a batch in one launch:
  * modify_conformer(pos, tr_update, rot_update, torsion_updates) of utils/diffusion_utils.py:37-60 = rigid move about the
  * centre (rot_update is an axis-angle vector, utils/geometry.py:72-86), torsions in bond order (utils/torsion.py:68-94:
