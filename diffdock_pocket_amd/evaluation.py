@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from .inputs import ATOM_TYPE_3, _SYMBOLS
+from .pose_args import check_poses
 
 ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 OVERLAP_DISTANCE = 0.4
@@ -340,10 +341,7 @@ class PoseEvaluator:
 
     def evaluate(self, lig_pos: torch.Tensor, atom_pos: Optional[torch.Tensor] = None) -> PoseMetrics:
         """lig_pos [S, n, 3] (and, for flexible runs, atom_pos [S, n_a, 3]) -> PoseMetrics of [S] tensors on the poses' device."""
-        if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
-            raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")
-        if atom_pos is not None and (atom_pos.dim() != 3 or atom_pos.shape[1:] != (self.n_a, 3) or atom_pos.shape[0] != lig_pos.shape[0]):
-            raise ValueError(f"atom_pos: expected [S, {self.n_a}, 3], got {tuple(atom_pos.shape)}")
+        check_poses(self.n, self.n_a, None, lig_pos, atom_pos, "evaluator")      # the shapes; device poses: _evaluate_hip tests the device
         if lig_pos.is_cuda:
             return self._evaluate_hip(lig_pos, atom_pos)
         return self._evaluate_torch(lig_pos.float(), None if atom_pos is None else atom_pos.float())
@@ -364,8 +362,7 @@ class PoseEvaluator:
 
     def _evaluate_hip(self, lig, apos) -> PoseMetrics:
         from . import launch as LA
-        if self.device.type != "cuda" or lig.device != self.device:
-            raise ValueError(f"poses on {lig.device}, evaluator built for {self.device}")
+        self._check_lig(lig)
         t = self._dev
         with torch.cuda.device(lig.device):
             lig = lig.float().contiguous()
@@ -401,10 +398,7 @@ class PoseEvaluator:
         return _contacts_torch(lig, t["lig_r"], self._receptor(t, apos), t["rec_r"], t["ref_centroid"], self.overlap)
 
     def _check_lig(self, lig_pos):
-        if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
-            raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")
-        if lig_pos.is_cuda and (self.device.type != "cuda" or lig_pos.device != self.device):
-            raise ValueError(f"poses on {lig_pos.device}, evaluator built for {self.device}")
+        check_poses(self.n, self.n_a, self.device, lig_pos, None, "evaluator")
 
     def pairwise_rmsd(self, lig_pos: torch.Tensor) -> torch.Tensor:
         """lig_pos [S, n, 3] -> [S, S] symmetry-corrected RMSD of every pair of poses (no centring, no alignment, the minimum over

@@ -22,9 +22,10 @@ from __future__ import annotations
 
 import csv
 import dataclasses
+import functools
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -71,6 +72,12 @@ class ComplexResult:
     #                                                      poses (host tensors)
     interaction_reference: Optional["InteractionProfile"] = None  # interaction_profile with evaluate=True: the profile of the input pose
 
+    def clear(self):
+        """A stage of the row failed: every result goes back to its default.  What says which row it was and why it ended stays."""
+        for f in dataclasses.fields(self):
+            if f.name not in ("name", "skipped", "pockets", "original_center"):
+                setattr(self, f.name, [] if f.name == "files" else None)
+
 
 def _none(v):
     return None if v is None or str(v).strip() == "" or str(v).strip().lower() in ("nan", "none") else v
@@ -103,18 +110,25 @@ def _esm_rows(esm_embeddings, name):
     return None
 
 
-def build_row_graph(row: Dict, esm_embeddings=None, root: str = "", allow_zero_esm: bool = False, **graph_kwargs):
-    """One csv row -> complex graph (receptor.x = [residue index | 1280 ESM columns]).  The stored embedding may cover the
-    whole structure (per chain or concatenated): it is sliced with the kept-residue indices like the reference does
-    (inputs.slice_lm_embeddings).  A row without an embedding is an ERROR (-> the row is reported as skipped) unless
-    `allow_zero_esm` asks for a zero block, which is out of the model's training distribution and is announced loudly."""
+def read_row_texts(row: Dict, root: str = "") -> Tuple[str, str]:
+    """(PDB text, SDF text) of one csv row."""
     lig = row["ligand"]
     if not lig.lower().endswith(".sdf"):
         raise NotImplementedError(f"ligand '{lig}': only SDF files are read without rdkit")
     with open(os.path.join(root, row["experimental_protein"])) as f:
         pdb_text = f.read()
     with open(os.path.join(root, lig)) as f:
-        sdf_text = f.read()
+        return pdb_text, f.read()
+
+
+def build_row_graph(row: Dict, esm_embeddings=None, root: str = "", allow_zero_esm: bool = False, texts: Optional[Tuple[str, str]] = None,
+                    **graph_kwargs):
+    """One csv row -> complex graph (receptor.x = [residue index | 1280 ESM columns]).  The stored embedding may cover the
+    whole structure (per chain or concatenated): it is sliced with the kept-residue indices like the reference does
+    (inputs.slice_lm_embeddings).  A row without an embedding is an ERROR (-> the row is reported as skipped) unless
+    `allow_zero_esm` asks for a zero block, which is out of the model's training distribution and is announced loudly.
+    texts: read_row_texts(row, root) where the caller has read the files already."""
+    pdb_text, sdf_text = texts or read_row_texts(row, root)
     e = _esm_rows(esm_embeddings, row.get("esm_name", row["complex_name"]))
     if e is None and not allow_zero_esm:
         raise ValueError(f"{row['complex_name']}: no ESM embedding found (pass allow_zero_esm=True to run on a zero block)")
@@ -279,11 +293,12 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
         if i not in mine:
             continue
         split = shard == "samples" and world > 1
-        g = None
+        g = texts = None
         try:
             if row.get("pocket_error") is not None:
                 raise ValueError(row["pocket_error"])
-            g = build_row_graph(row, esm_embeddings, root, allow_zero_esm=allow_zero_esm, **(graph_kwargs or {}))
+            texts = read_row_texts(row, root)      # read once: the graph, the receptor forms of the stages and the writer share them
+            g = build_row_graph(row, esm_embeddings, root, allow_zero_esm=allow_zero_esm, texts=texts, **(graph_kwargs or {}))
         except Exception as e:      # noqa: BLE001 - the reference skips a failing complex and goes on (inference.py:282-287)
             res.skipped = f"{type(e).__name__}: {e}"
         if split and not _all_ok(dist, g is not None, device):
@@ -339,36 +354,23 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
                 ltraj = _gather_rows(dist, ltraj, sizes)
             if atraj is not None:
                 atraj = _gather_rows(dist, atraj, sizes)
-        scorer = scores = None
-        if score_poses is not None:       # on the gathered poses, in sample order: the ranking below may depend on it
-            try:
-                scorer = _scorer_row(row, root, g, device, flex, score_poses)
-                scores = scorer.score(lig, apos if flex else None)
-            except Exception as e:      # noqa: BLE001
-                res.skipped = f"scoring: {type(e).__name__}: {e}"
-            if split and not _all_ok(dist, scores is not None, device):
-                res.skipped = res.skipped or "skipped: scoring failed on another rank"
-            if res.skipped is not None:
+        # From here on every rank holds all poses and runs the same stages in the same order; each enabled stage is one _stage call,
+        # and with sample sharding one agreement of the ranks, so no stage may be skipped or reordered on one rank alone.
+        tools = _RowTools(row, g, device, flex, score_poses, texts)
+        stage = functools.partial(_stage, res, (lambda ok: _all_ok(dist, ok, device)) if split else None)
+        scores = minimized = searched = None
+        # scoring, minimisation and search run on the gathered poses in sample order: the ranking below may depend on them
+        if score_poses is not None:
+            scores = stage("scoring", "scoring failed on another rank", lambda: tools.score(lig, apos))
+            if scores is None:
                 continue
-        minimized = None
-        if minimize_poses is not None:    # on the gathered poses, in sample order: the ranking below may depend on it
-            try:
-                minimized = _minimize_row(row, root, g, device, flex, lig, apos, score_poses, minimize_poses)
-            except Exception as e:      # noqa: BLE001
-                res.skipped = f"minimisation: {type(e).__name__}: {e}"
-            if split and not _all_ok(dist, minimized is not None, device):
-                res.skipped = res.skipped or "skipped: minimisation failed on another rank"
-            if res.skipped is not None:
+        if minimize_poses is not None:
+            minimized = stage("minimisation", "minimisation failed on another rank", lambda: tools.minimize(lig, apos, minimize_poses))
+            if minimized is None:
                 continue
-        searched = None
-        if search_poses is not None:      # on the gathered poses, in sample order: the ranking below may depend on it
-            try:
-                searched = _search_row(row, root, g, device, flex, lig, apos, score_poses, search_poses)
-            except Exception as e:      # noqa: BLE001
-                res.skipped = f"search: {type(e).__name__}: {e}"
-            if split and not _all_ok(dist, searched is not None, device):
-                res.skipped = res.skipped or "skipped: the search failed on another rank"
-            if res.skipped is not None:
+        if search_poses is not None:
+            searched = stage("search", "the search failed on another rank", lambda: tools.search(lig, apos, search_poses))
+            if searched is None:
                 continue
         if rank_by == "score":
             order = rank_order(scores.total)
@@ -393,82 +395,56 @@ def _run_csv(csv_path, model, device, confidence_model, samples_per_complex, inf
         if searched is not None:
             res.searched = searched.index(order.cpu())
             res.searched_pos = res.searched.lig_pos
+        ranked, apos_ranked = lig[order], None if apos is None else apos[order]
         if evaluate:
-            metrics = None
-            try:
-                metrics = _evaluate_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order])
-            except Exception as e:      # noqa: BLE001
-                res.skipped = f"evaluation: {type(e).__name__}: {e}"
-            if split and not _all_ok(dist, metrics is not None, device):
-                res.skipped = res.skipped or "skipped: evaluation failed on another rank"
-            if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
+            res.metrics = stage("evaluation", "evaluation failed on another rank", lambda: tools.evaluate(ranked, apos_ranked))
+            if res.metrics is None:
                 continue
-            res.metrics = metrics
         if cluster_rmsd is not None:
-            clusters = None
-            try:
-                clusters = PoseEvaluator(g, device).cluster(lig[order], None, cluster_rmsd).cpu()
-            except Exception as e:      # noqa: BLE001
-                res.skipped = f"clustering: {type(e).__name__}: {e}"
-            if split and not _all_ok(dist, clusters is not None, device):
-                res.skipped = res.skipped or "skipped: clustering failed on another rank"
-            if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
+            res.clusters = stage("clustering", "clustering failed on another rank", lambda: tools.cluster(ranked, cluster_rmsd))
+            if res.clusters is None:
                 continue
-            res.clusters = clusters
         if resolve_clashes is not None:
-            refined = refined_scores = None
-            try:
-                done = _refine_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order], resolve_clashes,
-                                   evaluate)
-                if scorer is not None:
-                    refined_scores = scorer.score(done[0].lig_pos.to(lig.device), apos[order] if flex else None).cpu()
-                refined = done
-            except Exception as e:      # noqa: BLE001
-                res.skipped = f"clash relief: {type(e).__name__}: {e}"
-            if split and not _all_ok(dist, refined is not None, device):
-                res.skipped = res.skipped or "skipped: clash relief failed on another rank"
-            if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
+            done = stage("clash relief", "clash relief failed on another rank",
+                         lambda: tools.refine(ranked, apos_ranked, resolve_clashes, evaluate))
+            if done is None:
                 continue
-            res.refine, res.refined_metrics = refined
+            res.refine, res.refined_metrics, res.refined_scores = done
             res.refined_pos = res.refine.lig_pos
-            res.refined_scores = refined_scores
         if interaction_profile is not None:
-            found = None
-            try:
-                found = _interactions_row(row, root, g, device, flex, lig[order], None if apos is None else apos[order], score_poses,
-                                          interaction_profile, evaluate)
-            except Exception as e:      # noqa: BLE001
-                res.skipped = f"interaction profile: {type(e).__name__}: {e}"
-            if split and not _all_ok(dist, found is not None, device):
-                res.skipped = res.skipped or "skipped: the interaction profile failed on another rank"
-            if res.skipped is not None:
-                res.ligand_pos = res.confidence = res.order = res.metrics = res.clusters = res.scores = res.minimized = res.minimized_pos = res.searched = res.searched_pos = None
-                res.refined_pos = res.refine = res.refined_metrics = res.refined_scores = None
+            done = stage("interaction profile", "the interaction profile failed on another rank",
+                         lambda: tools.interactions(ranked, apos_ranked, interaction_profile, evaluate))
+            if done is None:
                 continue
-            res.interactions, res.interaction_reference = found
+            res.interactions, res.interaction_reference = done
         if save_visualisation:
             res.lig_traj = ltraj[order].cpu()
             res.atom_traj = atraj[order].cpu() if atraj is not None else None
-        if out_dir is not None:
-            ok = True
-            if rank == 0 or not split:
-                try:
-                    res.files = _write_row(out_dir, i, row, root, g, res, apos[order].cpu() if moved else None,
-                                           (graph_kwargs or {}).get("remove_hs", True))
-                except Exception as e:      # noqa: BLE001
-                    res.skipped, ok = f"writing: {type(e).__name__}: {e}", False
-            if split and not _all_ok(dist, ok, device):
-                res.skipped = res.skipped or "skipped: writing failed on rank 0"
-                ok = False
-            if not ok:
-                res.ligand_pos = res.confidence = res.order = res.lig_traj = res.atom_traj = res.clusters = None
-                res.refined_pos = res.refine = res.refined_metrics = res.scores = res.refined_scores = None
-                res.minimized = res.minimized_pos = res.searched = res.searched_pos = res.interactions = res.interaction_reference = None
-                res.files = []
+        if out_dir is not None:      # rank 0 alone writes the gathered poses; the others only agree on its outcome
+            files = stage("writing", "writing failed on rank 0",
+                          (lambda: tools.write(out_dir, i, res, apos_ranked.cpu() if moved else None, (graph_kwargs or {}).get("remove_hs", True)))
+                          if (rank == 0 or not split) else list)
+            if files is not None:
+                res.files = files
     return out
+
+
+def _stage(res: ComplexResult, agree, label: str, other: str, fn):
+    """One stage of a row of run_csv: what fn() returns (never None), or None where the row ends here.  An exception of fn skips the
+    row as `"{label}: ..."`; with sample sharding the ranks then agree (`agree(ok)`: True iff ok on every rank, one collective per
+    stage on every rank, whatever happened here) and a failure elsewhere skips the row as `"skipped: {other}"`.  A row that ends
+    loses every result it has so far (ComplexResult.clear)."""
+    value = None
+    try:
+        value = fn()
+    except Exception as e:      # noqa: BLE001 - the reference skips a failing complex and goes on (inference.py:282-287)
+        res.skipped = f"{label}: {type(e).__name__}: {e}"
+    if agree is not None and not agree(res.skipped is None):
+        res.skipped = res.skipped or f"skipped: {other}"
+    if res.skipped is None:
+        return value
+    res.clear()
+    return None
 
 
 def expand_pocket_rows(rows: List[Dict], root: str, device, config: PocketConfig, top_k: int = 1) -> List[Dict]:
@@ -497,93 +473,82 @@ def expand_pocket_rows(rows: List[Dict], root: str, device, config: PocketConfig
     return out
 
 
-def _write_row(out_dir, i, row, root, g, res: ComplexResult, apos, remove_hs) -> List[str]:
-    """outputs.write_complex for one processed row (ranked tensors of `res`)."""
-    with open(os.path.join(root, row["ligand"])) as f:
-        sdf_text = f.read()
-    pdb_text = None
-    if apos is not None or res.atom_traj is not None or isinstance(res.minimized, FlexMinimizeResult):
-        with open(os.path.join(root, row["experimental_protein"])) as f:
-            pdb_text = f.read()
-    return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), sdf_text, pdb_text, g, res.ligand_pos, res.confidence,
-                           apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs, clusters=res.clusters, order=res.order,
-                           refine=res.refine, pockets=res.pockets, pockets_docked=row.get("pockets_docked", 0), scores=res.scores,
-                           refined_scores=res.refined_scores, minimized=res.minimized, interactions=res.interactions,
-                           interaction_reference=res.interaction_reference, searched=res.searched)
+class _RowTools:
+    """What the stages of one processed row of run_csv share, each built when a stage first asks for it and at most once: the receptor
+    in its three forms and the tools on them.  A rigid row's receptor is the row's full PDB in the graph's frame, a flexible row's the
+    graph's atom nodes at each sample's own atom_pos (run_csv keeps an atom_pos for flexible rows only, so it is handed on as it is).
+    One method per stage; each returns host tensors.  texts: read_row_texts of the row."""
 
+    def __init__(self, row, g, device, flex, score_poses, texts):
+        self.row, self.g, self.device, self.flex, self.score_poses = row, g, device, flex, score_poses
+        self.pdb_text, self.sdf_text = texts
 
-def _evaluate_row(row, root, g, device, flex, lig, apos) -> PoseMetrics:
-    """PoseMetrics of the ranked poses of one row (see run_csv), on the host."""
-    if flex:
-        ev = PoseEvaluator(g, device)
-    else:
-        with open(os.path.join(root, row["experimental_protein"])) as f:
-            rec = PoseEvaluator.full_receptor(f.read(), g.original_center)
-        ev = PoseEvaluator(g, device, receptor=rec)
-    return ev.evaluate(lig, apos).cpu()
+    @functools.cached_property
+    def full_receptor(self):       # of the evaluation and the clash relief
+        return "graph" if self.flex else PoseEvaluator.full_receptor(self.pdb_text, self.g.original_center)
 
+    @functools.cached_property
+    def typed_receptor(self):      # of the physics score and everything that descends in it
+        return "graph" if self.flex else typed_receptor(self.pdb_text, self.g.original_center)
 
-def _refine_row(row, root, g, device, flex, lig, apos, config, evaluate):
-    """(RefineResult, PoseMetrics or None) of the ranked poses of one row (see run_csv), on the host.  The receptor is the one
-    _evaluate_row scores against."""
-    if flex:
-        rf = PoseRefiner(g, device, config=config)
-    else:
-        with open(os.path.join(root, row["experimental_protein"])) as f:
-            rec = PoseEvaluator.full_receptor(f.read(), g.original_center)
-        rf = PoseRefiner(g, device, receptor=rec, config=config)
-    out = rf.refine(lig, apos if flex else None)
-    metrics = _evaluate_row(row, root, g, device, flex, out.lig_pos, apos) if evaluate else None
-    return out.cpu(), metrics
+    @functools.cached_property
+    def residues(self):
+        return receptor_residues(self.pdb_text)
 
+    @functools.cached_property
+    def evaluator(self) -> PoseEvaluator:
+        return PoseEvaluator(self.g, self.device, receptor=self.full_receptor)
 
-def _scorer_row(row, root, g, device, flex, config) -> PoseScorer:
-    """The PoseScorer of one row (see run_csv).  The receptor is the one _evaluate_row scores against."""
-    if flex:
-        return PoseScorer(g, device, config=config)
-    with open(os.path.join(root, row["experimental_protein"])) as f:
-        rec = typed_receptor(f.read(), g.original_center)
-    return PoseScorer(g, device, receptor=rec, config=config)
+    @functools.cached_property
+    def scorer(self) -> PoseScorer:
+        """The one PoseScorer of the row: the minimiser and the searcher run on its tables (score_poses None: the default constants,
+        which is what they would build themselves)."""
+        return PoseScorer(self.g, self.device, receptor=self.typed_receptor, config=self.score_poses)
 
+    def score(self, lig, apos) -> PoseScores:
+        """On the poses' device: the ranking reads it there."""
+        return self.scorer.score(lig, apos)
 
-def _interactions_row(row, root, g, device, flex, lig, apos, score_config, config, evaluate):
-    """(InteractionProfile of the ranked poses of one row, InteractionProfile of the input pose or None), on the host (see run_csv).  The
-    receptor is the one _scorer_row takes, with its residues."""
-    if flex:
-        pf = InteractionProfiler(g, device, config=config, score_config=score_config)
-    else:
-        with open(os.path.join(root, row["experimental_protein"])) as f:
-            pdb_text = f.read()
-        pf = InteractionProfiler(g, device, receptor=(typed_receptor(pdb_text, g.original_center), receptor_residues(pdb_text)),
-                                 config=config, score_config=score_config)
-    out = pf.profile(lig, apos if flex else None).cpu()
-    ref = pf.profile(torch.as_tensor(g["ligand"].pos).float()[None].to(lig.device)).cpu() if evaluate else None
-    return out, ref
+    def minimize(self, lig, apos, config) -> MinimizeResult:
+        """A flexible row with config.sidechains: the FlexMinimizeResult of the joint minimisation."""
+        if self.flex and config.sidechains:
+            return FlexPoseMinimizer(self.g, self.device, score_config=self.score_poses, config=config).minimize(lig, apos).cpu()
+        return PoseMinimizer(self.g, self.device, config=config, scorer=self.scorer).minimize(lig, apos).cpu()
 
+    def search(self, lig, apos, config) -> SearchResult:
+        return PoseSearcher(self.g, self.device, config=config, scorer=self.scorer).search(lig, apos).cpu()
 
-def _minimize_row(row, root, g, device, flex, lig, apos, score_config, config) -> MinimizeResult:
-    """MinimizeResult of the poses of one row in sample order (see run_csv), on the host.  The receptor is the one _scorer_row takes.
-    A flexible row with config.sidechains: the FlexMinimizeResult of the joint minimisation."""
-    if flex and config.sidechains:
-        return FlexPoseMinimizer(g, device, score_config=score_config, config=config).minimize(lig, apos).cpu()
-    if flex:
-        mz = PoseMinimizer(g, device, score_config=score_config, config=config)
-    else:
-        with open(os.path.join(root, row["experimental_protein"])) as f:
-            rec = typed_receptor(f.read(), g.original_center)
-        mz = PoseMinimizer(g, device, receptor=rec, score_config=score_config, config=config)
-    return mz.minimize(lig, apos if flex else None).cpu()
+    def evaluate(self, lig, apos) -> PoseMetrics:
+        return self.evaluator.evaluate(lig, apos).cpu()
 
+    def cluster(self, lig, cutoff) -> PoseClusters:
+        return PoseEvaluator(self.g, self.device).cluster(lig, None, cutoff).cpu()
 
-def _search_row(row, root, g, device, flex, lig, apos, score_config, config) -> SearchResult:
-    """SearchResult of the poses of one row in sample order (see run_csv), on the host.  The receptor is the one _scorer_row takes."""
-    if flex:
-        ps = PoseSearcher(g, device, score_config=score_config, config=config)
-    else:
-        with open(os.path.join(root, row["experimental_protein"])) as f:
-            rec = typed_receptor(f.read(), g.original_center)
-        ps = PoseSearcher(g, device, receptor=rec, score_config=score_config, config=config)
-    return ps.search(lig, apos if flex else None).cpu()
+    def refine(self, lig, apos, config, evaluate):
+        """(RefineResult, PoseMetrics of the refined poses or None, their PoseScores or None)."""
+        out = PoseRefiner(self.g, self.device, receptor=self.full_receptor, config=config).refine(lig, apos)
+        metrics = self.evaluate(out.lig_pos, apos) if evaluate else None
+        scores = self.score(out.lig_pos, apos).cpu() if self.score_poses is not None else None
+        return out.cpu(), metrics, scores
+
+    def interactions(self, lig, apos, config, evaluate):
+        """(InteractionProfile of the poses, InteractionProfile of the input pose or None)."""
+        rec = "graph" if self.flex else (self.typed_receptor, self.residues)
+        pf = InteractionProfiler(self.g, self.device, receptor=rec, config=config, score_config=self.score_poses)
+        out = pf.profile(lig, apos).cpu()
+        ref = pf.profile(torch.as_tensor(self.g["ligand"].pos).float()[None].to(lig.device)).cpu() if evaluate else None
+        return out, ref
+
+    def write(self, out_dir, i, res: ComplexResult, apos, remove_hs) -> List[str]:
+        """outputs.write_complex of the ranked tensors of `res`."""
+        row = self.row
+        needs_pdb = apos is not None or res.atom_traj is not None or isinstance(res.minimized, FlexMinimizeResult)
+        return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), self.sdf_text, self.pdb_text if needs_pdb else None, self.g,
+                               res.ligand_pos, res.confidence, apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs,
+                               clusters=res.clusters, order=res.order, refine=res.refine, pockets=res.pockets,
+                               pockets_docked=row.get("pockets_docked", 0), scores=res.scores, refined_scores=res.refined_scores,
+                               minimized=res.minimized, interactions=res.interactions,
+                               interaction_reference=res.interaction_reference, searched=res.searched)
 
 
 def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:

@@ -50,7 +50,8 @@ import numpy as np
 import torch
 
 from .inputs import AMINO_ACIDS, parse_pdb
-from .scoring import ScoreConfig, TypedReceptor, _ramp, _weighted, type_ligand, type_receptor_graph
+from .pose_args import check_poses
+from .scoring import ScoreConfig, TypedReceptor, _ramp, _weighted, typed_tables
 
 CONTACT, HYDROPHOBIC_BIT, HBOND_BIT = 1, 2, 4
 
@@ -260,44 +261,25 @@ class InteractionProfiler:
         self.device = torch.device(device)
         self.n = int(graph["ligand"].pos.shape[0])
         self.n_a = int(graph["atom"].pos.shape[0])
-        lig_r, lig_f = type_ligand(graph)
         self.receptor_from_graph = isinstance(receptor, str)
-        if self.receptor_from_graph:
-            if receptor != "graph":
-                raise ValueError(f"receptor: 'graph' or (TypedReceptor, ResidueTable), got {receptor!r}")
-            rec_r, rec_f = type_receptor_graph(graph)
-            coords = torch.as_tensor(graph["atom"].pos).float().reshape(-1, 3).numpy()
-            table = graph_residues(graph)
-        else:
-            if not (isinstance(receptor, (tuple, list)) and len(receptor) == 2 and isinstance(receptor[0], TypedReceptor)
-                    and isinstance(receptor[1], ResidueTable)):
-                raise ValueError(f"receptor: 'graph' or (TypedReceptor, ResidueTable), got {type(receptor).__name__}")
-            typed, table = receptor
-            coords = np.asarray(typed.coords, dtype=np.float32).reshape(-1, 3)
-            rec_r, rec_f = np.asarray(typed.radii, dtype=np.float32), np.asarray(typed.flags, dtype=np.uint8)
-        table.check(len(rec_r))
+        pair = "(TypedReceptor, ResidueTable)"
+        if not self.receptor_from_graph and not (isinstance(receptor, (tuple, list)) and len(receptor) == 2
+                                                 and isinstance(receptor[0], TypedReceptor) and isinstance(receptor[1], ResidueTable)):
+            raise ValueError(f"receptor: 'graph' or {pair}, got {type(receptor).__name__}")
         # untyped atoms are dropped; the rows a per-sample atom_pos keeps are `self.keep`
-        keep = np.asarray(rec_r) >= 0
+        cpu, keep = typed_tables(graph, receptor if self.receptor_from_graph else receptor[0], drop_untyped_graph_atoms=True, expects=pair)
+        table = graph_residues(graph) if self.receptor_from_graph else receptor[1]
+        table.check(len(keep))
         self.keep = torch.from_numpy(np.nonzero(keep)[0])
         self.table = table.keep(keep)
         self.labels = list(self.table.labels)
         self.n_res = len(self.labels)
-        cpu = {"lig_r": torch.from_numpy(np.ascontiguousarray(lig_r)), "lig_f": torch.from_numpy(np.ascontiguousarray(lig_f)),
-               "rec": torch.from_numpy(np.ascontiguousarray(coords[keep])), "rec_r": torch.from_numpy(np.ascontiguousarray(rec_r[keep])),
-               "rec_f": torch.from_numpy(np.ascontiguousarray(rec_f[keep])),
-               "ptr": torch.from_numpy(np.ascontiguousarray(self.table.ptr, dtype=np.int32)), "keep": self.keep}
+        cpu.update(ptr=torch.from_numpy(np.ascontiguousarray(self.table.ptr, dtype=np.int32)), keep=self.keep)
         self._cpu = cpu
         self._dev = cpu if self.device.type == "cpu" else {k: v.to(self.device) for k, v in cpu.items()}
 
     def _check(self, lig_pos, atom_pos):
-        if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
-            raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")
-        if atom_pos is not None and (atom_pos.dim() != 3 or atom_pos.shape[1:] != (self.n_a, 3) or atom_pos.shape[0] != lig_pos.shape[0]):
-            raise ValueError(f"atom_pos: expected [S, {self.n_a}, 3], got {tuple(atom_pos.shape)}")
-        if lig_pos.is_cuda and (self.device.type != "cuda" or lig_pos.device != self.device):
-            raise ValueError(f"poses on {lig_pos.device}, profiler built for {self.device}")
-        if atom_pos is not None and atom_pos.device != lig_pos.device:
-            raise ValueError("lig_pos and atom_pos on different devices")
+        check_poses(self.n, self.n_a, self.device, lig_pos, atom_pos, "profiler")
 
     def profile(self, lig_pos: torch.Tensor, atom_pos: Optional[torch.Tensor] = None) -> InteractionProfile:
         """lig_pos [S, n, 3] (flexible runs: atom_pos [S, n_a, 3], each sample's own receptor; used by a graph receptor only) ->

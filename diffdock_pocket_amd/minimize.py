@@ -43,6 +43,7 @@ from typing import List, Optional
 import torch
 
 from .descent import DescentBuffers, descend_hip, descend_torch, ligand_torsions
+from .pose_args import check_anchor
 from .sampler import rotate_index_lists
 from .scoring import PoseScorer, PoseScores, ScoreConfig, score_torch
 
@@ -100,16 +101,24 @@ def _warn_once(msg: str):
 class PoseMinimizer:
     """Minimisation of the poses of one complex in the physics score (see the module docstring).
 
-    graph, device, receptor, score_config: as PoseScorer - receptor "graph" (the graph's atom nodes; each sample's own atom_pos when one
-    is handed in: flexible runs) or a scoring.TypedReceptor in the graph's frame.  One PoseScorer is built and its tables are reused."""
+    graph, device, receptor, score_config: as PoseScorer - receptor None or "graph" (the graph's atom nodes; each sample's own atom_pos
+    when one is handed in: flexible runs) or a scoring.TypedReceptor in the graph's frame.  One PoseScorer is built and its tables are
+    reused.  scorer: a PoseScorer of the same graph on the same device, in place of receptor and score_config: its tables and config
+    are used and none is built."""
 
-    def __init__(self, graph, device="cpu", receptor="graph", score_config: Optional[ScoreConfig] = None,
-                 config: Optional[MinimizeConfig] = None):
+    def __init__(self, graph, device="cpu", receptor=None, score_config: Optional[ScoreConfig] = None,
+                 config: Optional[MinimizeConfig] = None, scorer: Optional[PoseScorer] = None):
         self.config = config or MinimizeConfig()
         if not (self.config.restraint >= 0) or self.config.iterations < 0:
             raise ValueError("MinimizeConfig: restraint and iterations must not be negative")
         self.device = torch.device(device)
-        self.scorer = PoseScorer(graph, device, receptor=receptor, config=score_config)
+        if scorer is None:
+            scorer = PoseScorer(graph, device, receptor="graph" if receptor is None else receptor, config=score_config)
+        elif receptor is not None or score_config is not None:
+            raise ValueError("scorer: given in place of receptor and score_config, not with them")
+        elif scorer.device != self.device:
+            raise ValueError(f"scorer built for {scorer.device}, minimiser for {self.device}")
+        self.scorer = scorer
         self.score_config = self.scorer.config
         self.n, self.n_a = self.scorer.n, self.scorer.n_a
         self.bonds, self.mask_rotate = ligand_torsions(graph)
@@ -141,8 +150,7 @@ class PoseMinimizer:
         self._check(lig_pos, atom_pos)
         x = lig_pos.float().contiguous()
         a = x if anchor is None else anchor.float().contiguous()
-        if a.shape != x.shape or a.device != x.device:
-            raise ValueError("anchor: the shape and device of lig_pos")
+        check_anchor(x, a)
         S = x.shape[0]
         if not x.is_cuda:
             t, rec = self._tables(x, atom_pos)
@@ -182,8 +190,7 @@ class PoseMinimizer:
         self._check(lig_pos, atom_pos)
         x = lig_pos.float().contiguous()
         a = anchor.float().contiguous()
-        if a.shape != x.shape or a.device != x.device:
-            raise ValueError("anchor: the shape and device of lig_pos")
+        check_anchor(x, a)
         S = x.shape[0]
         if tuple(step.shape) != (S,) or tuple(accepted.shape) != (S,) or step.device != x.device or accepted.device != x.device:
             raise ValueError("step, accepted: one entry per pose, on the poses' device")

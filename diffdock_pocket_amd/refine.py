@@ -32,6 +32,7 @@ import torch
 
 from .descent import DescentBuffers, descend_hip, descend_torch, direction_torch, ligand_torsions  # noqa: F401 (the last two: re-exported)
 from .evaluation import OVERLAP_DISTANCE, PoseEvaluator
+from .pose_args import check_anchor, check_poses
 from .sampler import rotate_index_lists
 
 
@@ -150,14 +151,7 @@ class PoseRefiner:
 
     # ---- checks
     def _check(self, lig_pos, atom_pos):
-        if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
-            raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")
-        if atom_pos is not None and (atom_pos.dim() != 3 or atom_pos.shape[1:] != (self.n_a, 3) or atom_pos.shape[0] != lig_pos.shape[0]):
-            raise ValueError(f"atom_pos: expected [S, {self.n_a}, 3], got {tuple(atom_pos.shape)}")
-        if lig_pos.is_cuda and (self.device.type != "cuda" or lig_pos.device != self.device):
-            raise ValueError(f"poses on {lig_pos.device}, refiner built for {self.device}")
-        if atom_pos is not None and atom_pos.device != lig_pos.device:
-            raise ValueError("lig_pos and atom_pos on different devices")
+        check_poses(self.n, self.n_a, self.device, lig_pos, atom_pos, "refiner")
 
     def _tables(self, lig_pos, atom_pos):
         apos = None if atom_pos is None else atom_pos.float().contiguous()
@@ -173,8 +167,7 @@ class PoseRefiner:
         self._check(lig_pos, atom_pos)
         x = lig_pos.float().contiguous()
         a = x if anchor is None else anchor.float().contiguous()
-        if a.shape != x.shape or a.device != x.device:
-            raise ValueError("anchor: the shape and device of lig_pos")
+        check_anchor(x, a)
         lig_r, rec, rec_r = self._tables(x, atom_pos)
         if not x.is_cuda:
             return energy_torch(x, a, lig_r, rec, rec_r, self.self_pairs, self.overlap, self.config.restraint)

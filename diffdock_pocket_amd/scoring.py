@@ -55,6 +55,7 @@ import numpy as np
 import torch
 
 from .inputs import AMINO_ACIDS, ATOM_TYPE_3, ATOMIC_NUMBER, ATOMIC_NUMS, FORMAL_CHARGE, HYBRIDIZATION, NUM_H, parse_pdb, safe_index
+from .pose_args import check_poses
 from .refine import build_self_pairs, ligand_torsions
 
 ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
@@ -248,6 +249,30 @@ def typed_receptor(pdb_text: str, original_center) -> TypedReceptor:
     return TypedReceptor(coords, radii, flags)
 
 
+def typed_tables(graph, receptor, drop_untyped_graph_atoms: bool = False, expects: str = "a TypedReceptor"):
+    """The host tables of a complex's typed atoms: ({"lig_r" [n] fp32, "lig_f" [n] uint8, "rec" [m', 3] fp32, "rec_r" [m'] fp32, "rec_f"
+    [m'] uint8}, keep [m] bool, the typed ones of all m receptor atoms).  receptor: "graph" (the graph's atom nodes) or a TypedReceptor
+    in the graph's frame; `expects` names the other form in the ValueError of anything else."""
+    lig_r, lig_f = type_ligand(graph)
+    if isinstance(receptor, str):
+        if receptor != "graph":
+            raise ValueError(f"receptor: 'graph' or {expects}, got {receptor!r}")
+        rec_r, rec_f = type_receptor_graph(graph)
+        rec = torch.as_tensor(graph["atom"].pos).float().reshape(-1, 3).numpy()
+    else:
+        if not isinstance(receptor, TypedReceptor):
+            raise ValueError(f"receptor: 'graph' or {expects}, got {type(receptor).__name__}")
+        rec = np.asarray(receptor.coords, dtype=np.float32).reshape(-1, 3)
+        rec_r, rec_f = np.asarray(receptor.radii, dtype=np.float32), np.asarray(receptor.flags, dtype=np.uint8)
+    keep = np.asarray(rec_r) >= 0
+    # Untyped atoms take part in nothing and are dropped - except, for the scorer, those of a graph receptor: a per-sample atom_pos has
+    # all n_a rows and is handed to the kernel as it is.  The profiler drops them there too and indexes atom_pos with `keep`.
+    if drop_untyped_graph_atoms or not isinstance(receptor, str):
+        rec, rec_r, rec_f = rec[keep], rec_r[keep], rec_f[keep]
+    tables = {"lig_r": lig_r, "lig_f": lig_f, "rec": rec, "rec_r": rec_r, "rec_f": rec_f}
+    return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in tables.items()}, keep
+
+
 # ---------------------------------------------------------------------------------------------- the PyTorch fp64 form
 def _ramp(s, good, bad):
     return torch.where(s <= good, torch.ones_like(s), torch.where(s < bad, (bad - s) / (bad - good), torch.zeros_like(s)))
@@ -338,38 +363,18 @@ class PoseScorer:
         self.device = torch.device(device)
         self.n = int(graph["ligand"].pos.shape[0])
         self.n_a = int(graph["atom"].pos.shape[0])
-        lig_r, lig_f = type_ligand(graph)
         self.receptor_from_graph = isinstance(receptor, str)
-        if self.receptor_from_graph:
-            if receptor != "graph":
-                raise ValueError(f"receptor: 'graph' or a TypedReceptor, got {receptor!r}")
-            rec_r, rec_f = type_receptor_graph(graph)
-            rec = torch.as_tensor(graph["atom"].pos).float().reshape(-1, 3)
-        else:
-            if not isinstance(receptor, TypedReceptor):
-                raise ValueError(f"receptor: 'graph' or a TypedReceptor, got {type(receptor).__name__}")
-            keep = np.asarray(receptor.radii) >= 0
-            rec = torch.as_tensor(np.asarray(receptor.coords, dtype=np.float32).reshape(-1, 3)[keep])
-            rec_r, rec_f = np.asarray(receptor.radii, dtype=np.float32)[keep], np.asarray(receptor.flags, dtype=np.uint8)[keep]
+        cpu, _ = typed_tables(graph, receptor)
         bonds, mask_rotate = ligand_torsions(graph)
         self.n_tor = int(bonds.shape[0])
         self.tor_divisor = 1.0 + self.config.w_torsion * self.n_tor
         self.self_pairs = build_self_pairs(self.n, torch.as_tensor(graph["ligand", "ligand"].edge_index).numpy(), mask_rotate.numpy())
-        cpu = {"lig_r": torch.from_numpy(np.ascontiguousarray(lig_r)), "lig_f": torch.from_numpy(np.ascontiguousarray(lig_f)),
-               "rec": rec.contiguous(), "rec_r": torch.from_numpy(np.ascontiguousarray(rec_r)),
-               "rec_f": torch.from_numpy(np.ascontiguousarray(rec_f)), "pairs": self.self_pairs.contiguous()}
+        cpu["pairs"] = self.self_pairs.contiguous()
         self._cpu = cpu
         self._dev = cpu if self.device.type == "cpu" else {k: v.to(self.device) for k, v in cpu.items()}
 
     def _check(self, lig_pos, atom_pos):
-        if lig_pos.dim() != 3 or lig_pos.shape[1:] != (self.n, 3):
-            raise ValueError(f"lig_pos: expected [S, {self.n}, 3], got {tuple(lig_pos.shape)}")
-        if atom_pos is not None and (atom_pos.dim() != 3 or atom_pos.shape[1:] != (self.n_a, 3) or atom_pos.shape[0] != lig_pos.shape[0]):
-            raise ValueError(f"atom_pos: expected [S, {self.n_a}, 3], got {tuple(atom_pos.shape)}")
-        if lig_pos.is_cuda and (self.device.type != "cuda" or lig_pos.device != self.device):
-            raise ValueError(f"poses on {lig_pos.device}, scorer built for {self.device}")
-        if atom_pos is not None and atom_pos.device != lig_pos.device:
-            raise ValueError("lig_pos and atom_pos on different devices")
+        check_poses(self.n, self.n_a, self.device, lig_pos, atom_pos, "scorer")
 
     def score(self, lig_pos: torch.Tensor, atom_pos: Optional[torch.Tensor] = None, with_grad: bool = False) -> PoseScores:
         """lig_pos [S, n, 3] (flexible runs: atom_pos [S, n_a, 3], each sample's own receptor; used by a graph receptor only) ->

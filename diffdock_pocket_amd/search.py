@@ -62,7 +62,7 @@ import torch
 
 from .minimize import MinimizeConfig, PoseMinimizer, _warn_once
 from .sampler import modify_conformer, modify_conformer_hip
-from .scoring import PoseScores, ScoreConfig
+from .scoring import PoseScorer, PoseScores, ScoreConfig
 
 
 @dataclass
@@ -162,11 +162,11 @@ def select_torch(best_e, best_pos, best_cycle, R: int):
 class PoseSearcher:
     """The search around the poses of one complex (see the module docstring).
 
-    graph, device, receptor, score_config: as PoseMinimizer.  One PoseMinimizer is built (iterations = config.iterations, restraint =
-    config.restraint, the default step constants) and its tables are reused."""
+    graph, device, receptor, score_config, scorer: as PoseMinimizer.  One PoseMinimizer is built (iterations = config.iterations,
+    restraint = config.restraint, the default step constants) and its tables are reused."""
 
-    def __init__(self, graph, device="cpu", receptor="graph", score_config: Optional[ScoreConfig] = None,
-                 config: Optional[SearchConfig] = None):
+    def __init__(self, graph, device="cpu", receptor=None, score_config: Optional[ScoreConfig] = None,
+                 config: Optional[SearchConfig] = None, scorer: Optional[PoseScorer] = None):
         c = self.config = config or SearchConfig()
         if c.replicas < 1 or c.cycles < 0 or c.iterations < 0:
             raise ValueError("SearchConfig: replicas must be at least 1, cycles and iterations must not be negative")
@@ -174,7 +174,7 @@ class PoseSearcher:
             raise ValueError("SearchConfig: temperature must be positive and finite")
         if not (c.restraint >= 0) or min(c.sigma_tr, c.sigma_rot, c.sigma_tor) < 0:
             raise ValueError("SearchConfig: restraint and the sigmas must not be negative")
-        self.minimizer = PoseMinimizer(graph, device, receptor=receptor, score_config=score_config,
+        self.minimizer = PoseMinimizer(graph, device, receptor=receptor, score_config=score_config, scorer=scorer,
                                        config=MinimizeConfig(iterations=c.iterations, restraint=c.restraint))
         self.device = self.minimizer.device
         self.scorer = self.minimizer.scorer
