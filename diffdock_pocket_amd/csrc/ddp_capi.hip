@@ -6,6 +6,7 @@
 
 #include "ddp_hip.h"
 #include "ddp_internal.h"
+#include "ddp_conv_deal.h"
 
 // The layout of ABI version 17.  ddp_score_form_t sits in the four argument structs where their eleven doubles used to be spelled
 // out: a caller compiled against the flat fields and this library agree on every byte.
@@ -25,6 +26,29 @@ int ddp_fail(int code, const char* msg) {
 int ddp_fail_hip(hipError_t err, const char* where) {
   snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(err));
   return (int)err;
+}
+
+// DDP_CONV_DEAL in the environment (read at the first conv launch), or the value written here (tests, A/B tools): the tiles per chunk of
+// the conv launches' chunk-cyclic tile order (ddp_deal_tile, csrc/ddp_conv_deal.h), 0 = one contiguous range of tiles per XCD.
+// Results do not depend on it.
+#define DDP_CONV_DEAL_DEFAULT 8
+extern "C" int ddp_conv_deal;
+int ddp_conv_deal = -1;
+int ddp_conv_deal_chunk(void) {
+  if (ddp_conv_deal < 0) {
+    const char* e = getenv("DDP_CONV_DEAL");
+    const int v = (e && e[0] >= '0' && e[0] <= '9') ? atoi(e) : DDP_CONV_DEAL_DEFAULT;
+    ddp_conv_deal = (v > 4096) ? 4096 : v;
+  }
+  return (ddp_conv_deal > 4096) ? 4096 : ddp_conv_deal;
+}
+// the tile of workgroup `id` in a launch of `total` tiles dealt in chunks of c (the device's own function; tests/test_conv_deal_cpu.py)
+extern "C" int ddp_conv_deal_tile(int id, int total, int c) {
+  if (total < 1 || id < 0 || id >= total || c < 0 || c > 4096) {
+    ddp_fail(DDP_EINVAL, "ddp_conv_deal_tile: id in [0, total), c in [0, 4096]");
+    return -1;
+  }
+  return ddp_deal_tile(id, total, c);
 }
 
 int ddp_shape_rows_min_lds = 0;

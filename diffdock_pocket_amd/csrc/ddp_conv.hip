@@ -1566,6 +1566,7 @@ static int launch_conv(K kernel, ConvLaunch& L, const ddp_conv_task_t* tasks, in
   const ddp_conv_shape_t* shape = &L.shape;
   L.ntasks = 0;
   L.dev_counts = 0;
+  L.deal_c = ddp_conv_deal_chunk();
   int tiles = 0;
   for (int i = 0; i < ntasks; ++i) {
     if (tasks[i].n_edges <= 0) continue;  // an empty conv sends no message (models/score_model.py:109-111)

@@ -8,6 +8,7 @@
 
 #include "ddp_hip.h"
 #include "ddp_internal.h"
+#include "ddp_conv_deal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -65,6 +66,7 @@ struct ConvLaunch {
   int tv_off;   // 32-edge kernels: row stride (floats) of the LDS message tile; unused by the 64-edge kernel
   int ntasks;
   int dev_counts;   // some task carries n_edges_dev: tile table rebuilt on the device (conv_tile)
+  int deal_c;       // tiles per chunk of the chunk-cyclic tile order (ddp_deal_tile; ddp_conv_deal of include/ddp_hip.h), 0 = one range per XCD
   int tile_start[DDP_MAX_TASKS + 1];
   ddp_conv_task_t task[DDP_MAX_TASKS];
 };
@@ -115,22 +117,16 @@ __device__ __forceinline__ void build_features(const ddp_block_t& B, const ddp_c
   }
 }
 
-// workgroup id -> tile.  XCD-aware tile order: workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2), so
-// id -> tile is remapped to give every XCD one contiguous range of tiles: neighbouring tiles share source nodes (G rows,
-// x rows) and all tiles of a conv share its packed weights.
-__device__ __forceinline__ int xcd_tile(int ntl) {
-  const int q = ntl >> 3, rem = ntl & 7, x = (int)blockIdx.x & 7;
-  return ((x < rem) ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + ((int)blockIdx.x >> 3);
-}
+// workgroup id -> tile: ddp_deal_tile of ddp_conv_deal.h
 
 // workgroup -> (task, first edge, valid edges).  Host-side counts: the tile table of the launch.  Device-side counts
 // (ConvLaunch::dev_counts; include/ddp_hip.h "Device-side counts"): the grid covers the tasks' CAPACITIES, every workgroup
-// reads the actual edge counts, rebuilds the tile table from them and leaves if it lies behind the last tile - the XCD-aware
+// reads the actual edge counts, rebuilds the tile table from them and leaves if it lies behind the last tile - the tile
 // order is then the one of a launch of exactly that many tiles.
 template <int ET>
 __device__ __forceinline__ bool conv_tile(const ConvLaunch& L, int& t, int& p0, int& nvalid) {
   if (!L.dev_counts) {
-    const int tile = xcd_tile((int)gridDim.x);
+    const int tile = ddp_deal_tile((int)blockIdx.x, (int)gridDim.x, L.deal_c);
     t = 0;
     while (t + 1 < L.ntasks && tile >= L.tile_start[t + 1]) ++t;
     p0 = (tile - L.tile_start[t]) * ET;
@@ -152,7 +148,7 @@ __device__ __forceinline__ bool conv_tile(const ConvLaunch& L, int& t, int& p0, 
 #pragma unroll
   for (int i = 0; i < DDP_MAX_TASKS; ++i) total += (cnt[i] + ET - 1) / ET;
   if ((int)blockIdx.x >= total) return false;
-  const int tile = xcd_tile(total);
+  const int tile = ddp_deal_tile((int)blockIdx.x, total, L.deal_c);
   int base = 0;
   t = 0;
   p0 = 0;

@@ -778,6 +778,7 @@ int ddp_conv_rows_plan(const ddp_conv_shape_t* shape, const ddp_conv_task_t* tas
   L.tv_off = 0;
   L.ntasks = 0;
   L.dev_counts = 0;
+  L.deal_c = ddp_conv_deal_chunk();
   const int NS = (sc == 60) ? 12 : 6, nct1 = shape->nct1;
   if (nct1 != (shape->hid + 31) / 32) return ddp_fail(DDP_EINVAL, "ddp_conv_rows: nct1");
   int nts = nct1, frows = 0;

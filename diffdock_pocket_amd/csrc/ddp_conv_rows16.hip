@@ -37,6 +37,52 @@
 #include "ddp_conv_rows_common.h"
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// Diagnostic build only (-DDDP_DEAL_STAMPS, tools/conv_deal_xcd.py; absent from the product): where and when every workgroup ran.  Eight
+// words per workgroup id - XCC id, task, tile, start; then the end of each of its four waves - on the 100 MHz clock all XCDs share.
+#ifdef DDP_DEAL_STAMPS
+#define DS_WGS 16384
+__device__ unsigned long long ddp_deal_stamp_buf[(size_t)DS_WGS * 8];
+__device__ __forceinline__ unsigned long long ddp_deal_now() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#define DSTAMP_BEGIN(task_, tile_)                                                                     \
+  do {                                                                                                 \
+    const unsigned long long t_ = ddp_deal_now();                                                      \
+    unsigned xcc_;                                                                                     \
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_));                                \
+    if (threadIdx.x == 0 && blockIdx.x < DS_WGS) {                                                     \
+      unsigned long long* d_ = ddp_deal_stamp_buf + (size_t)blockIdx.x * 8;                            \
+      d_[0] = (unsigned long long)(xcc_ & 15u) + 1ull;                                                 \
+      d_[1] = (unsigned long long)(task_);                                                             \
+      d_[2] = (unsigned long long)(tile_);                                                             \
+      d_[3] = t_;                                                                                      \
+    }                                                                                                  \
+  } while (0)
+#define DSTAMP_END()                                                                                   \
+  do {                                                                                                 \
+    const unsigned long long t_ = ddp_deal_now();                                                      \
+    if ((threadIdx.x & 63) == 0 && blockIdx.x < DS_WGS) ddp_deal_stamp_buf[(size_t)blockIdx.x * 8 + 4 + (threadIdx.x >> 6)] = t_; \
+  } while (0)
+extern "C" int ddp_debug_read_deal_stamps(unsigned long long* host_dst, int n_wgs) {
+  if (n_wgs < 0 || n_wgs > DS_WGS) return -1;
+  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ddp_deal_stamp_buf), sizeof(unsigned long long) * 8 * (size_t)n_wgs);
+}
+extern "C" int ddp_debug_clear_deal_stamps(void) {
+  void* p = nullptr;
+  hipError_t e = hipGetSymbolAddress(&p, HIP_SYMBOL(ddp_deal_stamp_buf));
+  if (e != hipSuccess) return (int)e;
+  return (int)hipMemset(p, 0, sizeof(unsigned long long) * 8 * (size_t)DS_WGS);
+}
+#else
+#define DSTAMP_BEGIN(task_, tile_) do {} while (0)
+#define DSTAMP_END() do {} while (0)
+#endif
+
 __device__ __forceinline__ f32x4 r16_splat4(float v) { return f32x4{v, v, v, v}; }
 
 // acc[2 rt + ct] += A(h of row tile rt, k32 steps of piece P) x B(piece in LDS: fragments [k32 step][ct][plane]); three split products
@@ -440,6 +486,7 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
   const int tid = threadIdx.x;
   int ti, p0, nvalid;
   if (!conv_tile<ROWS_ET>(L, ti, p0, nvalid)) return;
+  DSTAMP_BEGIN(ti, p0 / ROWS_ET);
   const ddp_conv_task_t& T = L.task[ti];
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, n = lane & 15, g = lane >> 4;
   f32x4* ring = reinterpret_cast<f32x4*>(lds);
@@ -624,6 +671,7 @@ __device__ __forceinline__ void r16_body(const R16Launch& RL) {
         t = r16_segment<NS, 3, GF, DIRECT>(RL, B, bi, part, T, ah, al, ring, lbias, t, F, aux, rmask, src, nvw, wave, lane, nts);
     }
   }
+  DSTAMP_END();
 }
 
 template <int SZ, int GF>

@@ -59,4 +59,8 @@ static inline hipError_t ddp_need_lds(const void* kernel, int bytes, int* have) 
 extern int ddp_shape_rows_min_lds;      // ddp_conv_rows: dynamic LDS of a launch is at least this many bytes
 extern int ddp_shape_stage_a_pad;       // ddp_stage_a*: dynamic LDS added to the kernels' static LDS
 
+// Tiles per chunk of the conv launches' tile order (ddp_conv_deal of include/ddp_hip.h, resolved from the environment at the first call):
+// what a launcher writes into ConvLaunch::deal_c
+int ddp_conv_deal_chunk(void);
+
 #endif

@@ -455,6 +455,17 @@ int ddp_set_occupancy_shaping(int rows_min_lds_bytes, int stage_a_lds_pad_bytes)
  * tools may write it themselves.  Process-wide, read when a launch is enqueued. */
 extern int ddp_sa_drainwave;
 
+/* The order in which the workgroups of a conv launch (ddp_conv_messages, ddp_conv_rows) take its tiles.  Workgroup ids go round-robin to
+ * the 8 XCDs; the launch's task-major tile list is cut into chunks of ddp_conv_deal consecutive tiles and the chunks are dealt to the XCDs
+ * in turn, so that every XCD runs the same mix of the launch's convs (a workgroup's cost depends on its conv).  0 = one contiguous range
+ * of tiles per XCD (the order before this switch existed).  -1 (initial): the first launch reads DDP_CONV_DEAL from the environment
+ * (default 8) and stores the value here; tests and A/B tools may write it themselves (0 .. 4096).  Process-wide, read when a launch is
+ * enqueued (captured launches keep what they were captured with); results do not depend on it. */
+extern int ddp_conv_deal;
+/* The tile that workgroup `id` of a launch of `total` tiles takes when chunks of c tiles are dealt (c = 0: one range per XCD): the
+ * function the kernels call, for tests on the host.  A bijection of [0, total); -1 for arguments out of range. */
+int ddp_conv_deal_tile(int id, int total, int c);
+
 /* The pose update between two score-model calls, for all samples of a batch in one launch:
  * modify_conformer(pos, tr_update, rot_update, torsion_updates) of utils/diffusion_utils.py:37-60 = rigid move about the
  * centre (rot_update is an axis-angle vector, utils/geometry.py:72-86), torsions in bond order (utils/torsion.py:68-94:
