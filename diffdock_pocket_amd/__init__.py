@@ -8,7 +8,7 @@ __all__ = ["HeteroBatch", "Store", "collate", "set_time", "SigmaRanges", "get_t_
            "sinusoidal_embedding", "t_to_sigma", "get_model", "TensorProductScoreModel", "PoseEvaluator", "PoseClusters", "summarize", "PoseRefiner",
            "RefineConfig", "RefineResult", "PoseScorer", "ScoreConfig", "PoseScores", "PoseMinimizer", "MinimizeConfig",
            "MinimizeResult", "FlexPoseMinimizer", "FlexMinimizeResult", "InteractionProfiler", "ProfileConfig", "InteractionProfile",
-           "PoseSearcher", "SearchConfig", "SearchResult"]
+           "PoseSearcher", "SearchConfig", "SearchResult", "FlexPoseSearcher", "FlexSearchResult"]
 
 
 def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ctypes binding
@@ -39,4 +39,7 @@ def __getattr__(name):  # lazy: importing the model pulls in torch.nn and the ct
     if name in ("PoseSearcher", "SearchConfig", "SearchResult"):
         from . import search
         return getattr(search, name)
+    if name in ("FlexPoseSearcher", "FlexSearchResult"):
+        from . import search_flex
+        return getattr(search_flex, name)
     raise AttributeError(name)

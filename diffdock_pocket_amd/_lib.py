@@ -25,7 +25,7 @@ DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS, DDP_MINIMIZE_FLEX_MAX
 DDP_PAIRWISE_MAX_SAMPLES, DDP_CLUSTER_MAX_SAMPLES = 32768, 1024
 EXPORTS = ["ddp_conv_messages", "ddp_conv_rows", "ddp_stage_a_gh", "ddp_stage_a_gh3", "ddp_segment_reduce", "ddp_edge_featurize", "ddp_edge_featurize_jobs", "ddp_torsion_sh", "ddp_stage_a", "ddp_stage_a_h2",
            "ddp_pose_update", "ddp_sidechain_update", "ddp_sde_update", "ddp_radius_count", "ddp_radius_fill", "ddp_knn", "ddp_group_by_key", "ddp_node_linear", "ddp_scan_jobs", "ddp_mark_jobs", "ddp_rowcopy_jobs", "ddp_select_jobs",
-           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pose_search", "ddp_pose_search_select", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_conv_deal_tile", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
+           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pose_search", "ddp_pose_search_select", "ddp_pose_search_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_conv_deal_tile", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
 
 
 class Seg(C.Structure):
@@ -175,6 +175,15 @@ class SearchArgs(C.Structure):
     _fields_ = [("min", MinimizeArgs), ("replicas", _I), ("cycles", _I), ("cycle0", _I), ("reserved", _I), ("step_init", C.c_double),
                 ("temperature", C.c_double), ("perturb", _P), ("u", _P), ("cur_pos", _P), ("cur_e", _P), ("best_pos", _P), ("best_e", _P),
                 ("best_cycle", _P), ("accepted", _P), ("trace", _P), ("flags", _P), ("starts", _P)]
+
+
+class SearchFlexArgs(C.Structure):
+    """ddp_search_flex_args_t of include/ddp_hip.h: a ddp_minimize_flex_args_t (the score, the side chains and the line search), then
+    the chain's, with the moving atoms in the row state."""
+    _fields_ = [("flex", MinimizeFlexArgs), ("replicas", _I), ("cycles", _I), ("cycle0", _I), ("reserved", _I), ("step_init", C.c_double),
+                ("temperature", C.c_double), ("perturb", _P), ("u", _P), ("cur_pos", _P), ("cur_mov", _P), ("cur_e", _P), ("best_pos", _P),
+                ("best_mov", _P), ("best_e", _P), ("best_cycle", _P), ("accepted", _P), ("trace", _P), ("flags", _P), ("starts", _P),
+                ("starts_mov", _P)]
 
 
 class SearchSelectArgs(C.Structure):
@@ -368,6 +377,8 @@ def load():
     lib.ddp_pose_search.restype = C.c_int
     lib.ddp_pose_search_select.argtypes = [C.POINTER(SearchSelectArgs), C.c_void_p]
     lib.ddp_pose_search_select.restype = C.c_int
+    lib.ddp_pose_search_flex.argtypes = [C.POINTER(SearchFlexArgs), C.c_void_p]
+    lib.ddp_pose_search_flex.restype = C.c_int
     lib.ddp_pocket_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p]
     lib.ddp_pocket_occupancy.restype = C.c_int

@@ -3,7 +3,8 @@
 // states the whole definition).  The sibling of ddp_minimize.hip: the same loop, the same accept rule, the same one call site of the
 // evaluation, with a second molecule in the state.  One 256-thread workgroup per pose holds, for the whole call, what ddp_pose_minimize
 // holds for the ligand and, for the n_mov moving receptor atoms, the current and the trial coordinates, both gradients, radii, flags,
-// their receptor indices and the side-chain steps.
+// their receptor indices and the side-chain steps.  The LDS plan, the evaluation and the loop (fx_descend) live in
+// ddp_minimize_flex_loop.h, which ddp_search_flex.hip shares; this file is the kernel around them and the host entry.
 // One evaluation:
 //   1. score_evaluate of ddp_pose_descent.h for the ligand side.  Its tile-load hook (FxPatch) puts the moving atoms in from LDS as the
 //      receptor tile is loaded: a binary search of the atom's index in the sorted `mov` (at most 9 probes of LDS per loaded atom) is the
@@ -17,288 +18,12 @@
 // Every sum has a fixed order (ddp_pose_descent.h): butterflies inside a wave, the waves in wave order, the tiles in increasing order.
 // No atomics.  No data-dependent control flow around a barrier: trip counts and the conditions that skip a barrier (an index outside
 // the receptor, m <= one tile) are kernel arguments or table entries, the same for all 256 threads.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "ddp_hip.h"
-#include "ddp_internal.h"
-#include "ddp_horn.h"
-#include "ddp_pose_descent.h"
-
-#define DDP_FX_THREADS DDP_DESCENT_THREADS
-#define DDP_FX_WAVES DDP_DESCENT_WAVES
-#define DDP_FX_TILE DDP_SCORE_TILE
-#define DDP_FX_MOVING 0x80u                          // flag bit of a tile entry that the hook put in
-// fixed part of the LDS plan, every carve a multiple of 16 bytes: that of ddp_minimize.hip, then the second pass's partial sums
-#define DDP_FX_WE_BYTES (DDP_FX_WAVES * 10 * 8)      // [waves][8] fp64 of score_evaluate, then [waves] of the ligand restraint
-#define DDP_FX_RED_BYTES (DDP_FX_WAVES * 16 * 8)     // block sums of the direction and the pose map
-#define DDP_FX_WE2_BYTES 192                         // [waves][4] fp64 of sc, then [waves] of the side-chain restraint
-#define DDP_FX_FIXED_BYTES (DDP_FX_TILE * 16 + DDP_FX_TILE + DDP_FX_WE_BYTES + DDP_FX_RED_BYTES + 64 + DDP_FX_WE2_BYTES)
-
-static_assert(DDP_MINIMIZE_MAX_TORSIONS * sizeof(float) <= DDP_FX_TILE * sizeof(float4), "the torsion steps live in the tile between two evaluations");
-static_assert(DDP_FX_FIXED_BYTES % 16 == 0, "dynamic LDS carves stay 16-byte aligned");
-static_assert(DDP_FX_FIXED_BYTES == 18496, "the header states the fixed part of the plan");
-static_assert(DDP_FX_FIXED_BYTES + DDP_MINIMIZE_FLEX_MAX_STATE_BYTES <= 64 * 1024, "the LDS plan fits the 64 KiB a plain launch may ask for");
-static_assert(DDP_FX_WAVES * 5 * 8 <= DDP_FX_WE2_BYTES, "the second pass's partial sums");
-
-struct FxLds {
-  float4* tile;        // [DDP_FX_TILE] receptor x, y, z, radius; between two evaluations its first floats hold the ligand torsion steps
-  uint8_t* tflag;      // [DDP_FX_TILE]
-  double (*we)[8];     // [waves][8]
-  double* wr;          // [waves] the ligand restraint sums of the waves
-  double* red;         // scratch of block_sum
-  double* et;          // [6] the energies of the last evaluation
-  double (*we2)[4];    // [waves][4] the sc sums of the waves
-  double* wr2;         // [waves] the side-chain restraint sums of the waves
-  double* g;           // [2][n][3] ligand gradients: of the current pose and of the trial
-  double* gm;          // [2][n_mov][3] the same of the moving atoms
-  float* x;            // [2][n][3] the current pose and the trial
-  float* ym;           // [2][n_mov][3] the same of the moving atoms
-  float* rg;           // [n][3] the rigid copy of the pose map
-  float* rad;          // [n]
-  float* mrad;         // [n_mov] radius; negative: untyped, or an index outside the receptor - the atom takes part in nothing
-  int32_t* mov;        // [n_mov]
-  float* scstep;       // [n_sc] the side-chain steps
-  uint8_t* lflag;      // [n]
-  uint8_t* mflag;      // [n_mov]
-};
-
-// slot of receptor atom a among the moving atoms (mov sorted), or -1
-__device__ __forceinline__ int fx_slot(const int32_t* mov, int n_mov, int a) {
-  int lo = 0, hi = n_mov;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (mov[mid] < a) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < n_mov && mov[lo] == a) ? lo : -1;
-}
-
-// the tile-load hook of score_evaluate: a moving atom comes from ym (LDS), not from global memory
-struct FxPatch {
-  const int32_t* mov;
-  int n_mov;
-  const float* ym;
-  __device__ __forceinline__ void operator()(int j, float4& r, uint8_t& f) const {
-    const int k = fx_slot(mov, n_mov, j);
-    if (k >= 0) {
-      r.x = ym[3 * k]; r.y = ym[3 * k + 1]; r.z = ym[3 * k + 2];
-      f |= DDP_FX_MOVING;
-    }
-  }
-};
-
-// coordinates of receptor atom a (inside [0, m)): the moving atoms' LDS copy ym or the sample's receptor in global memory
-__device__ __forceinline__ void fx_atom(const FxLds& L, int n_mov, const float* rs, const float* ym, int a, float* p) {
-  const int k = fx_slot(L.mov, n_mov, a);
-  if (k >= 0) { p[0] = ym[3 * k]; p[1] = ym[3 * k + 1]; p[2] = ym[3 * k + 2]; }
-  else { p[0] = rs[3 * a]; p[1] = rs[3 * a + 1]; p[2] = rs[3 * a + 2]; }
-}
-
-// Energy [inter, intra, sc, ligand restraint term, side-chain restraint term, E] -> L.et, gradients -> g and gm of the state (x, ym)
-// (LDS, visible to all threads on entry).  Ends with a barrier: L.et, g and gm are visible on return.
-__device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, const FxLds& L, const float* rs, const float* __restrict__ as,
-                                         const float* __restrict__ ras, const float* x, const float* ym, double* g, double* gm) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m, n_mov = A.n_mov;
-  const FxPatch patch = {L.mov, n_mov, ym};
-  score_evaluate<true>(A, rs, L.tile, L.tflag, x, L.rad, L.lflag, g, L.we, patch);
-  // the ligand restraint, as mz_evaluate of ddp_minimize_loop.h
-  const double krest = 2.0 * A.restraint / (double)n;
-  double er_w = 0.0;
-  for (int i = wave; i < n; i += DDP_FX_WAVES) {
-    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
-    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
-    er_w += ax * ax + ay * ay + az * az;
-    if (lane == 0) { g[3 * i] = g[3 * i] + krest * ax; g[3 * i + 1] = g[3 * i + 1] + krest * ay; g[3 * i + 2] = g[3 * i + 2] + krest * az; }
-  }
-  if (lane == 0) L.wr[wave] = er_w;
-  // ---- the second pass.  d inter / dy_a by gather over the ligand atoms; the assignment also clears gm
-  const ddp_score_form_t& F = A.form;
-  const double cut2 = F.cutoff * F.cutoff;
-  for (int r = wave; r < n_mov; r += DDP_FX_WAVES) {
-    ScoreAcc acc = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};     // (its energy sums are not used: step 1 has them)
-    const double ra = L.mrad[r];
-    if (ra >= 0.0) {                               // (wave-uniform, no barrier inside)
-      const double xa = ym[3 * r], ya = ym[3 * r + 1], za = ym[3 * r + 2];
-      const unsigned fa = L.mflag[r];
-      for (int i = lane; i < n; i += 64) {
-        if (L.rad[i] < 0.f) continue;
-        score_pair<true>(F, cut2, xa - (double)x[3 * i], ya - (double)x[3 * i + 1], za - (double)x[3 * i + 2], ra + (double)L.rad[i], fa,
-                         L.lflag[i], acc);
-      }
-    }
-    const double gx = wave_sum(acc.gx), gy = wave_sum(acc.gy), gz = wave_sum(acc.gz);
-    if (lane == 0) { gm[3 * r] = gx; gm[3 * r + 1] = gy; gm[3 * r + 2] = gz; }   // (atom r is this wave's alone)
-  }
-  // sc: the partners of sc_pairs, tile by tile.  st: partners that stay, mv: partners that move themselves (half the energy)
-  ScoreAcc st = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0.0}, mv = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};
-  for (int j0 = 0; n_mov > 0 && j0 < m; j0 += DDP_FX_TILE) {
-    const int mt = min(DDP_FX_TILE, m - j0);
-    if (m > DDP_FX_TILE) {                         // (the same for all threads) more than one tile: stream them again
-      __syncthreads();
-      for (int j = tid; j < mt; j += DDP_FX_THREADS) {
-        float4 q = make_float4(rs[3 * (j0 + j)], rs[3 * (j0 + j) + 1], rs[3 * (j0 + j) + 2], A.rec_radii[j0 + j]);
-        uint8_t f = A.rec_flags[j0 + j];
-        patch(j0 + j, q, f);
-        L.tile[j] = q;
-        L.tflag[j] = f;
-      }
-      __syncthreads();
-    }
-    for (int r = wave; r < n_mov; r += DDP_FX_WAVES) {
-      const double ra = L.mrad[r];
-      st.gx = st.gy = st.gz = 0.0;
-      mv.gx = mv.gy = mv.gz = 0.0;
-      if (ra >= 0.0) {
-        const double xa = ym[3 * r], ya = ym[3 * r + 1], za = ym[3 * r + 2];
-        const unsigned fa = L.mflag[r];
-        const int a = L.mov[r];
-        const uint8_t* __restrict__ sp = A.sc_pairs + (size_t)r * m + j0;
-        for (int j = lane; j < mt; j += 64) {
-          if (!sp[j] || j0 + j == a) continue;
-          const float4 q = L.tile[j];
-          if (q.w < 0.f) continue;                 // an untyped receptor atom
-          const unsigned fj = L.tflag[j];
-          const double dx = xa - (double)q.x, dy = ya - (double)q.y, dz = za - (double)q.z, rsum = ra + (double)q.w;
-          if (fj & DDP_FX_MOVING) score_pair<true>(F, cut2, dx, dy, dz, rsum, fa, fj, mv);
-          else score_pair<true>(F, cut2, dx, dy, dz, rsum, fa, fj, st);
-        }
-      }
-      const double gx = wave_sum(st.gx + mv.gx), gy = wave_sum(st.gy + mv.gy), gz = wave_sum(st.gz + mv.gz);
-      if (lane == 0) { gm[3 * r] += gx; gm[3 * r + 1] += gy; gm[3 * r + 2] += gz; }
-    }
-  }
-  // the side-chain restraint
-  const double krs = n_mov > 0 ? 2.0 * A.restraint_sc / (double)n_mov : 0.0;
-  double er2_w = 0.0;
-  for (int r = wave; r < n_mov; r += DDP_FX_WAVES) {
-    const int a = L.mov[r];
-    if (a < 0 || a >= m) continue;                 // an index outside the receptor: no read (wave-uniform)
-    const double ax = (double)ym[3 * r] - (double)ras[3 * a], ay = (double)ym[3 * r + 1] - (double)ras[3 * a + 1],
-                 az = (double)ym[3 * r + 2] - (double)ras[3 * a + 2];
-    er2_w += ax * ax + ay * ay + az * az;
-    if (lane == 0) { gm[3 * r] = gm[3 * r] + krs * ax; gm[3 * r + 1] = gm[3 * r + 1] + krs * ay; gm[3 * r + 2] = gm[3 * r + 2] + krs * az; }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double c = wave_sum(st.t[k]) + 0.5 * wave_sum(mv.t[k]);
-    if (lane == 0) L.we2[wave][k] = c;
-  }
-  if (lane == 0) L.wr2[wave] = er2_w;
-  __syncthreads();
-  if (tid == 0) {
-    double t[8], inter, intra, er = L.wr[0], er2 = L.wr2[0], c[4];
-    score_totals(A.form, L.we, t, inter, intra);
-    for (int w = 1; w < DDP_FX_WAVES; ++w) { er += L.wr[w]; er2 += L.wr2[w]; }
-    for (int k = 0; k < 4; ++k) {
-      c[k] = L.we2[0][k];
-      for (int w = 1; w < DDP_FX_WAVES; ++w) c[k] += L.we2[w][k];
-    }
-    const double sc = F.w_gauss * c[0] + F.w_repulsion * c[1] + F.w_hydrophobic * c[2] + F.w_hbond * c[3];
-    const double rest = A.restraint * (er / (double)n);
-    const double rest2 = n_mov > 0 ? A.restraint_sc * (er2 / (double)n_mov) : 0.0;
-    L.et[0] = inter; L.et[1] = intra; L.et[2] = sc; L.et[3] = rest; L.et[4] = rest2;
-    L.et[5] = (((inter + intra) + sc) + rest) + rest2;
-  }
-  __syncthreads();
-}
-
-// the range of sc_sub that bond j turns, clamped to the table
-__device__ __forceinline__ void fx_range(const ddp_minimize_flex_args_t& A, int j, int& m0, int& m1) {
-  m0 = min(max(A.sc_map[2 * j], 0), A.n_sub);
-  m1 = min(max(A.sc_map[2 * j + 1], 0), A.n_sub);
-}
-
-// L.scstep[j] = step * the inertia-scaled direction of side-chain bond j at the state ym with the gradient gm, fp64, rounded to fp32.
-// Wave w owns the bonds w, w + 4, ..., its lanes stride over the bond's subcomponent.  Visible after the caller's next barrier.
-__device__ __forceinline__ void fx_sc_direction(const ddp_minimize_flex_args_t& A, const FxLds& L, const float* rs, const float* ym,
-                                                const double* gm, double step) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = A.m, n_mov = A.n_mov;
-  for (int j = wave; j < A.n_sc; j += DDP_FX_WAVES) {
-    const int u = A.sc_edge_idx[2 * j], v = A.sc_edge_idx[2 * j + 1];
-    double num = 0.0, den = 0.0;
-    if (u >= 0 && u < m && v >= 0 && v < m) {      // an entry outside the receptor: no read, the bond gets 0
-      float pu[3], pv[3];
-      fx_atom(L, n_mov, rs, ym, u, pu);
-      fx_atom(L, n_mov, rs, ym, v, pv);
-      const double vx = pv[0], vy = pv[1], vz = pv[2];
-      double ux = (double)pu[0] - vx, uy = (double)pu[1] - vy, uz = (double)pu[2] - vz;
-      const double len = sqrt(ux * ux + uy * uy + uz * uz);
-      ux /= len; uy /= len; uz /= len;
-      int m0, m1;
-      fx_range(A, j, m0, m1);
-      for (int i = m0 + lane; i < m1; i += 64) {
-        const int a = A.sc_sub[i];
-        if (a < 0 || a >= m || a == u || a == v) continue;   // the bond's own atoms lie on the axis: no lever, exactly
-        const int k = fx_slot(L.mov, n_mov, a);
-        if (k < 0) continue;                       // not a moving atom: it takes part in nothing
-        const double px = (double)ym[3 * k] - vx, py = (double)ym[3 * k + 1] - vy, pz = (double)ym[3 * k + 2] - vz;
-        const double ax = uy * pz - uz * py, ay = uz * px - ux * pz, az = ux * py - uy * px;
-        num += gm[3 * k] * ax + gm[3 * k + 1] * ay + gm[3 * k + 2] * az;
-        den += ax * ax + ay * ay + az * az;
-      }
-    }
-    num = wave_sum(num); den = wave_sum(den);
-    if (lane == 0) L.scstep[j] = (float)(step * (den == 0.0 ? 0.0 : -num / den));
-  }
-}
-
-// yt = the side-chain map of ddp_sidechain_update_kernel applied to ym with the angles L.scstep, fp32, bonds in list order; the axis of a
-// bond is read by every thread before the barrier behind which the bond's atoms move.  Ends with a barrier: yt is visible on return.
-__device__ __forceinline__ void fx_sc_update(const ddp_minimize_flex_args_t& A, const FxLds& L, const float* rs, const float* ym, float* yt) {
-  const int tid = threadIdx.x, m = A.m, n_mov = A.n_mov;
-  for (int i = tid; i < 3 * n_mov; i += DDP_FX_THREADS) yt[i] = ym[i];
-  __syncthreads();
-  float M[9];
-  for (int j = 0; j < A.n_sc; ++j) {
-    const int u = A.sc_edge_idx[2 * j], v = A.sc_edge_idx[2 * j + 1];
-    if (u < 0 || u >= m || v < 0 || v >= m) continue;   // an entry outside the receptor: no read, no rotation (the same for all threads)
-    float pu[3], pv[3];
-    fx_atom(L, n_mov, rs, yt, u, pu);
-    fx_atom(L, n_mov, rs, yt, v, pv);
-    const float ax = pu[0] - pv[0], ay = pu[1] - pv[1], az = pu[2] - pv[2];
-    const float k = L.scstep[j] / sqrtf(ax * ax + ay * ay + az * az);
-    rotvec_to_matrix(ax * k, ay * k, az * k, M);
-    __syncthreads();                             // every thread has read the axis before an atom on it may move
-    int m0, m1;
-    fx_range(A, j, m0, m1);
-    for (int i = m0 + tid; i < m1; i += DDP_FX_THREADS) {
-      const int a = A.sc_sub[i];
-      if (a < 0 || a >= m) continue;
-      const int s = fx_slot(L.mov, n_mov, a);
-      if (s < 0) continue;
-      const float px = yt[3 * s] - pv[0], py = yt[3 * s + 1] - pv[1], pz = yt[3 * s + 2] - pv[2];
-      yt[3 * s] = M[0] * px + M[1] * py + M[2] * pz + pv[0];
-      yt[3 * s + 1] = M[3] * px + M[4] * py + M[5] * pz + pv[1];
-      yt[3 * s + 2] = M[6] * px + M[7] * py + M[8] * pz + pv[2];
-    }
-    __syncthreads();
-  }
-}
+#include "ddp_minimize_flex_loop.h"
 
 __global__ __launch_bounds__(DDP_FX_THREADS) void ddp_pose_minimize_flex_kernel(const ddp_minimize_flex_args_t A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fx_lds[];
   const int s = blockIdx.x, tid = threadIdx.x, n = A.n, m = A.m, n_mov = A.n_mov, S = A.n_samples;
-  FxLds L;
-  unsigned char* p = fx_lds;
-  L.tile = (float4*)p; p += DDP_FX_TILE * sizeof(float4);
-  L.tflag = p; p += DDP_FX_TILE;
-  L.we = (double(*)[8])p; L.wr = (double*)p + DDP_FX_WAVES * 8; p += DDP_FX_WE_BYTES;
-  L.red = (double*)p; p += DDP_FX_RED_BYTES;
-  L.et = (double*)p; p += 64;
-  L.we2 = (double(*)[4])p; L.wr2 = (double*)p + DDP_FX_WAVES * 4; p += DDP_FX_WE2_BYTES;
-  L.g = (double*)p; p += (size_t)48 * n;
-  L.gm = (double*)p; p += (size_t)48 * n_mov;
-  L.x = (float*)p; p += (size_t)24 * n;
-  L.ym = (float*)p; p += (size_t)24 * n_mov;
-  L.rg = (float*)p; p += (size_t)12 * n;
-  L.rad = (float*)p; p += (size_t)4 * n;
-  L.mrad = (float*)p; p += (size_t)4 * n_mov;
-  L.mov = (int32_t*)p; p += (size_t)4 * n_mov;
-  L.scstep = (float*)p; p += (size_t)4 * A.n_sc;
-  L.lflag = p; p += n;
-  L.mflag = p;
+  const FxLds L = fx_carve(fx_lds, n, n_mov, A.n_sc);
   float* gpos = A.pos + (size_t)s * n * 3;
   const float* __restrict__ as = A.anchor + (size_t)s * n * 3;
   float* rs = A.rec + (size_t)s * A.rec_stride;      // read through the whole call, its moving atoms written once at exit
@@ -306,46 +31,21 @@ __global__ __launch_bounds__(DDP_FX_THREADS) void ddp_pose_minimize_flex_kernel(
   // the start state goes into the TRIAL buffers: pass 0 of the loop evaluates it and takes it whatever its energy
   int cur = 0;
   for (int i = tid; i < 3 * n; i += DDP_FX_THREADS) L.x[3 * n + i] = gpos[i];
-  for (int i = tid; i < n; i += DDP_FX_THREADS) { L.rad[i] = A.lig_radii[i]; L.lflag[i] = A.lig_flags[i]; }
+  fx_load_tables(A, L);
   for (int r = tid; r < n_mov; r += DDP_FX_THREADS) {
     const int a = A.mov[r];
     const bool in = a >= 0 && a < m;               // an index outside the receptor: no read, the atom takes part in nothing
-    L.mov[r] = a;
-    L.mrad[r] = in ? A.rec_radii[a] : -1.f;
-    L.mflag[r] = in ? A.rec_flags[a] : (uint8_t)0;
     float* y = L.ym + 3 * n_mov + 3 * r;
     y[0] = in ? rs[3 * a] : 0.f; y[1] = in ? rs[3 * a + 1] : 0.f; y[2] = in ? rs[3 * a + 2] : 0.f;
   }
   double step = A.step[s];
   int taken = 0;
-  double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, e0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   __syncthreads();
-  for (int it = 0; it <= A.iterations; ++it) {
-    if (it > 0) {
-      // the ligand torsion steps go to the tile's first n_tor floats, the side-chain steps to L.scstep; the barrier makes them visible
-      float tr[3], rot[3];
-      descent_direction<true>(L.x + cur * 3 * n, L.g + cur * 3 * n, n, A.n_tor, A.bonds, A.mask_rotate, step, L.red, tr, rot, (float*)L.tile);
-      fx_sc_direction(A, L, rs, L.ym + cur * 3 * n_mov, L.gm + cur * 3 * n_mov, step);
-      __syncthreads();
-      descent_pose_update(A, L.x + cur * 3 * n, L.x + (cur ^ 1) * 3 * n, L.rg, (const float*)L.tile, (float*)L.red, tr, rot);
-      fx_sc_update(A, L, rs, L.ym + cur * 3 * n_mov, L.ym + (cur ^ 1) * 3 * n_mov);
-    }
-    fx_evaluate(A, L, rs, as, ras, L.x + (cur ^ 1) * 3 * n, L.ym + (cur ^ 1) * 3 * n_mov, L.g + (cur ^ 1) * 3 * n, L.gm + (cur ^ 1) * 3 * n_mov);
-    const double et5 = L.et[5];
-    const bool take = it == 0 || et5 < e[5];     // strict, fp64, false for NaN; the same LDS words for every thread
-    if (take) {
-      e[0] = L.et[0]; e[1] = L.et[1]; e[2] = L.et[2]; e[3] = L.et[3]; e[4] = L.et[4]; e[5] = et5;
-      cur ^= 1;
-    }
-    if (it > 0) {
-      step = take ? fmin(A.grow * step, A.step_max) : A.shrink * step;
-      taken += take ? 1 : 0;
-    } else if (tid == 0) {
-      double* ei = A.energy_in + 6 * (size_t)s;
-      for (int k = 0; k < 6; ++k) ei[k] = e[k];
-    }
-    if (A.history && tid == 0) A.history[(size_t)it * S + s] = e[5];
-    // (the next write of L.et lies behind the barriers of the next evaluation)
+  fx_descend(A, L, rs, as, ras, A.iterations, cur, step, taken, e, e0, A.history ? A.history + s : (double*)nullptr, (size_t)S);
+  if (tid == 0) {
+    double* ei = A.energy_in + 6 * (size_t)s;
+    for (int k = 0; k < 6; ++k) ei[k] = e0[k];
   }
   if (tid == 0) {
     double* eo = A.energy_out + 6 * (size_t)s;

@@ -39,6 +39,7 @@ from .interactions import InteractionProfile, InteractionProfiler, ProfileConfig
 from .minimize import MinimizeConfig, MinimizeResult, PoseMinimizer  # noqa: F401
 from .minimize_flex import FlexMinimizeResult, FlexPoseMinimizer  # noqa: F401
 from .search import PoseSearcher, SearchConfig, SearchResult  # noqa: F401
+from .search_flex import FlexPoseSearcher, FlexSearchResult  # noqa: F401
 from .refine import PoseRefiner, RefineConfig, RefineResult  # noqa: F401
 from .sampler import Sampler, SamplerConfig
 from .scoring import PoseScorer, PoseScores, ScoreConfig, rank_order, typed_receptor  # noqa: F401
@@ -66,7 +67,8 @@ class ComplexResult:
     minimized: Optional["MinimizeResult"] = None   # run_csv(minimize_poses=cfg): minimize.MinimizeResult of the ranked poses (host tensors);
     #                                                a flexible row with cfg.sidechains: minimize_flex.FlexMinimizeResult
     minimized_pos: Optional[torch.Tensor] = None   # run_csv(minimize_poses=cfg): [N, n_lig, 3] the ranked poses after the minimisation
-    searched: Optional["SearchResult"] = None      # run_csv(search_poses=cfg): search.SearchResult of the ranked poses (host tensors)
+    searched: Optional["SearchResult"] = None      # run_csv(search_poses=cfg): search.SearchResult of the ranked poses (host tensors);
+    #                                                a flexible row with cfg.sidechains: search_flex.FlexSearchResult
     searched_pos: Optional[torch.Tensor] = None    # run_csv(search_poses=cfg): [N, n_lig, 3] the ranked poses after the search
     interactions: Optional["InteractionProfile"] = None  # run_csv(interaction_profile=cfg): interactions.InteractionProfile of the ranked
     #                                                      poses (host tensors)
@@ -234,7 +236,11 @@ def run_csv(csv_path: str, model, device, *, confidence_model=None, samples_per_
     is not validated against smina or Vina (search.py states what it is and is not).  `searched` (a SearchResult) and `searched_pos`
     in ranked order; with out_dir also rank{k}_searched.sdf per pose and searched.csv (outputs.write_searched_csv).  The receptor is
     the scoring's: the row's full typed PDB for rigid rows, each sample's own atom nodes for flexible rows.  It is independent of
-    minimize_poses and resolve_clashes: all of them start from the sampled poses.  rank_by="searched_score" (implies the search with the
+    minimize_poses and resolve_clashes: all of them start from the sampled poses.  search_poses.sidechains=True: a flexible row goes
+    through search_flex.FlexPoseSearcher instead, which moves the side chains of the flexible residues with the ligand, in the random
+    moves and in the descent: `searched` is then a FlexSearchResult, E in searched.csv the joint E, and with out_dir also
+    rank{k}_searched_protein.pdb (the receptor with the searched side chains) and searched_sidechains.csv; rigid rows take the path
+    above.  rank_by="searched_score" (implies the search with the
     default SearchConfig) orders the poses by ascending `scores_after.total` through scoring.rank_order, and everything downstream
     follows that order.  None: nothing is computed, allocated, launched or written.  A failure skips the row like a failure of the
     evaluation."""
@@ -516,6 +522,9 @@ class _RowTools:
         return PoseMinimizer(self.g, self.device, config=config, scorer=self.scorer).minimize(lig, apos).cpu()
 
     def search(self, lig, apos, config) -> SearchResult:
+        """A flexible row with config.sidechains: the FlexSearchResult of the search with the side chains in the state."""
+        if self.flex and config.sidechains:
+            return FlexPoseSearcher(self.g, self.device, score_config=self.score_poses, config=config).search(lig, apos).cpu()
         return PoseSearcher(self.g, self.device, config=config, scorer=self.scorer).search(lig, apos).cpu()
 
     def evaluate(self, lig, apos) -> PoseMetrics:
@@ -542,7 +551,8 @@ class _RowTools:
     def write(self, out_dir, i, res: ComplexResult, apos, remove_hs) -> List[str]:
         """outputs.write_complex of the ranked tensors of `res`."""
         row = self.row
-        needs_pdb = apos is not None or res.atom_traj is not None or isinstance(res.minimized, FlexMinimizeResult)
+        needs_pdb = apos is not None or res.atom_traj is not None or isinstance(res.minimized, FlexMinimizeResult) or \
+            isinstance(res.searched, FlexSearchResult)
         return O.write_complex(O.complex_dir(out_dir, i, row["complex_name"]), self.sdf_text, self.pdb_text if needs_pdb else None, self.g,
                                res.ligand_pos, res.confidence, apos, res.lig_traj, res.atom_traj, remove_hs=remove_hs,
                                clusters=res.clusters, order=res.order, refine=res.refine, pockets=res.pockets,
@@ -649,6 +659,15 @@ def _parser():
     p.add_argument("--search_temperature", type=float, default=SearchConfig.temperature,
                    help="with --search_poses: temperature of the Metropolis rule, in units of the score")
     p.add_argument("--search_seed", type=int, default=SearchConfig.seed, help="with --search_poses: seed of the random moves")
+    p.add_argument("--search_sidechains", action="store_true", default=False,
+                   help="implies --search_poses; rows with flexible residues search the chi angles of those residues together with the "
+                        "ligand (search_flex.py: Gaussian chi moves around the current rotamer, the joint descent of --minimize_sidechains; "
+                        "no backbone motion, no rotamer library): rank{k}_searched_protein.pdb and searched_sidechains.csv are written too; "
+                        "rigid rows are searched as without the flag; independent of --minimize_sidechains (default: off)")
+    p.add_argument("--search_sigma_chi", type=float, default=SearchConfig.sigma_chi,
+                   help="with --search_sidechains: standard deviation of the random side-chain steps, rad per bond")
+    p.add_argument("--search_sidechain_restraint", type=float, default=SearchConfig.sidechain_restraint,
+                   help="with --search_sidechains: weight of the restraint of the moving side-chain atoms to their sampled positions")
     p.add_argument("--interaction_profile", action="store_true", default=False,
                    help="say which residues every pose touches and how: the pair terms of the physics score summed per residue, with "
                         "contact / hydrophobic / hbond bits (not validated against PLIP or ProLIF); writes interactions.csv, "
@@ -693,6 +712,15 @@ def _load_model(model_dir, ckpt, device, confidence_mode=False):
     return model.to(device).eval(), args, sigma
 
 
+def _search_config(a) -> Optional[SearchConfig]:
+    """The SearchConfig of the parsed flags, or None: --search_sidechains and --rank_by searched_score imply --search_poses."""
+    if not (a.search_poses or a.search_sidechains or a.rank_by == "searched_score"):
+        return None
+    return SearchConfig(replicas=a.search_replicas, cycles=a.search_cycles, iterations=a.search_iterations, temperature=a.search_temperature,
+                        seed=a.search_seed, sidechains=a.search_sidechains, sigma_chi=a.search_sigma_chi,
+                        sidechain_restraint=a.search_sidechain_restraint)
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     """The command line: `python -m diffdock_pocket_amd.inference --protein_path P --ligand L.sdf --model_dir M ...` or
     `--protein_ligand_csv C`.  Writes `{out_dir}/index{i}___{name}` per complex (run_csv(out_dir=...)); returns 0 when every
@@ -715,6 +743,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--minimize_iterations and --minimize_restraint must not be negative")
     if not a.minimize_sidechain_restraint >= 0:
         ap.error("--minimize_sidechain_restraint must not be negative")
+    if not a.search_sigma_chi >= 0:
+        ap.error("--search_sigma_chi must not be negative")
+    if not a.search_sidechain_restraint >= 0:
+        ap.error("--search_sidechain_restraint must not be negative")
     if a.search_replicas < 1 or a.search_cycles < 0 or a.search_iterations < 0 or not (0 < a.search_temperature < float("inf")):
         ap.error("--search_replicas must be at least 1, --search_cycles and --search_iterations not negative, --search_temperature "
                  "positive and finite")
@@ -785,9 +817,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                                     sidechains=a.minimize_sidechains, sidechain_restraint=a.minimize_sidechain_restraint)
                       if (a.minimize_poses or a.minimize_sidechains or a.rank_by == "minimized_score") else None,
                       interaction_profile=ProfileConfig(contact_distance=a.interaction_contact_distance) if a.interaction_profile else None,
-                      search_poses=SearchConfig(replicas=a.search_replicas, cycles=a.search_cycles, iterations=a.search_iterations,
-                                                temperature=a.search_temperature, seed=a.search_seed)
-                      if (a.search_poses or a.rank_by == "searched_score") else None)
+                      search_poses=_search_config(a))
     failed = [r for r in res if r.skipped is not None]
     for r in res:
         print(f"{r.name}: " + (f"skipped ({r.skipped})" if r.skipped else f"{len(r.files)} files"), flush=True)

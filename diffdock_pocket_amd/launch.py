@@ -996,6 +996,49 @@ def pose_minimize_flex(pos, anchor, lig_radii, lig_flags, rec, rec_anchor, rec_r
               bonds, mask_rotate, step, accepted, energy_in, energy_out, iterations, restraint, grow, shrink, step_max, history, grad, side)
 
 
+# ------------------------------------------------------------------------------------------------ flexible search (csrc/ddp_search_flex.hip)
+def pose_search_flex(anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate, tables, replicas, cycle0,
+                     perturb, u, cur_pos, cur_mov, cur_e, best_pos, best_mov, best_e, best_cycle, accepted, trace, flags, iterations, temperature,
+                     step_init=1.0, restraint=0.0, restraint_sc=0.0, grow=2.0, shrink=0.5, step_max=1024.0, starts=None, starts_mov=None,
+                     rec_anchor=None):
+    """ddp_pose_search_flex: C cycles of the search of search_flex.py on the replicas * S rows of the S sampled states (anchor [S, n, 3],
+    rec [S, m, 3], both fp32 and only read), in one launch.  As pose_search, with: tables: what flex_tables returns; perturb [C, rows,
+    6 + T + n_sc]; the moving atoms of the row state cur_mov, best_mov [rows, n_mov, 3] fp32; cur_e, best_e [rows, 6]; starts_mov
+    [C, rows, n_mov, 3] or None; rec_anchor [S, m, 3]: the anchor of the side-chain restraint (None: rec, the definition).  Shapes and
+    dtypes are checked here; no device tensor is downloaded."""
+    who = "pose_search_flex"
+    dev, S, n, m, rec_stride = pose_dims(who, anchor, rec, per_sample=True)
+    T = 0 if bonds is None else int(bonds.shape[0])
+    replicas, cycle0, iterations = int(replicas), int(cycle0), int(iterations)
+    if replicas < 1 or cycle0 < 0 or iterations < 0:
+        raise L.DdpError(f"{who}: replicas < 1, cycle0 < 0 or iterations < 0")
+    if u is None or u.dim() != 2:
+        raise L.DdpError(f"{who}: u [cycles, rows]")
+    mov, edge, sub, mapping, pairs = (tables[k] for k in ("mov", "edge_idx", "sub", "mapping", "pairs"))
+    n_mov, n_sc, n_sub = int(mov.shape[0]), int(edge.shape[0]), int(sub.shape[0])
+    rec_anchor = rec if rec_anchor is None else rec_anchor
+    Cn, rows = int(u.shape[0]), S * replicas
+    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+    state = [(anchor, f32, (S, n, 3), "anchor"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"), (rec, f32, (S, m, 3), "rec"),
+             (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (self_pairs, u8, (n, n), "self_pairs"),
+             (bonds, i32, (T, 2), "bonds"), (mask_rotate, u8, (T, n), "mask_rotate"), (rec_anchor, f32, (S, m, 3), "rec_anchor"),
+             (mov, i32, (n_mov,), "mov"), (edge, i32, (n_sc, 2), "sc_edge_idx"), (sub, i32, (n_sub,), "sc_sub"), (mapping, i32, (n_sc, 2), "sc_map"),
+             (pairs, u8, (n_mov, m), "sc_pairs")]
+    chain = [(perturb, f32, (Cn, rows, 6 + T + n_sc), "perturb"), (u, f64, (Cn, rows), "u"), (cur_pos, f32, (rows, n, 3), "cur_pos"),
+             (cur_mov, f32, (rows, n_mov, 3), "cur_mov"), (cur_e, f64, (rows, 6), "cur_e"), (best_pos, f32, (rows, n, 3), "best_pos"),
+             (best_mov, f32, (rows, n_mov, 3), "best_mov"), (best_e, f64, (rows, 6), "best_e"), (best_cycle, i32, (rows,), "best_cycle"),
+             (accepted, i32, (rows,), "accepted"), (trace, f64, (Cn, rows, 2), "trace"), (flags, u8, (Cn, rows), "flags"),
+             (starts, f32, (Cn, rows, n, 3), "starts"), (starts_mov, f32, (Cn, rows, n_mov, 3), "starts_mov")]
+    a = L.SearchFlexArgs(replicas=replicas, cycles=Cn, cycle0=cycle0, step_init=float(step_init), temperature=float(temperature))
+    a.flex = _pose_args(L.MinimizeFlexArgs, who, dev, state, ("self_pairs",) + (("bonds", "mask_rotate") if T == 0 else ()), config, n_samples=S,
+                        n=n, m=m, rec_stride=rec_stride, n_tor=T, iterations=iterations, restraint=float(restraint), grow=float(grow),
+                        shrink=float(shrink), step_max=float(step_max), n_mov=n_mov, n_sc=n_sc, n_sub=n_sub, restraint_sc=float(restraint_sc))
+    check_tensors(who, dev, chain, ("starts", "starts_mov"))
+    for t, _, _, name in chain:
+        setattr(a, name, _p(t) or None)
+    L.check(L.load().ddp_pose_search_flex(C.byref(a), stream()), "ddp_pose_search_flex")
+
+
 # ------------------------------------------------------------------------------------------------ pocket finder (csrc/ddp_pockets.hip)
 def _grid_n(dims) -> int:
     nx, ny, nz = (int(d) for d in dims)

@@ -307,16 +307,18 @@ def write_searched_csv(path: str, searched, order=None) -> str:
     """searched.csv of one complex: one row per pose in RANKED order (search.SearchResult of the ranked poses).  rank and sample as
     minimized.csv; total_* are scoring.PoseScores.total of the pose before and after (comparable with scores.csv); energy_* the E of
     search.py of the sampled pose, after the plain descent of replica 0 and of the result; best_replica and best_cycle say which chain
-    found the result and when (-1: the sampled pose itself), moves counts that chain's Metropolis moves, rmsd_moved is in angstrom."""
+    found the result and when (-1: the sampled pose itself), moves counts that chain's Metropolis moves, rmsd_moved is in angstrom.  A
+    search_flex.FlexSearchResult (energies [N, 6]): the same columns, energy_* the joint E of search_flex.py."""
     import csv
     r = searched.cpu()
+    e = r.energy_after.shape[1] - 1            # the column of E: 3, or 5 for the joint energy
     sample = list(range(r.lig_pos.shape[0])) if order is None else [int(v) for v in _np(order).reshape(-1)]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(SEARCHED_COLUMNS)
         for k in range(r.lig_pos.shape[0]):
             w.writerow([k + 1, sample[k], f"{float(r.scores_before.total[k]):.6g}", f"{float(r.scores_after.total[k]):.6g}",
-                        f"{float(r.energy_before[k, 3]):.6g}", f"{float(r.energy_minimized[k, 3]):.6g}", f"{float(r.energy_after[k, 3]):.6g}",
+                        f"{float(r.energy_before[k, e]):.6g}", f"{float(r.energy_minimized[k, e]):.6g}", f"{float(r.energy_after[k, e]):.6g}",
                         int(r.replica[k]), int(r.cycle[k]), int(r.moves[k]), f"{float(r.rmsd_moved[k]):.4f}"])
     return path
 
@@ -339,6 +341,14 @@ def write_minimized_sidechains_csv(path: str, minimized, order=None) -> str:
             w.writerow([k + 1, sample[k], f"{float(r.energy_before[k, 2]):.6g}", f"{float(r.energy_after[k, 2]):.6g}",
                         f"{float(r.energy_after[k, 4]):.6g}", f"{float(r.sidechain_rmsd_moved[k]):.4f}"])
     return path
+
+
+def write_searched_sidechains_csv(path: str, searched, order=None) -> str:
+    """searched_sidechains.csv of one complex whose side chains were searched with the ligand (search_flex.FlexSearchResult of the ranked
+    poses): the columns of minimized_sidechains.csv, one row per pose in RANKED order; sc_* the side chains' own pair energy sc(y) of the
+    sampled state and of the result, sidechain_restraint_after their restraint term, sidechain_rmsd_moved the RMSD over the moving atoms
+    in angstrom."""
+    return write_minimized_sidechains_csv(path, searched, order)
 
 
 # ---------------------------------------------------------------------------------------------- interaction profile
@@ -452,7 +462,8 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
     interactions (interactions.InteractionProfile of the ranked poses; interaction_reference: of the known pose): also interactions.csv,
     interaction_summary.csv and interaction_similarity.csv.
     searched (search.SearchResult of the ranked poses): also rank{k}_searched.sdf, the pose after the search in the physics score, and
-    searched.csv."""
+    searched.csv; a search_flex.FlexSearchResult: also rank{k}_searched_protein.pdb, the receptor with the side chains the pose was
+    searched with (write_receptor), and searched_sidechains.csv."""
     os.makedirs(write_dir, exist_ok=True)
     mol = heavy_molecule(sdf_text)
     name, oc = sdf_name(sdf_text), getattr(graph, "original_center", None)
@@ -513,6 +524,12 @@ def write_complex(write_dir: str, sdf_text: str, pdb_text: Optional[str], graph,
         for k in range(searched.lig_pos.shape[0]):
             write_sdf(put(os.path.join(write_dir, f"rank{k + 1}_searched.sdf")), mol, searched.lig_pos[k], name, oc)
         write_searched_csv(put(os.path.join(write_dir, "searched.csv")), searched, order)
+        if hasattr(searched, "atom_pos"):
+            mv = moving_atoms(graph).tolist()
+            for k in range(searched.atom_pos.shape[0]):
+                write_receptor(put(os.path.join(write_dir, f"rank{k + 1}_searched_protein.pdb")), pdb_text, graph,
+                               [_np(searched.atom_pos[k])[mv]], remove_hs)
+            write_searched_sidechains_csv(put(os.path.join(write_dir, "searched_sidechains.csv")), searched, order)
     if interactions is not None:
         write_interactions_csv(put(os.path.join(write_dir, "interactions.csv")), interactions, order)
         write_interaction_summary_csv(put(os.path.join(write_dir, "interaction_summary.csv")), interactions)

@@ -35,8 +35,8 @@ numbers of all config.cycles cycles, so advance(a) followed by advance(b) equals
 
 What it is not:
   - not Vina's search: all degrees of freedom move at once, and the local step is the line search of descent.py, not BFGS;
-  - no side-chain or receptor motion: flexible rows search against each sample's own, fixed side chains (MinimizeConfig.sidechains
-    is not combined with it);
+  - no side-chain or receptor motion here: this class searches flexible rows against each sample's own, fixed side chains.  The
+    search that moves the side chains with the ligand is search_flex.py (SearchConfig.sidechains, FlexPoseSearcher);
   - no hydrogens;
   - the score is not validated against smina or Vina (see scoring.py), so a lower E is not a better pose;
   - no exchange between replicas (no parallel tempering).
@@ -78,6 +78,9 @@ class SearchConfig:
     sigma_tor: float = 0.5        # of the random torsion steps, rad per bond
     seed: int = 0                 # of the CPU generator that draws perturb and u
     restraint: float = 0.0        # k of the restraint to the sampled pose
+    sidechains: bool = False      # run_csv: flexible rows go through search_flex.FlexPoseSearcher (PoseSearcher ignores it)
+    sigma_chi: float = 0.3        # search_flex.py: standard deviation of the random side-chain steps, rad per bond
+    sidechain_restraint: float = 0.0   # k_sc of search_flex.py, the restraint of the moving side-chain atoms to their sampled positions
 
 
 @dataclass

@@ -1121,6 +1121,58 @@ typedef struct {
 } ddp_search_select_args_t;
 int ddp_pose_search_select(const ddp_search_select_args_t* args, void* stream);
 
+/* ---- the same search with the flexible side chains of the receptor in the state: the random move also turns the side-chain bonds, and
+ * the descent of a cycle is the joint line search of ddp_pose_minimize_flex (csrc/ddp_search_flex.hip; host side
+ * diffdock_pocket_amd/search_flex.py, whose module docstring states the whole definition).  Rows, cycles, the Metropolis rule, the
+ * best-so-far rule, trace, flags, cycle0 and the indexing of the per-cycle arrays by the cycle OF THIS CALL are those of
+ * ddp_pose_search, read on entry 5 of the six energies (inter, intra, sc, ligand restraint term, side-chain restraint term, E).
+ * `flex` carries the score, the side-chain tables and the line search as for ddp_pose_minimize_flex: n_samples, n, m, rec_stride, n_tor,
+ * iterations (of one descent), anchor (the sampled poses x0), lig_radii, lig_flags, rec (the sampled receptors y0, one per pose, READ
+ * ONLY here: the replicas of a pose share it; its moving atoms are read for the fresh state, every other atom throughout), rec_anchor
+ * (the anchor of the side-chain restraint: rec itself in the definition), rec_radii, rec_flags, self_pairs, bonds, mask_rotate, form,
+ * restraint, restraint_sc, grow, shrink, step_max, n_mov, n_sc, n_sub, mov, sc_edge_idx, sc_sub, sc_map, sc_pairs.  Its pos, step,
+ * accepted, energy_in, energy_out, history, grad and grad_mov are not read and may be NULL.  Every descent starts with step = step_init.
+ * perturb [cycles][rows][6 + n_tor + n_sc] fp32: tr, rot, the ligand torsions in bond order, then one angle per side-chain bond in list
+ * order.  The start state of a cycle: the pose map of ddp_pose_update on cur_pos and the arithmetic of ddp_sidechain_update (bonds in
+ * list order, fp32, no re-alignment) on cur_mov; optional records starts [cycles][rows][n][3] and starts_mov [cycles][rows][n_mov][3].
+ * Row state, in and out: cur_pos, best_pos [rows][n][3] and cur_mov, best_mov [rows][n_mov][3] fp32 (the moving atoms only, in the
+ * order of mov), cur_e, best_e [rows][6] fp64, best_cycle and accepted int32 [rows].  cycle0 = 0: the state is not read, the kernel
+ * writes the fresh state (cur_pos = best_pos = x0, cur_mov = best_mov = the moving atoms of rec, every energy +inf, best_cycle -1,
+ * accepted 0) and replica 0 starts its first cycle at the sampled state bit for bit, its perturb entries ignored.  x and y are always
+ * taken or kept together.
+ * Invariants: those of ddp_pose_search (two launches, batch against single pose, a + b cycles against a then b: the same bits).  The
+ * local descent of a cycle equals ddp_pose_minimize_flex from (starts[c][q], rec[s] with starts_mov[c][q] in place of its moving
+ * atoms) with the anchors (x0[s], rec_anchor[s]), step_init and `iterations` iterations, bit for bit (one loop,
+ * csrc/ddp_minimize_flex_loop.h).  With n_mov = n_sc = 0: cur_pos, best_pos, best_cycle, accepted, trace, flags and entries 0, 1 and 5
+ * of the energies are the bits of ddp_pose_search (its entries 0, 1 and 3).  No atomics, every sum in a fixed order, no data-dependent
+ * control flow around a barrier.  A NaN in x or in a moving atom makes the row never move: beyond the fresh state it writes only its
+ * trace and flags (and the unchanged scalars of its state); it touches no other row.  cur_* / best_* of a row are written only on a
+ * move / an improvement.
+ * LDS plan and limits: those of ddp_pose_minimize_flex, unchanged (18496 bytes + 89 n + 81 n_mov + 4 n_sc, at most 64 KiB; DDP_ELIMIT
+ * above DDP_MINIMIZE_MAX_ATOMS, DDP_MINIMIZE_MAX_TORSIONS, DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS or
+ * DDP_MINIMIZE_FLEX_MAX_STATE_BYTES).  n_samples = 0 or cycles = 0: no-op.  DDP_EINVAL without a launch: what ddp_pose_minimize_flex
+ * and ddp_pose_search reject (of the pointers: those read here), and a NULL cur_mov or best_mov with n_mov > 0. */
+typedef struct {
+  ddp_minimize_flex_args_t flex; /* the score, the side-chain tables and the line search, see above */
+  int32_t replicas, cycles, cycle0, reserved;
+  double step_init, temperature;
+  const float* perturb;         /* [cycles][rows][6 + n_tor + n_sc] */
+  const double* u;              /* [cycles][rows] */
+  float* cur_pos;               /* [rows][n][3], in/out */
+  float* cur_mov;               /* [rows][n_mov][3], in/out */
+  double* cur_e;                /* [rows][6], in/out */
+  float* best_pos;              /* [rows][n][3], in/out */
+  float* best_mov;              /* [rows][n_mov][3], in/out */
+  double* best_e;               /* [rows][6], in/out */
+  int32_t* best_cycle;          /* [rows], in/out */
+  int32_t* accepted;            /* [rows], in/out */
+  double* trace;                /* [cycles][rows][2] */
+  uint8_t* flags;               /* [cycles][rows] */
+  float* starts;                /* [cycles][rows][n][3] or NULL */
+  float* starts_mov;            /* [cycles][rows][n_mov][3] or NULL */
+} ddp_search_flex_args_t;
+int ddp_pose_search_flex(const ddp_search_flex_args_t* args, void* stream);
+
 /* ---- geometric pocket finder: LIGSITE-style buriedness on a grid (csrc/ddp_pockets.hip; host side diffdock_pocket_amd/pockets.py, which
  * states the whole definition).  This project's own method, no learned predictor.  Grid point (i, j, k), 0 <= i < nx ..., has the flat
  * index g = (i ny + j) nz + k and sits at lo + (i, j, k) spacing; everything outside the grid is free space.  nx ny nz < 2^31.
