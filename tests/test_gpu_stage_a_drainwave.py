@@ -1,6 +1,7 @@
 """ddp_stage_a_gh3's store-wave kernel (ddp_stage_a_g3dw_kernel: 3 MFMA waves + 1 store wave per workgroup) against the four symmetric
 waves it replaces for long products: the two write the SAME BYTES - G planes, Gb, padding - and raise range_flag alike, whatever tile or
-workgroup a row sits in.  ddp_sa_drainwave (include/ddp_hip.h) selects the form: 0 = symmetric, 2 = store wave for every product."""
+workgroup a row sits in.  ddp_sa_drainwave (include/ddp_hip.h) selects the form: 0 = symmetric, 2 = store wave for every product.
+The symmetric form is only the yardstick HERE: tests/test_gpu_stage_a_planes_fp64.py is where both forms meet the definition (fp64, byte for byte)."""
 import ctypes as C
 
 import pytest
