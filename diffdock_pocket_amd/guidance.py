@@ -146,11 +146,11 @@ class GuidanceWorkspace:
         LA.clash_guidance(a, torch._C._cuda_getCurrentRawStream(pos.device.index))
 
 
-def check_config(weight, t_max, max_tr, max_rot, max_tor):
-    """Negative or NaN values raise (a cap of +infinity is allowed: no cap)."""
-    for name, v in (("clash_guidance_weight", weight), ("clash_guidance_t_max", t_max), ("clash_guidance_max_tr", max_tr),
-                    ("clash_guidance_max_rot", max_rot), ("clash_guidance_max_tor", max_tor)):
+def check_config(weight, t_max, max_tr, max_rot, max_tor, prefix: str = "clash_guidance"):
+    """Negative or NaN values raise (a cap of +infinity is allowed: no cap).  prefix: the SamplerConfig fields' common name, for the
+    messages (score_guidance.py checks its own five through here)."""
+    for name, v in (("weight", weight), ("t_max", t_max), ("max_tr", max_tr), ("max_rot", max_rot), ("max_tor", max_tor)):
         if not float(v) >= 0.0:
-            raise ValueError(f"{name} must not be negative or NaN, got {v!r}")
+            raise ValueError(f"{prefix}_{name} must not be negative or NaN, got {v!r}")
     if math.isinf(float(weight)):
-        raise ValueError("clash_guidance_weight must be finite")
+        raise ValueError(f"{prefix}_weight must be finite")

@@ -573,10 +573,13 @@ def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
 
 # ---------------------------------------------------------------------------------------------- command line
 def _guidance_fields(a) -> Dict:
-    """The --clash_guidance* flags as SamplerConfig fields."""
+    """The --clash_guidance* and --score_guidance* flags as SamplerConfig fields (clash first, five each)."""
     return dict(clash_guidance_weight=a.clash_guidance, clash_guidance_t_max=a.clash_guidance_t_max,
                 clash_guidance_max_tr=a.clash_guidance_max_tr, clash_guidance_max_rot=a.clash_guidance_max_rot,
-                clash_guidance_max_tor=a.clash_guidance_max_tor)
+                clash_guidance_max_tor=a.clash_guidance_max_tor,
+                score_guidance_weight=a.score_guidance, score_guidance_t_max=a.score_guidance_t_max,
+                score_guidance_max_tr=a.score_guidance_max_tr, score_guidance_max_rot=a.score_guidance_max_rot,
+                score_guidance_max_tor=a.score_guidance_max_tor)
 
 
 def _parser():
@@ -621,6 +624,14 @@ def _parser():
     p.add_argument("--clash_guidance_max_tr", type=float, default=1.0, help="cap of the guidance translation per step (Angstrom)")
     p.add_argument("--clash_guidance_max_rot", type=float, default=0.5, help="cap of the guidance rotation per step (rad)")
     p.add_argument("--clash_guidance_max_tor", type=float, default=0.5, help="cap of the guidance torsion step per bond (rad)")
+    p.add_argument("--score_guidance", type=float, default=0.0, metavar="W",
+                   help="> 0: nudge every denoising step down the gradient of the Vinardo-form physics score (inter + intra, the "
+                        "graph's pocket atoms) with this per-step weight (score_guidance.py; untuned, not validated on real "
+                        "checkpoints; default: off)")
+    p.add_argument("--score_guidance_t_max", type=float, default=1.0, help="guide only the steps with diffusion time t <= this")
+    p.add_argument("--score_guidance_max_tr", type=float, default=1.0, help="cap of the score-guidance translation per step (Angstrom)")
+    p.add_argument("--score_guidance_max_rot", type=float, default=0.5, help="cap of the score-guidance rotation per step (rad)")
+    p.add_argument("--score_guidance_max_tor", type=float, default=0.5, help="cap of the score-guidance torsion step per bond (rad)")
     p.add_argument("--cluster_rmsd", type=float, default=None,
                    help="group the ranked poses into binding modes at this symmetry-corrected RMSD cutoff and write modes.csv (default: off)")
     p.add_argument("--resolve_clashes", action="store_true", default=False,
@@ -767,9 +778,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         graph_kwargs["flexdist"] = float(margs.flexdist)
     try:
         from .guidance import check_config
-        check_config(*_guidance_fields(a).values())
+        fields = list(_guidance_fields(a).values())
+        check_config(*fields[:5])
+        check_config(*fields[5:], prefix="score_guidance")
     except ValueError as e:
-        ap.error(str(e).replace("clash_guidance_weight", "--clash_guidance").replace("clash_guidance_", "--clash_guidance_"))
+        msg = str(e)
+        for kind in ("clash", "score"):
+            msg = msg.replace(f"{kind}_guidance_weight", f"--{kind}_guidance").replace(f"{kind}_guidance_", f"--{kind}_guidance_")
+        ap.error(msg)
     cfg = SamplerConfig(inference_steps=a.inference_steps, sigma=sigma,
                         temp_sampling=[a.temp_sampling_tr, a.temp_sampling_rot, a.temp_sampling_tor, a.temp_sampling_sc_tor],
                         temp_psi=[a.temp_psi_tr, a.temp_psi_rot, a.temp_psi_tor, a.temp_psi_sc_tor], temp_sigma_data=a.temp_sigma_data,

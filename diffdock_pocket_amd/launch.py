@@ -811,6 +811,12 @@ def clash_guidance(a: L.GuidanceArgs, st=None):
     L.check(L.load().ddp_clash_guidance(C.byref(a), stream() if st is None else st), "ddp_clash_guidance")
 
 
+def score_guidance(a: L.ScoreGuidanceArgs, st=None):
+    """ddp_score_guidance: the score-guidance increments of a.pos added to a.upd, on stream `st` (None: the current stream of the
+    current device).  score_guidance.ScoreGuidanceWorkspace builds the struct and checks the tensors."""
+    L.check(L.load().ddp_score_guidance(C.byref(a), stream() if st is None else st), "ddp_score_guidance")
+
+
 # ------------------------------------------------------------------------------------------------ physics score (csrc/ddp_score.hip)
 def pose_score(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, tor_divisor=1.0, self_pairs=None, energy=None, grad=None,
                with_grad=False):

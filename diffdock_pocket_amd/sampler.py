@@ -208,11 +208,26 @@ class SamplerConfig:
     clash_guidance_max_tr: float = 1.0
     clash_guidance_max_rot: float = 0.5
     clash_guidance_max_tor: float = 0.5
+    # physics-score guidance (score_guidance.py, which states the definition; this project's own term): > 0 adds, at every step with
+    # t <= score_guidance_t_max, the capped descent direction of the Vinardo-form score (inter + intra of scoring.py, with the
+    # constants of score_guidance_config; None: ScoreConfig()) times this weight to the tr / rot / tor updates, after clash guidance
+    # where both are on.  A per-step constant like clash_guidance_weight; schedule and caps are untuned choices.  0: nothing is
+    # allocated, launched or uploaded.
+    score_guidance_weight: float = 0.0
+    score_guidance_t_max: float = 1.0
+    score_guidance_max_tr: float = 1.0
+    score_guidance_max_rot: float = 0.5
+    score_guidance_max_tor: float = 0.5
+    score_guidance_config: Optional["ScoreConfig"] = None     # scoring.ScoreConfig
 
     def __post_init__(self):
         from .guidance import check_config
         check_config(self.clash_guidance_weight, self.clash_guidance_t_max, self.clash_guidance_max_tr, self.clash_guidance_max_rot,
                      self.clash_guidance_max_tor)
+        check_config(self.score_guidance_weight, self.score_guidance_t_max, self.score_guidance_max_tr, self.score_guidance_max_rot,
+                     self.score_guidance_max_tor, prefix="score_guidance")
+        if self.score_guidance_config is not None:
+            self.score_guidance_config.check()
 
 
 class Sampler:
@@ -265,6 +280,9 @@ class Sampler:
         self.guidance = cfg.clash_guidance_weight > 0
         if self.guidance:
             self._init_guidance(g)
+        self.score_guidance = cfg.score_guidance_weight > 0
+        if self.score_guidance:
+            self._init_score_guidance(g)
 
     # -- steric-clash guidance (SamplerConfig.clash_guidance_weight > 0; guidance.py) ---------------------------------
     def _init_guidance(self, g):
@@ -281,6 +299,22 @@ class Sampler:
         """w_t of guidance.py: the weight while t <= clash_guidance_t_max, else 0."""
         from .guidance import step_weight
         return step_weight(self.cfg.clash_guidance_weight, t, self.cfg.clash_guidance_t_max)
+
+    # -- physics-score guidance (SamplerConfig.score_guidance_weight > 0; score_guidance.py) -------------------------
+    def _init_score_guidance(self, g):
+        """The host tables (once; a ligand above the kernel's limits raises here) and, on a HIP device, the workspace of the one
+        ddp_score_guidance launch.  With no_torsion the direction is rigid only."""
+        from . import score_guidance
+        cfg = self.cfg
+        self.sguid_caps = (cfg.score_guidance_max_tr, cfg.score_guidance_max_rot, cfg.score_guidance_max_tor)
+        self.sguid_tables = score_guidance.build_tables(g, torsions=not cfg.no_torsion, config=cfg.score_guidance_config)
+        if self.on_hip:
+            self.sguid_ws = score_guidance.ScoreGuidanceWorkspace(self.sguid_tables, self.device, self.sguid_caps)
+
+    def _score_guidance_weight(self, t: float) -> float:
+        """w_t of score_guidance.py: the weight while t <= score_guidance_t_max, else 0."""
+        from .score_guidance import step_weight
+        return step_weight(self.cfg.score_guidance_weight, t, self.cfg.score_guidance_t_max)
 
     # -- SVGD particle interaction (SamplerConfig.svgd_weight > 0; svgd.py) ------------------------------------------
     def _init_svgd(self, g):
@@ -455,6 +489,8 @@ class Sampler:
             host[2:5] = torch.tensor(self._svgd_gdt(t_idx, schedule), dtype=torch.float64).float()     # read by ddp_svgd_rows
         if self.guidance:
             host[5] = self._guidance_weight(t)                                                         # read by ddp_clash_guidance
+        if self.score_guidance:
+            host[6] = self._score_guidance_weight(t)                                                   # read by ddp_score_guidance
         host[8:16] = torch.tensor(coef, dtype=torch.float64).float()
         o = self._off
 
@@ -516,6 +552,9 @@ class Sampler:
         if self.guidance:  # after SVGD (svgd_only does not erase it), against the receptor before this step's side-chain update
             self.guid_ws.launch(self.lig_pos, self.atom_pos if self.has_flex else None,
                                 (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[5:6])
+        if self.score_guidance:  # after clash guidance, on the same poses against the same receptor
+            self.sguid_ws.launch(self.lig_pos, self.atom_pos if self.has_flex else None,
+                                 (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[6:7])
         if self.has_flex:
             L.check(lib.ddp_sidechain_update(self.atom_pos.data_ptr(), self.n, self.n_a, self.upd["sc"].data_ptr(), self.S,
                                              self.sc_edge_i32.data_ptr(), self.sc_sub_i32.data_ptr(), self.sc_map_i32.data_ptr(),
@@ -713,6 +752,11 @@ class Sampler:
             guid = guidance.increments_torch(self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else self.guid_tables.rec,
                                              self.guid_tables, self._guidance_weight(t), cfg.clash_guidance_max_tr,
                                              cfg.clash_guidance_max_rot, cfg.clash_guidance_max_tor)
+        sguid = None
+        if self.score_guidance:  # the same poses and receptor; added after the clash increments
+            from . import score_guidance
+            sguid = score_guidance.increments_torch(self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else self.sguid_tables.rec,
+                                                    self.sguid_tables, self._score_guidance_weight(t), self.sguid_caps)
 
         def perturb(score, g, sigma, lo, hi, k, zz):
             if cfg.ode:
@@ -753,6 +797,10 @@ class Sampler:
             tr_p, rot_p = tr_p + guid[0].to(dev), rot_p + guid[1].to(dev)
             if tor_p is not None:
                 tor_p = tor_p + guid[2].to(dev)
+        if sguid is not None:
+            tr_p, rot_p = tr_p + sguid[0].to(dev), rot_p + sguid[1].to(dev)
+            if tor_p is not None:
+                tor_p = tor_p + sguid[2].to(dev)
         if self.lig_pos.is_cuda:   # one HIP launch; the PyTorch form below is the same arithmetic (CPU tests)
             self.lig_pos = modify_conformer_hip(self.lig_pos, tr_p, rot_p, tor_p, self.bonds_i32, self.mask_u8)
         else:

@@ -1239,6 +1239,43 @@ typedef struct {
 } ddp_clash_guidance_args_t;
 int ddp_clash_guidance(const ddp_clash_guidance_args_t* args, void* stream);
 
+/* ---- physics-score guidance term of the reverse-diffusion step (csrc/ddp_score_guidance.hip; host side
+ * diffdock_pocket_amd/score_guidance.py and sampler.py).  This project's own term, not part of the reference.  At a denoising step the
+ * updates of sample s are nudged down the gradient of the Vinardo-form score of ddp_pose_score, along the sampler's own degrees of
+ * freedom: unlike ddp_clash_guidance the energy has attractive terms.  pos, lig_radii, lig_flags, rec, m, rec_stride, rec_radii,
+ * rec_flags, self_pairs and form exactly as ddp_pose_score (a negative radius: untyped, the atom takes part in nothing); bonds
+ * [n_tor][2], mask_rotate [n_tor][n] as ddp_refine_direction.  With g = dE/dx the fp64 gradient of E = inter + intra (the energy of
+ * ddp_pose_minimize at restraint 0, not divided by a torsion divisor), steps 1 to 4 are those of ddp_clash_guidance above: w = *weight
+ * from DEVICE memory (unless w > 0 the workgroups return before any store: upd, energy and grad are left untouched), the direction of
+ * ddp_refine_direction for step[s] = w rounded to fp32, the cap factor in fp64 from those fp32 values, upd_X[s] += (float)(f_s *
+ * (double)d_X), every element by one thread, no atomics.  The term runs after ddp_clash_guidance where both are on.
+ * energy [n_samples][2] = (inter, intra) and grad [n_samples][n][3] = g are optional outputs (NULL: not written), bit for bit what
+ * ddp_pose_score gives; with caps of +infinity and upd = 0 the increments are bit for bit ddp_refine_direction's on that gradient.
+ * One 256-thread workgroup per sample; LDS: the receptor tile and its flags (17 KiB), the fp64 gradient, the pose, radii and flags
+ * (41 n bytes), the torsion components (4 n_tor) and 480 bytes of scratch: 62.5 KiB at both limits.  Every sum in a fixed order: two
+ * launches give the same bits; a NaN pose poisons its own sample only.  n_samples = 0: no-op; m = 0: no ligand-receptor term; n_tor =
+ * 0: rigid only (bonds, mask_rotate, upd[2] may be NULL).  n > DDP_EVAL_MAX_ATOMS or n_tor > DDP_GUIDANCE_MAX_TORSIONS: DDP_ELIMIT; a
+ * NULL pointer, a bad shape, a negative or NaN cap, the constant checks of ddp_score_form_t: DDP_EINVAL; nothing is launched. */
+typedef struct {
+  int32_t n_samples, n, m, rec_stride, n_tor;
+  const float* pos;             /* [n_samples][n][3] */
+  const float* lig_radii;       /* [n] */
+  const uint8_t* lig_flags;     /* [n] */
+  const float* rec;             /* [m][3], or [n_samples] blocks rec_stride floats apart */
+  const float* rec_radii;       /* [m] */
+  const uint8_t* rec_flags;     /* [m] */
+  const uint8_t* self_pairs;    /* [n][n] or NULL */
+  const int32_t* bonds;         /* [n_tor][2] */
+  const uint8_t* mask_rotate;   /* [n_tor][n] */
+  ddp_score_form_t form;        /* the constants of the score form */
+  const float* weight;          /* one value, device memory */
+  double max_tr, max_rot, max_tor;
+  float* upd[3];                /* [n_samples][3], [n_samples][3], [n_samples][n_tor] */
+  double* energy;               /* [n_samples][2] or NULL */
+  double* grad;                 /* [n_samples][n][3] or NULL */
+} ddp_score_guidance_args_t;
+int ddp_score_guidance(const ddp_score_guidance_args_t* args, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
 /* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, the csrc headers, include/ddp_hip.h) the library was built from */
