@@ -22,10 +22,12 @@ DDP_EVAL_MAX_ATOMS = 1024
 DDP_GUIDANCE_MAX_TORSIONS = 1024
 DDP_MINIMIZE_MAX_ATOMS, DDP_MINIMIZE_MAX_TORSIONS = 512, 4096
 DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS, DDP_MINIMIZE_FLEX_MAX_STATE_BYTES = 256, 256, 47040
+DDP_SCORE_GUIDANCE_FLEX_MAX_ATOMS, DDP_SCORE_GUIDANCE_FLEX_MAX_TORSIONS = DDP_MINIMIZE_MAX_ATOMS, DDP_GUIDANCE_MAX_TORSIONS
+DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING, DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS = DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS
 DDP_PAIRWISE_MAX_SAMPLES, DDP_CLUSTER_MAX_SAMPLES = 32768, 1024
 EXPORTS = ["ddp_conv_messages", "ddp_conv_rows", "ddp_stage_a_gh", "ddp_stage_a_gh3", "ddp_segment_reduce", "ddp_edge_featurize", "ddp_edge_featurize_jobs", "ddp_torsion_sh", "ddp_stage_a", "ddp_stage_a_h2",
            "ddp_pose_update", "ddp_sidechain_update", "ddp_sde_update", "ddp_radius_count", "ddp_radius_fill", "ddp_knn", "ddp_group_by_key", "ddp_node_linear", "ddp_scan_jobs", "ddp_mark_jobs", "ddp_rowcopy_jobs", "ddp_select_jobs",
-           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_score_guidance", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pose_search", "ddp_pose_search_select", "ddp_pose_search_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_conv_deal_tile", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
+           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_score_guidance", "ddp_score_guidance_flex", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pose_search", "ddp_pose_search_select", "ddp_pose_search_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_conv_deal_tile", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
 
 
 class Seg(C.Structure):
@@ -152,6 +154,14 @@ class ScoreGuidanceArgs(C.Structure):
                 ("rec", _P), ("rec_radii", _P), ("rec_flags", _P), ("self_pairs", _P), ("bonds", _P), ("mask_rotate", _P), ("form", ScoreForm),
                 ("weight", _P), ("max_tr", C.c_double), ("max_rot", C.c_double), ("max_tor", C.c_double), ("upd", _P * 3), ("energy", _P),
                 ("grad", _P)]
+
+
+class ScoreGuidanceFlexArgs(C.Structure):
+    """ddp_score_guidance_flex_args_t of include/ddp_hip.h: the fields of ddp_score_guidance_args_t up to upd, then the side chains'."""
+    _anonymous_ = ("form",)
+    _fields_ = ScoreGuidanceArgs._fields_[:-2] + [("n_mov", _I), ("n_sc", _I), ("n_sub", _I), ("reserved", _I), ("mov", _P), ("sc_edge_idx", _P),
+                                                  ("sc_sub", _P), ("sc_map", _P), ("sc_pairs", _P), ("max_sc", C.c_double), ("upd_sc", _P),
+                                                  ("energy", _P), ("grad_mov", _P)]
 
 
 class ProfileArgs(C.Structure):
@@ -376,6 +386,8 @@ def load():
     lib.ddp_clash_guidance.restype = C.c_int
     lib.ddp_score_guidance.argtypes = [C.POINTER(ScoreGuidanceArgs), C.c_void_p]
     lib.ddp_score_guidance.restype = C.c_int
+    lib.ddp_score_guidance_flex.argtypes = [C.POINTER(ScoreGuidanceFlexArgs), C.c_void_p]
+    lib.ddp_score_guidance_flex.restype = C.c_int
     lib.ddp_pose_score.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
     lib.ddp_pose_score.restype = C.c_int
     lib.ddp_pose_profile.argtypes = [C.POINTER(ProfileArgs), C.c_void_p]

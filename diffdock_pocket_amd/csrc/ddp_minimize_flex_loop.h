@@ -95,8 +95,10 @@ __device__ __forceinline__ FxLds fx_carve(unsigned char* p, int n, int n_mov, in
 }
 
 // the tables of the plan: the ligand's radii and flags, the moving atoms' receptor indices, radii and flags.  An index outside the
-// receptor: no read, the atom takes part in nothing.  Visible after the caller's next barrier.
-__device__ __forceinline__ void fx_load_tables(const ddp_minimize_flex_args_t& A, const FxLds& L) {
+// receptor: no read, the atom takes part in nothing.  Visible after the caller's next barrier.  Args: ddp_minimize_flex_args_t, or the
+// struct of another entry with the same field names (ddp_score_guidance_flex_args_t).
+template <class Args>
+__device__ __forceinline__ void fx_load_tables(const Args& A, const FxLds& L) {
   const int tid = threadIdx.x, n = A.n, m = A.m, n_mov = A.n_mov;
   for (int i = tid; i < n; i += DDP_FX_THREADS) { L.rad[i] = A.lig_radii[i]; L.lflag[i] = A.lig_flags[i]; }
   for (int r = tid; r < n_mov; r += DDP_FX_THREADS) {
@@ -140,24 +142,15 @@ __device__ __forceinline__ void fx_atom(const FxLds& L, int n_mov, const float* 
   else { p[0] = rs[3 * a]; p[1] = rs[3 * a + 1]; p[2] = rs[3 * a + 2]; }
 }
 
-// Energy [inter, intra, sc, ligand restraint term, side-chain restraint term, E] -> L.et, gradients -> g and gm of the state (x, ym)
-// (LDS, visible to all threads on entry).  Ends with a barrier: L.et, g and gm are visible on return.
-__device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, const FxLds& L, const float* rs, const float* __restrict__ as,
-                                         const float* __restrict__ ras, const float* x, const float* ym, double* g, double* gm) {
+// The second pass of one evaluation, for the state (x, ym) in LDS with the receptor tile of score_evaluate (patched by FxPatch) still in
+// L.tile when m <= one tile: gm = d inter / dy_a + d sc / dy_a of every moving atom (lane 0 of the owning wave: visible after the
+// caller's next barrier) and L.we2 = the waves' partial sums of the four unweighted sc terms.  Shared by fx_evaluate below and by
+// ddp_score_guidance_flex_kernel (ddp_score_guidance_flex.hip).  Args as fx_load_tables.
+template <class Args>
+__device__ __forceinline__ void fx_second_pass(const Args& A, const FxLds& L, const float* rs, const float* x, const float* ym, double* gm) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m, n_mov = A.n_mov;
   const FxPatch patch = {L.mov, n_mov, ym};
-  score_evaluate<true>(A, rs, L.tile, L.tflag, x, L.rad, L.lflag, g, L.we, patch);
-  // the ligand restraint, as mz_evaluate of ddp_minimize_loop.h
-  const double krest = 2.0 * A.restraint / (double)n;
-  double er_w = 0.0;
-  for (int i = wave; i < n; i += DDP_FX_WAVES) {
-    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
-    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
-    er_w += ax * ax + ay * ay + az * az;
-    if (lane == 0) { g[3 * i] = g[3 * i] + krest * ax; g[3 * i + 1] = g[3 * i + 1] + krest * ay; g[3 * i + 2] = g[3 * i + 2] + krest * az; }
-  }
-  if (lane == 0) L.wr[wave] = er_w;
-  // ---- the second pass.  d inter / dy_a by gather over the ligand atoms; the assignment also clears gm
+  // d inter / dy_a by gather over the ligand atoms; the assignment also clears gm
   const ddp_score_form_t& F = A.form;
   const double cut2 = F.cutoff * F.cutoff;
   for (int r = wave; r < n_mov; r += DDP_FX_WAVES) {
@@ -213,6 +206,41 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
       if (lane == 0) { gm[3 * r] += gx; gm[3 * r + 1] += gy; gm[3 * r + 2] += gz; }
     }
   }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double c = wave_sum(st.t[k]) + 0.5 * wave_sum(mv.t[k]);
+    if (lane == 0) L.we2[wave][k] = c;
+  }
+}
+
+// by one thread, after the barrier behind fx_second_pass: sc = the weighted sum of the four terms, the waves in wave order
+__device__ __forceinline__ double fx_sc_total(const ddp_score_form_t& F, const double (*we2)[4]) {
+  double c[4];
+  for (int k = 0; k < 4; ++k) {
+    c[k] = we2[0][k];
+    for (int w = 1; w < DDP_FX_WAVES; ++w) c[k] += we2[w][k];
+  }
+  return F.w_gauss * c[0] + F.w_repulsion * c[1] + F.w_hydrophobic * c[2] + F.w_hbond * c[3];
+}
+
+// Energy [inter, intra, sc, ligand restraint term, side-chain restraint term, E] -> L.et, gradients -> g and gm of the state (x, ym)
+// (LDS, visible to all threads on entry).  Ends with a barrier: L.et, g and gm are visible on return.
+__device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, const FxLds& L, const float* rs, const float* __restrict__ as,
+                                         const float* __restrict__ ras, const float* x, const float* ym, double* g, double* gm) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m, n_mov = A.n_mov;
+  const FxPatch patch = {L.mov, n_mov, ym};
+  score_evaluate<true>(A, rs, L.tile, L.tflag, x, L.rad, L.lflag, g, L.we, patch);
+  // the ligand restraint, as mz_evaluate of ddp_minimize_loop.h
+  const double krest = 2.0 * A.restraint / (double)n;
+  double er_w = 0.0;
+  for (int i = wave; i < n; i += DDP_FX_WAVES) {
+    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
+    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
+    er_w += ax * ax + ay * ay + az * az;
+    if (lane == 0) { g[3 * i] = g[3 * i] + krest * ax; g[3 * i + 1] = g[3 * i + 1] + krest * ay; g[3 * i + 2] = g[3 * i + 2] + krest * az; }
+  }
+  if (lane == 0) L.wr[wave] = er_w;
+  fx_second_pass(A, L, rs, x, ym, gm);
   // the side-chain restraint
   const double krs = n_mov > 0 ? 2.0 * A.restraint_sc / (double)n_mov : 0.0;
   double er2_w = 0.0;
@@ -224,22 +252,13 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
     er2_w += ax * ax + ay * ay + az * az;
     if (lane == 0) { gm[3 * r] = gm[3 * r] + krs * ax; gm[3 * r + 1] = gm[3 * r + 1] + krs * ay; gm[3 * r + 2] = gm[3 * r + 2] + krs * az; }
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double c = wave_sum(st.t[k]) + 0.5 * wave_sum(mv.t[k]);
-    if (lane == 0) L.we2[wave][k] = c;
-  }
   if (lane == 0) L.wr2[wave] = er2_w;
   __syncthreads();
   if (tid == 0) {
-    double t[8], inter, intra, er = L.wr[0], er2 = L.wr2[0], c[4];
+    double t[8], inter, intra, er = L.wr[0], er2 = L.wr2[0];
     score_totals(A.form, L.we, t, inter, intra);
     for (int w = 1; w < DDP_FX_WAVES; ++w) { er += L.wr[w]; er2 += L.wr2[w]; }
-    for (int k = 0; k < 4; ++k) {
-      c[k] = L.we2[0][k];
-      for (int w = 1; w < DDP_FX_WAVES; ++w) c[k] += L.we2[w][k];
-    }
-    const double sc = F.w_gauss * c[0] + F.w_repulsion * c[1] + F.w_hydrophobic * c[2] + F.w_hbond * c[3];
+    const double sc = fx_sc_total(A.form, L.we2);
     const double rest = A.restraint * (er / (double)n);
     const double rest2 = n_mov > 0 ? A.restraint_sc * (er2 / (double)n_mov) : 0.0;
     L.et[0] = inter; L.et[1] = intra; L.et[2] = sc; L.et[3] = rest; L.et[4] = rest2;
@@ -249,15 +268,17 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
 }
 
 // the range of sc_sub that bond j turns, clamped to the table
-__device__ __forceinline__ void fx_range(const ddp_minimize_flex_args_t& A, int j, int& m0, int& m1) {
+template <class Args>
+__device__ __forceinline__ void fx_range(const Args& A, int j, int& m0, int& m1) {
   m0 = min(max(A.sc_map[2 * j], 0), A.n_sub);
   m1 = min(max(A.sc_map[2 * j + 1], 0), A.n_sub);
 }
 
 // L.scstep[j] = step * the inertia-scaled direction of side-chain bond j at the state ym with the gradient gm, fp64, rounded to fp32.
 // Wave w owns the bonds w, w + 4, ..., its lanes stride over the bond's subcomponent.  Visible after the caller's next barrier.
-__device__ __forceinline__ void fx_sc_direction(const ddp_minimize_flex_args_t& A, const FxLds& L, const float* rs, const float* ym,
-                                                const double* gm, double step) {
+// Args as fx_load_tables.
+template <class Args>
+__device__ __forceinline__ void fx_sc_direction(const Args& A, const FxLds& L, const float* rs, const float* ym, const double* gm, double step) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = A.m, n_mov = A.n_mov;
   for (int j = wave; j < A.n_sc; j += DDP_FX_WAVES) {
     const int u = A.sc_edge_idx[2 * j], v = A.sc_edge_idx[2 * j + 1];

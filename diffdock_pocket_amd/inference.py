@@ -573,13 +573,15 @@ def _gather_rows(dist, t: torch.Tensor, sizes: Sequence[int]) -> torch.Tensor:
 
 # ---------------------------------------------------------------------------------------------- command line
 def _guidance_fields(a) -> Dict:
-    """The --clash_guidance* and --score_guidance* flags as SamplerConfig fields (clash first, five each)."""
+    """The --clash_guidance* and --score_guidance* flags as SamplerConfig fields (clash first, five each, then the two of the
+    side-chain part of score guidance)."""
     return dict(clash_guidance_weight=a.clash_guidance, clash_guidance_t_max=a.clash_guidance_t_max,
                 clash_guidance_max_tr=a.clash_guidance_max_tr, clash_guidance_max_rot=a.clash_guidance_max_rot,
                 clash_guidance_max_tor=a.clash_guidance_max_tor,
                 score_guidance_weight=a.score_guidance, score_guidance_t_max=a.score_guidance_t_max,
                 score_guidance_max_tr=a.score_guidance_max_tr, score_guidance_max_rot=a.score_guidance_max_rot,
-                score_guidance_max_tor=a.score_guidance_max_tor)
+                score_guidance_max_tor=a.score_guidance_max_tor, score_guidance_sidechains=a.score_guidance_sidechains,
+                score_guidance_max_sc=a.score_guidance_max_sc)
 
 
 def _parser():
@@ -632,6 +634,11 @@ def _parser():
     p.add_argument("--score_guidance_max_tr", type=float, default=1.0, help="cap of the score-guidance translation per step (Angstrom)")
     p.add_argument("--score_guidance_max_rot", type=float, default=0.5, help="cap of the score-guidance rotation per step (rad)")
     p.add_argument("--score_guidance_max_tor", type=float, default=0.5, help="cap of the score-guidance torsion step per bond (rad)")
+    p.add_argument("--score_guidance_sidechains", action="store_true",
+                   help="with --score_guidance in a flexible run: guide the side-chain updates too, down the joint energy inter + intra + "
+                        "sc of the joint minimiser with respect to the chi angles (score_guidance.py; untuned, no backbone motion, no "
+                        "rotamer library); a no-op on a rigid run")
+    p.add_argument("--score_guidance_max_sc", type=float, default=0.5, help="cap of the score-guidance side-chain step per bond (rad)")
     p.add_argument("--cluster_rmsd", type=float, default=None,
                    help="group the ranked poses into binding modes at this symmetry-corrected RMSD cutoff and write modes.csv (default: off)")
     p.add_argument("--resolve_clashes", action="store_true", default=False,
@@ -780,7 +787,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         from .guidance import check_config
         fields = list(_guidance_fields(a).values())
         check_config(*fields[:5])
-        check_config(*fields[5:], prefix="score_guidance")
+        check_config(*fields[5:10], prefix="score_guidance")
+        if not a.score_guidance_max_sc >= 0.0:
+            raise ValueError(f"score_guidance_max_sc must not be negative or NaN, got {a.score_guidance_max_sc!r}")
     except ValueError as e:
         msg = str(e)
         for kind in ("clash", "score"):

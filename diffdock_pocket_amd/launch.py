@@ -817,6 +817,13 @@ def score_guidance(a: L.ScoreGuidanceArgs, st=None):
     L.check(L.load().ddp_score_guidance(C.byref(a), stream() if st is None else st), "ddp_score_guidance")
 
 
+def score_guidance_flex(a: L.ScoreGuidanceFlexArgs, st=None):
+    """ddp_score_guidance_flex: the score-guidance increments of a.pos and of the side chains of a.rec added to a.upd and a.upd_sc, on
+    stream `st` (None: the current stream of the current device).  score_guidance.ScoreGuidanceFlexWorkspace builds the struct and
+    checks the tensors."""
+    L.check(L.load().ddp_score_guidance_flex(C.byref(a), stream() if st is None else st), "ddp_score_guidance_flex")
+
+
 # ------------------------------------------------------------------------------------------------ physics score (csrc/ddp_score.hip)
 def pose_score(pos, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, tor_divisor=1.0, self_pairs=None, energy=None, grad=None,
                with_grad=False):

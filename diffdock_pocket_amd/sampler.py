@@ -219,6 +219,11 @@ class SamplerConfig:
     score_guidance_max_rot: float = 0.5
     score_guidance_max_tor: float = 0.5
     score_guidance_config: Optional["ScoreConfig"] = None     # scoring.ScoreConfig
+    # the same term for the side-chain updates of a flexible run (score_guidance.py, steps S1 - S4): the capped descent direction of the
+    # joint energy inter + intra + sc of minimize_flex.py with respect to the chi angles, times the same w_t, with a cap of its own
+    # (radians, untuned).  The ligand increments stay what they are.  A no-op on a rigid run or with score_guidance_weight = 0.
+    score_guidance_sidechains: bool = False
+    score_guidance_max_sc: float = 0.5
 
     def __post_init__(self):
         from .guidance import check_config
@@ -228,6 +233,8 @@ class SamplerConfig:
                      self.score_guidance_max_tor, prefix="score_guidance")
         if self.score_guidance_config is not None:
             self.score_guidance_config.check()
+        if not float(self.score_guidance_max_sc) >= 0.0:
+            raise ValueError(f"score_guidance_max_sc must not be negative or NaN, got {self.score_guidance_max_sc!r}")
 
 
 class Sampler:
@@ -281,6 +288,7 @@ class Sampler:
         if self.guidance:
             self._init_guidance(g)
         self.score_guidance = cfg.score_guidance_weight > 0
+        self.score_guidance_sc = False
         if self.score_guidance:
             self._init_score_guidance(g)
 
@@ -308,7 +316,14 @@ class Sampler:
         cfg = self.cfg
         self.sguid_caps = (cfg.score_guidance_max_tr, cfg.score_guidance_max_rot, cfg.score_guidance_max_tor)
         self.sguid_tables = score_guidance.build_tables(g, torsions=not cfg.no_torsion, config=cfg.score_guidance_config)
-        if self.on_hip:
+        # the side chains too (score_guidance_sidechains, a flexible run): the tables of minimize_flex.py, above the limits of
+        # ddp_score_guidance_flex this raises; on a HIP device that entry's workspace takes the place of ddp_score_guidance's
+        self.sguid_sc_tables = score_guidance.build_sidechain_tables(g, self.sguid_tables) if cfg.score_guidance_sidechains and self.has_flex else None
+        self.score_guidance_sc = self.sguid_sc_tables is not None
+        if self.on_hip and self.score_guidance_sc:
+            self.sguid_ws = score_guidance.ScoreGuidanceFlexWorkspace(self.sguid_tables, self.sguid_sc_tables, self.device, self.sguid_caps,
+                                                                      cfg.score_guidance_max_sc)
+        elif self.on_hip:
             self.sguid_ws = score_guidance.ScoreGuidanceWorkspace(self.sguid_tables, self.device, self.sguid_caps)
 
     def _score_guidance_weight(self, t: float) -> float:
@@ -552,7 +567,10 @@ class Sampler:
         if self.guidance:  # after SVGD (svgd_only does not erase it), against the receptor before this step's side-chain update
             self.guid_ws.launch(self.lig_pos, self.atom_pos if self.has_flex else None,
                                 (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[5:6])
-        if self.score_guidance:  # after clash guidance, on the same poses against the same receptor
+        if self.score_guidance and self.score_guidance_sc:  # one launch for the ligand and the side-chain increments
+            self.sguid_ws.launch(self.lig_pos, self.atom_pos, (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None),
+                                 self.params[6:7], self.upd["sc"])
+        elif self.score_guidance:  # after clash guidance, on the same poses against the same receptor
             self.sguid_ws.launch(self.lig_pos, self.atom_pos if self.has_flex else None,
                                  (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[6:7])
         if self.has_flex:
@@ -752,11 +770,14 @@ class Sampler:
             guid = guidance.increments_torch(self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else self.guid_tables.rec,
                                              self.guid_tables, self._guidance_weight(t), cfg.clash_guidance_max_tr,
                                              cfg.clash_guidance_max_rot, cfg.clash_guidance_max_tor)
-        sguid = None
+        sguid = sguid_sc = None
         if self.score_guidance:  # the same poses and receptor; added after the clash increments
             from . import score_guidance
             sguid = score_guidance.increments_torch(self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else self.sguid_tables.rec,
                                                     self.sguid_tables, self._score_guidance_weight(t), self.sguid_caps)
+            if self.score_guidance_sc:  # the side chains' increments, on the same pose and receptor
+                sguid_sc = score_guidance.increments_sc_torch(self.lig_pos.cpu(), self.atom_pos.cpu(), self.sguid_tables, self.sguid_sc_tables,
+                                                              self._score_guidance_weight(t), cfg.score_guidance_max_sc)
 
         def perturb(score, g, sigma, lo, hi, k, zz):
             if cfg.ode:
@@ -780,6 +801,8 @@ class Sampler:
             sc_g = sc_s * math.sqrt(2 * math.log(sg.sidechain_tor_sigma_max / sg.sidechain_tor_sigma_min))
             sc_p = perturb(sc_score.reshape(self.n, self.S), sc_g, sc_s, sg.sidechain_tor_sigma_min,
                            sg.sidechain_tor_sigma_max, 3, z_sc)
+            if sguid_sc is not None:
+                sc_p = sc_p + sguid_sc.to(dev)
             if self.atom_pos.is_cuda:
                 self.atom_pos = apply_sidechain_torsions_hip(self.atom_pos, self.sc_edge_i32, self.sc_sub_i32, self.sc_map_i32, sc_p)
             else:

@@ -19,10 +19,30 @@ against, and let g = dE/dx be the fp64 gradient of E(x) = inter(x, rec) + intra(
     (radians); the defaults 1.0 / 0.5 / 0.5 are untuned choices, fitted to nothing.
  4. Update.  upd_X[s] += (float)(f_s * (double)d_X) for X in tr, rot, tor - added AFTER the SDE / ODE update, after SVGD and after
     clash guidance when that is on too (both may be on, each with its own caps; svgd_only erases neither).  Side-chain updates get no
-    guidance.  w_t == 0 writes nothing, not even + 0.
+    guidance unless score_guidance_sidechains is set (below).  w_t == 0 writes nothing, not even + 0.
  5. Receptor.  The graph's typed atom nodes, typed as PoseScorer(graph, receptor="graph") types them.  Rigid runs: shared by all
     samples.  Flexible runs: each sample's own current atom_pos, before this step's side-chain update.  The ligand is typed by
     scoring.type_ligand.  Untyped atoms take part in nothing, as in the score.
+
+Side chains (SamplerConfig.score_guidance_sidechains, off by default; a flexible run only, otherwise a no-op).  The ligand part above
+is unchanged - the ligand increments of a flexible run are exactly what they are without the flag.  For sample s of a flexible run at
+a step with w_t > 0 (the same w_t, the same params[6]), with x as above and y the sample's current atom_pos, before this step's
+side-chain update:
+
+ S1. Gradient.  g_y = dE/dy_a over the moving atoms Mv of E(x, y) = inter(x, y) + intra(x) + sc(y): the joint energy of
+     minimize_flex.py at both restraints 0, with the tables of minimize_flex.sidechain_tables(graph) (mov, edge_idx, sub, mapping,
+     sc_pairs), the receptor typed as PoseScorer(graph, receptor="graph") types it and the same ScoreConfig as the ligand term
+     (score_guidance_config).
+ S2. Direction.  d_sc = w_t * minimize_flex.direction_sc_torch(y, g_y, ...) in fp64, rounded to fp32.  The sign convention is the
+     minimiser's: the angles are applied through the sampler's own side-chain map (apply_sidechain_torsions / ddp_sidechain_update).
+ S3. Cap factor.  f_sc = min(1, max_sc / max_j |d_sc[j]|), in fp64 from the fp32 values; a zero maximum gives no constraint.  max_sc
+     is score_guidance_max_sc (radians), default 0.5, untuned like the others.  It is a factor of its own, separate from f_s.
+ S4. Update.  upd_sc[s, j] += (float)(f_sc * (double)d_sc[j]) - added after the SDE / ODE update and before the side-chain update.
+     w_t == 0 writes nothing.
+
+What the side-chain part is not: there is no backbone motion and no rotamer library (a local nudge of the chi angles from where the
+sampler has them); the constants are untuned; the score is not validated against smina or Vina; a lower E is not a better pose.  No
+restraint term acts inside the step, clash guidance does not reach the side chains, and the receptor is the graph's pocket atoms.
 
 What the term is not: the score is not validated against smina or Vina; the weight, the schedule and the caps are untuned and the
 term is untested on real checkpoints; its torsion component is the heuristic of descent.py (ddp_pose_update re-aligns the conformer
@@ -32,7 +52,9 @@ pose.
 
 Two forms of the same arithmetic: `increments_torch`, fp64 PyTorch on host tensors (the CPU `Sampler.step`), and
 `ScoreGuidanceWorkspace`, one fused launch of csrc/ddp_score_guidance.hip per step that reads w_t from device memory (the captured
-step needs no re-capture when t crosses t_max)."""
+step needs no re-capture when t crosses t_max).  The side-chain part likewise: `increments_sc_torch` and
+`ScoreGuidanceFlexWorkspace`, one launch of csrc/ddp_score_guidance_flex.hip that REPLACES the ddp_score_guidance launch of the step
+and writes the ligand increments (the same bits) and the side-chain increments."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -102,6 +124,48 @@ def increments_torch(x, rec, tables: ScoreGuidanceTables, w_t: float, caps):
     return tuple((f[:, None] * v.double()).float() for v in d)
 
 
+# the limits of ddp_score_guidance_flex (include/ddp_hip.h: DDP_SCORE_GUIDANCE_FLEX_MAX_ATOMS, _MAX_TORSIONS, _MAX_MOVING, _MAX_BONDS)
+FLEX_MAX_ATOMS, FLEX_MAX_TORSIONS, FLEX_MAX_MOVING, FLEX_MAX_BONDS = 512, 1024, 256, 256
+
+
+def build_sidechain_tables(graph, tables: ScoreGuidanceTables):
+    """The side-chain tables of the term for a complex graph with flexResidues: minimize_flex.sidechain_tables (checked on the host by
+    check_sidechain_tables), None for a graph without them.  tables: the ligand term's, of the same graph.  Raises above the limits of
+    ddp_score_guidance_flex, whatever device the sampler runs on."""
+    from .minimize_flex import sidechain_tables
+    sc = sidechain_tables(graph)
+    if sc is None:
+        return None
+    T = int(tables.bonds.shape[0])
+    if tables.n > FLEX_MAX_ATOMS or T > FLEX_MAX_TORSIONS or sc.n_mov > FLEX_MAX_MOVING or sc.n_sc > FLEX_MAX_BONDS:
+        raise ValueError(f"score guidance of side chains: {tables.n} ligand atoms, {T} rotatable bonds, {sc.n_mov} moving atoms and "
+                         f"{sc.n_sc} side-chain bonds exceed the limits of ddp_score_guidance_flex ({FLEX_MAX_ATOMS} atoms, "
+                         f"{FLEX_MAX_TORSIONS} bonds, {FLEX_MAX_MOVING} moving atoms, {FLEX_MAX_BONDS} side-chain bonds)")
+    return sc
+
+
+def cap_factor_sc(d_sc, max_sc):
+    """f_sc [S] fp64 of step S3 from the fp32 direction d_sc [S, n_sc]."""
+    f = torch.ones(d_sc.shape[0], dtype=torch.float64)
+    if d_sc.shape[1] == 0:
+        return f
+    mx = d_sc.double().abs().max(-1)[0]
+    return torch.where(mx > 0, torch.minimum(f, float(max_sc) / mx.clamp(min=1e-300)), f)
+
+
+def increments_sc_torch(x, y, tables: ScoreGuidanceTables, sc_tables, w_t: float, max_sc: float):
+    """inc_sc [S, n_sc] fp32: the increments of step S4 for host poses x [S, n, 3] fp32 and each sample's own receptor atoms y
+    [S, m, 3] fp32; sc_tables: a minimize_flex.SidechainTables; None when w_t is not above 0 (nothing is to be added)."""
+    from .minimize_flex import direction_sc_torch, energy_flex_torch
+    if not w_t > 0:
+        return None
+    x, y, sc = x.float(), y.float(), sc_tables
+    _, _, gy = energy_flex_torch(x, y, x, y, tables.lig_radii, tables.lig_flags, tables.rec_radii, tables.rec_flags, tables.self_pairs,
+                                 sc.mov, sc.pairs, tables.config, 0.0, 0.0)
+    d = (w_t * direction_sc_torch(y, gy, sc.mov, sc.edge_idx, sc.sub, sc.mapping)).float()
+    return (cap_factor_sc(d, max_sc)[:, None] * d.double()).float()
+
+
 class ScoreGuidanceWorkspace:
     """Device side: the tables uploaded once and the argument struct of ddp_score_guidance; `launch` enqueues the one launch on the
     current stream (no host work besides it: capturable)."""
@@ -148,3 +212,53 @@ class ScoreGuidanceWorkspace:
         a.grad = grad.data_ptr() if grad is not None else None
         LA.score_guidance(a, torch._C._cuda_getCurrentRawStream(lig_pos.device.index))
 
+
+
+class ScoreGuidanceFlexWorkspace(ScoreGuidanceWorkspace):
+    """Device side of the term with the side chains guided: the ligand tables of ScoreGuidanceWorkspace, the side-chain tables
+    (launch.flex_tables: checked on the host, uploaded once) and the argument struct of ddp_score_guidance_flex; `launch` enqueues the
+    one launch on the current stream (no host work besides it: capturable)."""
+
+    def __init__(self, tables: ScoreGuidanceTables, sc_tables, device, caps=(1.0, 0.5, 0.5), max_sc: float = 0.5):
+        from . import _lib as L
+        from . import launch as LA
+        super().__init__(tables, device, caps)
+        self.sc_tables = sc_tables
+        self.n_mov, self.n_sc, self.n_sub = sc_tables.n_mov, sc_tables.n_sc, int(sc_tables.sub.shape[0])
+        if self.n > FLEX_MAX_ATOMS or self.T > FLEX_MAX_TORSIONS or self.n_mov > FLEX_MAX_MOVING or self.n_sc > FLEX_MAX_BONDS:
+            raise ValueError(f"ScoreGuidanceFlexWorkspace: {self.n} ligand atoms, {self.T} rotatable bonds, {self.n_mov} moving atoms, "
+                             f"{self.n_sc} side-chain bonds exceed the limits of ddp_score_guidance_flex")
+        self._sc_dev = LA.flex_tables(sc_tables, self.m, device)
+        b, d = self.args, self._sc_dev
+        a = self.flex_args = L.ScoreGuidanceFlexArgs(n=self.n, m=self.m, n_tor=self.T, form=b.form, max_tr=b.max_tr, max_rot=b.max_rot,
+                                                     max_tor=b.max_tor, n_mov=self.n_mov, n_sc=self.n_sc, n_sub=self.n_sub,
+                                                     max_sc=float(max_sc))
+        for k in ("lig_radii", "lig_flags", "rec_radii", "rec_flags", "self_pairs", "bonds", "mask_rotate"):
+            setattr(a, k, getattr(b, k))
+        a.mov, a.sc_edge_idx, a.sc_sub = (d[k].data_ptr() or None for k in ("mov", "edge_idx", "sub"))
+        a.sc_map, a.sc_pairs = d["mapping"].data_ptr() or None, d["pairs"].data_ptr() or None
+
+    def launch(self, lig_pos, atom_pos, upd, weight, upd_sc, energy=None, grad_mov=None):
+        """lig_pos, upd, weight as ScoreGuidanceWorkspace.launch; atom_pos [S, m, 3]: each sample's own atom positions (only read);
+        upd_sc [S, n_sc] fp32, updated in place (None with n_sc = 0); energy [S, 3] = (inter, intra, sc), grad_mov [S, n_mov, 3] fp64:
+        optional outputs.  All contiguous tensors on the workspace's device."""
+        from . import launch as LA
+        S = lig_pos.shape[0]
+        want = [(lig_pos, torch.float32, (S, self.n, 3), "lig_pos"), (upd[0], torch.float32, (S, 3), "upd tr"),
+                (upd[1], torch.float32, (S, 3), "upd rot"), (atom_pos, torch.float32, (S, self.m, 3), "atom_pos"),
+                (energy, torch.float64, (S, 3), "energy"), (grad_mov, torch.float64, (S, self.n_mov, 3), "grad_mov")]
+        if self.T:
+            want.append((upd[2], torch.float32, (S, self.T), "upd tor"))
+        if self.n_sc:
+            want.append((upd_sc, torch.float32, (S, self.n_sc), "upd sc"))
+        LA.check_tensors("ScoreGuidanceFlexWorkspace.launch", self.device, want, ("energy", "grad_mov"), error=ValueError)
+        if weight.dtype != torch.float32 or weight.device != self.device or weight.numel() < 1 or not weight.is_contiguous():
+            raise ValueError("ScoreGuidanceFlexWorkspace.launch: weight = one fp32 value in device memory")
+        a = self.flex_args
+        a.n_samples, a.pos, a.weight = S, lig_pos.data_ptr(), weight.data_ptr()
+        a.rec, a.rec_stride = atom_pos.data_ptr() or None, 3 * self.m
+        a.upd[0], a.upd[1], a.upd[2] = upd[0].data_ptr(), upd[1].data_ptr(), (upd[2].data_ptr() if self.T else None)
+        a.upd_sc = upd_sc.data_ptr() if self.n_sc else None
+        a.energy = energy.data_ptr() if energy is not None else None
+        a.grad_mov = grad_mov.data_ptr() if grad_mov is not None else None
+        LA.score_guidance_flex(a, torch._C._cuda_getCurrentRawStream(lig_pos.device.index))

@@ -1276,6 +1276,64 @@ typedef struct {
 } ddp_score_guidance_args_t;
 int ddp_score_guidance(const ddp_score_guidance_args_t* args, void* stream);
 
+/* ---- the same term with the flexible side chains guided too (csrc/ddp_score_guidance_flex.hip; host side
+ * diffdock_pocket_amd/score_guidance.py, which states the definition, and sampler.py with score_guidance_sidechains).  In a flexible
+ * run it REPLACES the ddp_score_guidance launch of the step and does both jobs in one launch, one 256-thread workgroup per sample.
+ * The ligand fields are those of ddp_score_guidance_args_t and the ligand increments (upd[0 .. 2]) are bit for bit what
+ * ddp_score_guidance writes on the same inputs.  The receptor is one per sample, y = rec + s rec_stride (rec_stride >= 3 m; 0 with
+ * m > 0 is DDP_EINVAL), and is only read.  The side-chain tables mov, sc_edge_idx, sc_sub, sc_map and sc_pairs are those of
+ * ddp_minimize_flex_args_t.  With E(x, y) = inter(x, y) + intra(x) + sc(y), the joint energy of ddp_pose_minimize_flex at both
+ * restraints 0, and g_y = dE/dy_a over the moving atoms (the second pass of that entry's evaluation, shared with it through
+ * ddp_minimize_flex_loop.h: the gather over the ligand in LDS, then sc_pairs tile by tile; no atomics):
+ *   d_sc[j] = (float)(w * (-sum g_i . a_i / sum |a_i|^2)) over the subcomponent of bond j, the direction of ddp_pose_minimize_flex for
+ *             step = w = *weight (the same device value as the ligand part; unless w > 0 the workgroups return before any store);
+ *   f_sc    = min(1, max_sc / max_j |d_sc[j]|) in fp64 from those fp32 values (a zero maximum: no constraint) - a factor of its own,
+ *             separate from the ligand's f_s;
+ *   upd_sc[s][j] += (float)(f_sc * (double)d_sc[j]), every element by one thread.
+ * The angles are meant for ddp_sidechain_update, which the step runs next.  Optional outputs (NULL: not written): energy
+ * [n_samples][3] = inter, intra, sc and grad_mov [n_samples][n_mov][3] = g_y, fp64; sc and grad_mov are bit for bit those of
+ * ddp_pose_minimize_flex at iterations = 0, restraints 0, inter and intra those of ddp_score_guidance.  Every sum has a fixed order: two
+ * launches give the same bits; a NaN in x or in a moving atom poisons its own sample only.  No data-dependent control flow around a
+ * barrier; an entry of mov, sc_edge_idx or sc_sub outside [0, m) is skipped without a read, as in ddp_pose_minimize_flex.
+ * LDS: the 18496 fixed bytes of ddp_pose_minimize_flex + 41 n + 45 n_mov + 4 n_sc + 4 n_tor + 32 (ONE copy of the state: the pose and
+ * the moving atoms, one fp64 gradient each, radii, flags, indices, the two directions): 56160 bytes at all four limits.
+ * n > DDP_SCORE_GUIDANCE_FLEX_MAX_ATOMS, n_tor > DDP_SCORE_GUIDANCE_FLEX_MAX_TORSIONS, n_mov > DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING or
+ * n_sc > DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS: DDP_ELIMIT.  A NULL struct or required pointer (rec, rec_radii, rec_flags with m > 0; bonds,
+ * mask_rotate, upd[2] with n_tor > 0; mov, sc_pairs with n_mov > 0; sc_edge_idx, sc_map, upd_sc with n_sc > 0; sc_sub with n_sub > 0), a
+ * bad shape or negative count, a negative or NaN cap, the constant checks of ddp_score_form_t: DDP_EINVAL.  Nothing is launched then.
+ * n_samples = 0: no-op. */
+#define DDP_SCORE_GUIDANCE_FLEX_MAX_ATOMS DDP_MINIMIZE_MAX_ATOMS
+#define DDP_SCORE_GUIDANCE_FLEX_MAX_TORSIONS DDP_GUIDANCE_MAX_TORSIONS
+#define DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING DDP_MINIMIZE_FLEX_MAX_MOVING
+#define DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS DDP_MINIMIZE_FLEX_MAX_BONDS
+typedef struct {
+  int32_t n_samples, n, m, rec_stride, n_tor;
+  const float* pos;             /* [n_samples][n][3] */
+  const float* lig_radii;       /* [n] */
+  const uint8_t* lig_flags;     /* [n] */
+  const float* rec;             /* sample s: rec + s rec_stride, [m][3]; only read */
+  const float* rec_radii;       /* [m] */
+  const uint8_t* rec_flags;     /* [m] */
+  const uint8_t* self_pairs;    /* [n][n] or NULL */
+  const int32_t* bonds;         /* [n_tor][2] */
+  const uint8_t* mask_rotate;   /* [n_tor][n] */
+  ddp_score_form_t form;        /* the constants of the score form */
+  const float* weight;          /* one value, device memory */
+  double max_tr, max_rot, max_tor;
+  float* upd[3];                /* [n_samples][3], [n_samples][3], [n_samples][n_tor] */
+  int32_t n_mov, n_sc, n_sub, reserved;
+  const int32_t* mov;           /* [n_mov], sorted, unique */
+  const int32_t* sc_edge_idx;   /* [n_sc][2] */
+  const int32_t* sc_sub;        /* [n_sub] */
+  const int32_t* sc_map;        /* [n_sc][2] */
+  const uint8_t* sc_pairs;      /* [n_mov][m] */
+  double max_sc;
+  float* upd_sc;                /* [n_samples][n_sc] */
+  double* energy;               /* [n_samples][3] or NULL */
+  double* grad_mov;             /* [n_samples][n_mov][3] or NULL */
+} ddp_score_guidance_flex_args_t;
+int ddp_score_guidance_flex(const ddp_score_guidance_flex_args_t* args, void* stream);
+
 int ddp_abi_version(void);
 const char* ddp_last_error(void);
 /* 16 hex digits of the SHA-256 over the sources (every csrc .hip file, the csrc headers, include/ddp_hip.h) the library was built from */
