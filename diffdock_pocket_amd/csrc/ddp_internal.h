@@ -2,6 +2,8 @@
 #ifndef DDP_INTERNAL_H
 #define DDP_INTERNAL_H
 #include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include "ddp_hip.h"
@@ -34,6 +36,47 @@ static inline int ddp_pose_check_atoms(const char* who, int n, int limit, const 
   return ddp_fail(DDP_ELIMIT, msg);
 }
 #define DDP_POSE_CHECK_ATOMS(who, n, LIMIT) ddp_pose_check_atoms(who, n, LIMIT, #LIMIT)
+
+// The side-chain tables of the _flex entries (ddp_pose_minimize_flex, ddp_pose_search_flex, ddp_score_guidance_flex), counts already
+// known not to be negative: the entry's limits on moving atoms and side-chain bonds and, where the entry has one (state_name not
+// NULL), on the per-atom LDS state are DDP_ELIMIT and the text names the limit's macro; a table that its count needs and that is NULL
+// is DDP_EINVAL.  (rec_anchor, upd_sc and the row state are the entries' own.)
+static inline int ddp_pose_check_sidechains(const char* who, int n_mov, int n_sc, int n_sub, const void* mov, const void* sc_pairs,
+                                            const void* sc_edge_idx, const void* sc_map, const void* sc_sub, int max_moving,
+                                            const char* moving_name, int max_bonds, const char* bonds_name, size_t state, size_t max_state,
+                                            const char* state_name) {
+  char msg[160];
+  if (n_mov > max_moving) snprintf(msg, sizeof msg, "%s: more than %s moving atoms", who, moving_name);
+  else if (n_sc > max_bonds) snprintf(msg, sizeof msg, "%s: more than %s side-chain bonds", who, bonds_name);
+  else if (state_name && state > max_state) snprintf(msg, sizeof msg, "%s: 89 n + 81 n_mov + 4 n_sc exceeds %s", who, state_name);
+  else if ((n_mov > 0 && (!mov || !sc_pairs)) || (n_sc > 0 && (!sc_edge_idx || !sc_map)) || (n_sub > 0 && !sc_sub)) {
+    snprintf(msg, sizeof msg, "%s: null argument", who);
+    return ddp_fail(DDP_EINVAL, msg);
+  } else return 0;
+  return ddp_fail(DDP_ELIMIT, msg);
+}
+#define DDP_POSE_CHECK_SIDECHAINS(who, a, MOVING, BONDS, ...) \
+  ddp_pose_check_sidechains(who, (a)->n_mov, (a)->n_sc, (a)->n_sub, (a)->mov, (a)->sc_pairs, (a)->sc_edge_idx, (a)->sc_map, (a)->sc_sub, MOVING, #MOVING, BONDS, #BONDS, __VA_ARGS__)
+
+// The chain of the two search entries (a: ddp_search_args_t or ddp_search_flex_args_t), after the checks of the descent's pointers: the
+// row state, the random numbers and the records (state_ok: what the entry's state holds beyond the shared pointers), then the descent's
+// own scalars (descent_error: NULL, or what is wrong with them), then replicas, cycles, cycle0, temperature, step_init and the row count.
+template <class Args>
+static inline int ddp_pose_check_chain(const char* who, const Args* a, int n_samples, bool state_ok, const char* descent_error) {
+  const char* what = nullptr;
+  if (!a->perturb || !a->u || !a->cur_pos || !a->cur_e || !a->best_pos || !a->best_e || !a->best_cycle || !a->accepted || !a->trace || !a->flags ||
+      !state_ok)
+    what = "null perturb, u, state, trace or flags";
+  else if (descent_error) what = descent_error;
+  else if (a->replicas < 1 || a->cycles < 0 || a->cycle0 < 0) what = "replicas < 1, cycles or cycle0 < 0";
+  else if (!(a->temperature > 0.0) || !isfinite(a->temperature)) what = "temperature must be positive and finite";
+  else if (!(a->step_init > 0.0)) what = "step_init must be positive";
+  else if ((int64_t)n_samples * a->replicas > 0x7fffffff) what = "n_samples * replicas does not fit a launch";
+  if (!what) return 0;
+  char msg[128];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return ddp_fail(DDP_EINVAL, msg);
+}
 
 // After the launch: 0, or the launch's HIP error.
 static inline int ddp_launch_result(const char* who) {

@@ -4,20 +4,10 @@
 // evaluation, with a second molecule in the state.  One 256-thread workgroup per pose holds, for the whole call, what ddp_pose_minimize
 // holds for the ligand and, for the n_mov moving receptor atoms, the current and the trial coordinates, both gradients, radii, flags,
 // their receptor indices and the side-chain steps.  The LDS plan, the evaluation and the loop (fx_descend) live in
-// ddp_minimize_flex_loop.h, which ddp_search_flex.hip shares; this file is the kernel around them and the host entry.
-// One evaluation:
-//   1. score_evaluate of ddp_pose_descent.h for the ligand side.  Its tile-load hook (FxPatch) puts the moving atoms in from LDS as the
-//      receptor tile is loaded: a binary search of the atom's index in the sorted `mov` (at most 9 probes of LDS per loaded atom) is the
-//      slot lookup, so the trial receptor never goes through global memory.  The hook also marks a moving atom in bit 7 of its flag
-//      byte, which the pair arithmetic does not read.
-//   2. the ligand restraint of ddp_pose_minimize.
-//   3. the second pass: wave w owns the moving atoms w, w + 4, ...  Its lanes stride over the ligand atoms in LDS (the receptor-side
-//      gradient of inter, by gather), then over the receptor tile for the partners of sc_pairs (the energy and gradient of sc; a
-//      partner that moves itself counts half in the energy, it is met again from its own row), then lane 0 adds the side-chain
-//      restraint.  m <= one tile: the tile that step 1 loaded is still there and is used as it is.
-// Every sum has a fixed order (ddp_pose_descent.h): butterflies inside a wave, the waves in wave order, the tiles in increasing order.
-// No atomics.  No data-dependent control flow around a barrier: trip counts and the conditions that skip a barrier (an index outside
-// the receptor, m <= one tile) are kernel arguments or table entries, the same for all 256 threads.
+// ddp_minimize_flex_loop.h, which ddp_search_flex.hip shares; this file is the kernel around them and the host entry (fx_check of that
+// header holds the checks the two entries share).
+// The evaluation (its three passes, the fixed order of every sum, what keeps control flow uniform around the barriers) is described at
+// the head of that header.
 #include "ddp_minimize_flex_loop.h"
 
 __global__ __launch_bounds__(DDP_FX_THREADS) void ddp_pose_minimize_flex_kernel(const ddp_minimize_flex_args_t A) {
@@ -74,26 +64,16 @@ __global__ __launch_bounds__(DDP_FX_THREADS) void ddp_pose_minimize_flex_kernel(
 extern "C" int ddp_pose_minimize_flex(const ddp_minimize_flex_args_t* a, void* stream) {
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: null argument struct");
   if (a->n_samples == 0) return 0;
-  if (const int rc = ddp_pose_check_shape("ddp_pose_minimize_flex", a->n_samples, a->n, a->m, a->rec_stride,
-                                          a->n_tor >= 0 && a->n_mov >= 0 && a->n_sc >= 0 && a->n_sub >= 0, true))
-    return rc;
-  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_pose_minimize_flex", a->n, DDP_MINIMIZE_MAX_ATOMS)) return rc;
-  if (a->n_tor > DDP_MINIMIZE_MAX_TORSIONS) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: more than DDP_MINIMIZE_MAX_TORSIONS rotatable bonds");
-  if (a->n_mov > DDP_MINIMIZE_FLEX_MAX_MOVING) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: more than DDP_MINIMIZE_FLEX_MAX_MOVING moving atoms");
-  if (a->n_sc > DDP_MINIMIZE_FLEX_MAX_BONDS) return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: more than DDP_MINIMIZE_FLEX_MAX_BONDS side-chain bonds");
-  const size_t state = (size_t)89 * a->n + (size_t)81 * a->n_mov + (size_t)4 * a->n_sc;
-  if (state > DDP_MINIMIZE_FLEX_MAX_STATE_BYTES)
-    return ddp_fail(DDP_ELIMIT, "ddp_pose_minimize_flex: 89 n + 81 n_mov + 4 n_sc exceeds DDP_MINIMIZE_FLEX_MAX_STATE_BYTES");
+  if (const int rc = fx_check("ddp_pose_minimize_flex", a)) return rc;
   if (!a->pos || !a->anchor || !a->lig_radii || !a->lig_flags || !a->step || !a->accepted || !a->energy_in || !a->energy_out ||
       (a->m > 0 && (!a->rec || !a->rec_radii || !a->rec_flags)) || (a->n_tor > 0 && (!a->bonds || !a->mask_rotate)) ||
-      (a->n_mov > 0 && (!a->mov || !a->sc_pairs || !a->rec_anchor)) || (a->n_sc > 0 && (!a->sc_edge_idx || !a->sc_map)) ||
-      (a->n_sub > 0 && !a->sc_sub))
+      (a->n_mov > 0 && !a->rec_anchor))
     return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: null argument");
   if (a->iterations < 0 || !(a->restraint >= 0.0) || !(a->restraint_sc >= 0.0))
     return ddp_fail(DDP_EINVAL, "ddp_pose_minimize_flex: iterations or a restraint < 0");
   if (const int rc = score_check_constants(&a->form, "ddp_pose_minimize_flex")) return rc;
   // 18496 bytes fixed + 89 per ligand atom + 81 per moving atom + 4 per side-chain bond: at most 64 KiB
-  const size_t lds = DDP_FX_FIXED_BYTES + state;
-  hipLaunchKernelGGL(ddp_pose_minimize_flex_kernel, dim3(a->n_samples), dim3(DDP_FX_THREADS), lds, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(ddp_pose_minimize_flex_kernel, dim3(a->n_samples), dim3(DDP_FX_THREADS), fx_lds_bytes(a->n, a->n_mov, a->n_sc),
+                     (hipStream_t)stream, *a);
   return ddp_launch_result("ddp_pose_minimize_flex");
 }

@@ -11,7 +11,7 @@
 //      receptor tile is loaded: a binary search of the atom's index in the sorted `mov` (at most 9 probes of LDS per loaded atom) is the
 //      slot lookup, so the trial receptor never goes through global memory.  The hook also marks a moving atom in bit 7 of its flag
 //      byte, which the pair arithmetic does not read.
-//   2. the ligand restraint of ddp_pose_minimize.
+//   2. the ligand restraint of ddp_pose_minimize (descent_ligand_restraint of ddp_pose_descent.h).
 //   3. the second pass: wave w owns the moving atoms w, w + 4, ...  Its lanes stride over the ligand atoms in LDS (the receptor-side
 //      gradient of inter, by gather), then over the receptor tile for the partners of sc_pairs (the energy and gradient of sc; a
 //      partner that moves itself counts half in the energy, it is met again from its own row), then lane 0 adds the side-chain
@@ -71,6 +71,22 @@ struct FxLds {
 // the per-atom part of the plan, bounded by DDP_MINIMIZE_FLEX_MAX_STATE_BYTES, and the whole dynamic LDS block
 static inline size_t fx_state_bytes(int n, int n_mov, int n_sc) { return (size_t)89 * n + (size_t)81 * n_mov + (size_t)4 * n_sc; }
 static inline size_t fx_lds_bytes(int n, int n_mov, int n_sc) { return DDP_FX_FIXED_BYTES + fx_state_bytes(n, n_mov, n_sc); }
+
+// host: what ddp_pose_minimize_flex and ddp_pose_search_flex check alike before they look at their own pointers: the shape, the limits
+// of the plan (DDP_ELIMIT) and the side-chain tables
+static inline int fx_check(const char* who, const ddp_minimize_flex_args_t* a) {
+  if (const int rc = ddp_pose_check_shape(who, a->n_samples, a->n, a->m, a->rec_stride,
+                                          a->n_tor >= 0 && a->n_mov >= 0 && a->n_sc >= 0 && a->n_sub >= 0, true))
+    return rc;
+  if (const int rc = DDP_POSE_CHECK_ATOMS(who, a->n, DDP_MINIMIZE_MAX_ATOMS)) return rc;
+  if (a->n_tor > DDP_MINIMIZE_MAX_TORSIONS) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "%s: more than DDP_MINIMIZE_MAX_TORSIONS rotatable bonds", who);
+    return ddp_fail(DDP_ELIMIT, msg);
+  }
+  return DDP_POSE_CHECK_SIDECHAINS(who, a, DDP_MINIMIZE_FLEX_MAX_MOVING, DDP_MINIMIZE_FLEX_MAX_BONDS, fx_state_bytes(a->n, a->n_mov, a->n_sc),
+                                   DDP_MINIMIZE_FLEX_MAX_STATE_BYTES, "DDP_MINIMIZE_FLEX_MAX_STATE_BYTES");
+}
 
 __device__ __forceinline__ FxLds fx_carve(unsigned char* p, int n, int n_mov, int n_sc) {
   FxLds L;
@@ -230,16 +246,7 @@ __device__ __forceinline__ void fx_evaluate(const ddp_minimize_flex_args_t& A, c
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n, m = A.m, n_mov = A.n_mov;
   const FxPatch patch = {L.mov, n_mov, ym};
   score_evaluate<true>(A, rs, L.tile, L.tflag, x, L.rad, L.lflag, g, L.we, patch);
-  // the ligand restraint, as mz_evaluate of ddp_minimize_loop.h
-  const double krest = 2.0 * A.restraint / (double)n;
-  double er_w = 0.0;
-  for (int i = wave; i < n; i += DDP_FX_WAVES) {
-    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
-    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
-    er_w += ax * ax + ay * ay + az * az;
-    if (lane == 0) { g[3 * i] = g[3 * i] + krest * ax; g[3 * i + 1] = g[3 * i + 1] + krest * ay; g[3 * i + 2] = g[3 * i + 2] + krest * az; }
-  }
-  if (lane == 0) L.wr[wave] = er_w;
+  descent_ligand_restraint(A, x, as, g, L.wr);
   fx_second_pass(A, L, rs, x, ym, gm);
   // the side-chain restraint
   const double krs = n_mov > 0 ? 2.0 * A.restraint_sc / (double)n_mov : 0.0;

@@ -67,17 +67,9 @@ __device__ __forceinline__ MzLds mz_carve(unsigned char* p, int n) {
 template <class Args>
 __device__ __forceinline__ void mz_evaluate(const Args& A, const MzLds& L, const float* __restrict__ rs, const float* __restrict__ as,
                                             const float* x, double* g) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n;
+  const int tid = threadIdx.x, n = A.n;
   score_evaluate<true>(A, rs, L.tile, L.tflag, x, L.rad, L.lflag, g, L.we);
-  const double krest = 2.0 * A.restraint / (double)n;
-  double er_w = 0.0;
-  for (int i = wave; i < n; i += DDP_MZ_WAVES) {
-    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
-    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
-    er_w += ax * ax + ay * ay + az * az;
-    if (lane == 0) { g[3 * i] = g[3 * i] + krest * ax; g[3 * i + 1] = g[3 * i + 1] + krest * ay; g[3 * i + 2] = g[3 * i + 2] + krest * az; }
-  }
-  if (lane == 0) L.wr[wave] = er_w;
+  descent_ligand_restraint(A, x, as, g, L.wr);
   __syncthreads();
   if (tid == 0) {
     double t[8], inter, intra, er = L.wr[0];

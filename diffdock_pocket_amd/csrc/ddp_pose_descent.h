@@ -1,7 +1,9 @@
-// ddp_pose_descent.h - the pieces that the clash relief (ddp_refine.hip), the physics score (ddp_score.hip), the fused minimiser
-// (ddp_minimize.hip) and the joint minimiser (ddp_minimize_flex.hip) share, each defined once: the fixed-order reductions, the search
-// direction in pose space, the pose map on a pose held in LDS and the evaluation of the Vinardo-form score.  All of them run one
-// 256-thread workgroup per sample.  Every function takes plain pointers (global memory or LDS:
+// ddp_pose_descent.h - the pieces that the clash relief (ddp_refine.hip), the physics score (ddp_score.hip), the two minimisers
+// (ddp_minimize.hip, ddp_minimize_flex.hip), the two searches (ddp_search.hip, ddp_search_flex.hip) and the three guidance terms
+// (ddp_guidance.hip, ddp_score_guidance.hip, ddp_score_guidance_flex.hip) share, each defined once: the fixed-order reductions, the
+// search direction in pose space, the pose map on a pose held in LDS, the evaluation of the Vinardo-form score, the ligand restraint
+// pass.  All of them run one 256-thread workgroup per sample.  Every function
+// takes plain pointers (global memory or LDS:
 // the callers are inlined, so the compiler sees the address space) and the LDS carve stays the calling kernel's own.  Every sum has a
 // fixed order: a wave owns an output (a ligand atom, a rotatable bond), its 64 lanes stride over the summands, a butterfly of
 // __shfl_xor (every stage adds two equal-rank partial sums, addition is commutative: all lanes end with the same bits), and sums over
@@ -275,6 +277,23 @@ __device__ __forceinline__ void score_totals(const ddp_score_form_t& A, const do
   inter = A.w_gauss * t[0] + A.w_repulsion * t[1] + A.w_hydrophobic * t[2] + A.w_hbond * t[3];
   // every self pair is met from both ends and counts half each time: exact
   intra = A.w_gauss * (0.5 * t[4]) + A.w_repulsion * (0.5 * t[5]) + A.w_hydrophobic * (0.5 * t[6]) + A.w_hbond * (0.5 * t[7]);
+}
+
+// ---- the restraint of the ligand to its anchor `as` (global memory) in a pass of its own, after score_evaluate: wave w sums
+// |x_i - as_i|^2 over its atoms w, w + 4, ... in that order (all lanes hold the same value), lane 0 adds the term's gradient to g and
+// leaves the wave's sum in wr[wave]; both visible after the caller's next barrier.  A: n and restraint are read.
+template <class Args>
+__device__ __forceinline__ void descent_ligand_restraint(const Args& A, const float* x, const float* __restrict__ as, double* g, double* wr) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = A.n;
+  const double krest = 2.0 * A.restraint / (double)n;
+  double er_w = 0.0;
+  for (int i = wave; i < n; i += DDP_DESCENT_WAVES) {
+    const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
+    const double ax = xi - (double)as[3 * i], ay = yi - (double)as[3 * i + 1], az = zi - (double)as[3 * i + 2];
+    er_w += ax * ax + ay * ay + az * az;
+    if (lane == 0) { g[3 * i] = g[3 * i] + krest * ax; g[3 * i + 1] = g[3 * i + 1] + krest * ay; g[3 * i + 2] = g[3 * i + 2] + krest * az; }
+  }
+  if (lane == 0) wr[wave] = er_w;
 }
 
 // host: the constant checks of ddp_score_form_t, for every entry that takes a form; 0, or DDP_EINVAL with a text that names `who`

@@ -123,14 +123,11 @@ extern "C" int ddp_score_guidance_flex(const ddp_score_guidance_flex_args_t* a, 
   if (const int rc = DDP_POSE_CHECK_ATOMS(who, a->n, DDP_SCORE_GUIDANCE_FLEX_MAX_ATOMS)) return rc;
   if (a->n_tor > DDP_SCORE_GUIDANCE_FLEX_MAX_TORSIONS)
     return ddp_fail(DDP_ELIMIT, "ddp_score_guidance_flex: more than DDP_SCORE_GUIDANCE_FLEX_MAX_TORSIONS rotatable bonds");
-  if (a->n_mov > DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING)
-    return ddp_fail(DDP_ELIMIT, "ddp_score_guidance_flex: more than DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING moving atoms");
-  if (a->n_sc > DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS)
-    return ddp_fail(DDP_ELIMIT, "ddp_score_guidance_flex: more than DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS side-chain bonds");
+  if (const int rc = DDP_POSE_CHECK_SIDECHAINS(who, a, DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING, DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS, 0, 0, nullptr))
+    return rc;
   if (!a->pos || !a->lig_radii || !a->lig_flags || !a->weight || !a->upd[0] || !a->upd[1] ||
       (a->m > 0 && (!a->rec || !a->rec_radii || !a->rec_flags)) || (a->n_tor > 0 && (!a->bonds || !a->mask_rotate || !a->upd[2])) ||
-      (a->n_mov > 0 && (!a->mov || !a->sc_pairs)) || (a->n_sc > 0 && (!a->sc_edge_idx || !a->sc_map || !a->upd_sc)) ||
-      (a->n_sub > 0 && !a->sc_sub))
+      (a->n_sc > 0 && !a->upd_sc))
     return ddp_fail(DDP_EINVAL, "ddp_score_guidance_flex: null argument");
   if (const int rc = score_check_constants(&a->form, who)) return rc;
   if (!(a->max_tr >= 0.0) || !(a->max_rot >= 0.0) || !(a->max_tor >= 0.0) || !(a->max_sc >= 0.0))

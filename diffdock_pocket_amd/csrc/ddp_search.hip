@@ -117,27 +117,24 @@ __global__ __launch_bounds__(DDP_MZ_THREADS) void ddp_pose_search_select_kernel(
 }
 
 extern "C" int ddp_pose_search(const ddp_search_args_t* a, void* stream) {
+  const char* who = "ddp_pose_search";
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_pose_search: null argument struct");
   const ddp_minimize_args_t* m = &a->min;
   if (m->n_samples == 0) return 0;
-  if (const int rc = ddp_pose_check_shape("ddp_pose_search", m->n_samples, m->n, m->m, m->rec_stride, m->n_tor >= 0)) return rc;
-  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_pose_search", m->n, DDP_MINIMIZE_MAX_ATOMS)) return rc;
+  if (const int rc = ddp_pose_check_shape(who, m->n_samples, m->n, m->m, m->rec_stride, m->n_tor >= 0)) return rc;
+  if (const int rc = DDP_POSE_CHECK_ATOMS(who, m->n, DDP_MINIMIZE_MAX_ATOMS)) return rc;
   if (m->n_tor > DDP_MINIMIZE_MAX_TORSIONS) return ddp_fail(DDP_ELIMIT, "ddp_pose_search: more than DDP_MINIMIZE_MAX_TORSIONS rotatable bonds");
   if (!m->anchor || !m->lig_radii || !m->lig_flags || (m->m > 0 && (!m->rec || !m->rec_radii || !m->rec_flags)) ||
       (m->n_tor > 0 && (!m->bonds || !m->mask_rotate)))
     return ddp_fail(DDP_EINVAL, "ddp_pose_search: null argument");
-  if (!a->perturb || !a->u || !a->cur_pos || !a->cur_e || !a->best_pos || !a->best_e || !a->best_cycle || !a->accepted || !a->trace || !a->flags)
-    return ddp_fail(DDP_EINVAL, "ddp_pose_search: null perturb, u, state, trace or flags");
-  if (m->iterations < 0 || !(m->restraint >= 0.0)) return ddp_fail(DDP_EINVAL, "ddp_pose_search: iterations or restraint < 0");
-  if (a->replicas < 1 || a->cycles < 0 || a->cycle0 < 0) return ddp_fail(DDP_EINVAL, "ddp_pose_search: replicas < 1, cycles or cycle0 < 0");
-  if (!(a->temperature > 0.0) || !isfinite(a->temperature)) return ddp_fail(DDP_EINVAL, "ddp_pose_search: temperature must be positive and finite");
-  if (!(a->step_init > 0.0)) return ddp_fail(DDP_EINVAL, "ddp_pose_search: step_init must be positive");
-  if ((int64_t)m->n_samples * a->replicas > 0x7fffffff) return ddp_fail(DDP_EINVAL, "ddp_pose_search: n_samples * replicas does not fit a launch");
-  if (const int rc = score_check_constants(&m->form, "ddp_pose_search")) return rc;
+  if (const int rc = ddp_pose_check_chain(who, a, m->n_samples, true,
+                                          m->iterations < 0 || !(m->restraint >= 0.0) ? "iterations or restraint < 0" : nullptr))
+    return rc;
+  if (const int rc = score_check_constants(&m->form, who)) return rc;
   if (a->cycles == 0) return 0;
   hipLaunchKernelGGL(ddp_pose_search_kernel, dim3((unsigned)(m->n_samples * a->replicas)), dim3(DDP_MZ_THREADS), mz_lds_bytes(m->n),
                      (hipStream_t)stream, *a);
-  return ddp_launch_result("ddp_pose_search");
+  return ddp_launch_result(who);
 }
 
 extern "C" int ddp_pose_search_select(const ddp_search_select_args_t* a, void* stream) {

@@ -122,33 +122,17 @@ extern "C" int ddp_pose_search_flex(const ddp_search_flex_args_t* a, void* strea
   if (!a) return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: null argument struct");
   const ddp_minimize_flex_args_t* f = &a->flex;
   if (f->n_samples == 0) return 0;
-  if (const int rc = ddp_pose_check_shape(who, f->n_samples, f->n, f->m, f->rec_stride,
-                                          f->n_tor >= 0 && f->n_mov >= 0 && f->n_sc >= 0 && f->n_sub >= 0, true))
-    return rc;
-  if (const int rc = DDP_POSE_CHECK_ATOMS("ddp_pose_search_flex", f->n, DDP_MINIMIZE_MAX_ATOMS)) return rc;
-  if (f->n_tor > DDP_MINIMIZE_MAX_TORSIONS) return ddp_fail(DDP_ELIMIT, "ddp_pose_search_flex: more than DDP_MINIMIZE_MAX_TORSIONS rotatable bonds");
-  if (f->n_mov > DDP_MINIMIZE_FLEX_MAX_MOVING) return ddp_fail(DDP_ELIMIT, "ddp_pose_search_flex: more than DDP_MINIMIZE_FLEX_MAX_MOVING moving atoms");
-  if (f->n_sc > DDP_MINIMIZE_FLEX_MAX_BONDS) return ddp_fail(DDP_ELIMIT, "ddp_pose_search_flex: more than DDP_MINIMIZE_FLEX_MAX_BONDS side-chain bonds");
-  if (fx_state_bytes(f->n, f->n_mov, f->n_sc) > DDP_MINIMIZE_FLEX_MAX_STATE_BYTES)
-    return ddp_fail(DDP_ELIMIT, "ddp_pose_search_flex: 89 n + 81 n_mov + 4 n_sc exceeds DDP_MINIMIZE_FLEX_MAX_STATE_BYTES");
+  if (const int rc = fx_check(who, f)) return rc;
   if (!f->anchor || !f->lig_radii || !f->lig_flags || (f->m > 0 && (!f->rec || !f->rec_radii || !f->rec_flags)) ||
-      (f->n_tor > 0 && (!f->bonds || !f->mask_rotate)) || (f->n_mov > 0 && (!f->mov || !f->sc_pairs || !f->rec_anchor)) ||
-      (f->n_sc > 0 && (!f->sc_edge_idx || !f->sc_map)) || (f->n_sub > 0 && !f->sc_sub))
+      (f->n_tor > 0 && (!f->bonds || !f->mask_rotate)) || (f->n_mov > 0 && !f->rec_anchor))
     return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: null argument");
-  if (!a->perturb || !a->u || !a->cur_pos || !a->cur_e || !a->best_pos || !a->best_e || !a->best_cycle || !a->accepted || !a->trace || !a->flags ||
-      (f->n_mov > 0 && (!a->cur_mov || !a->best_mov)))
-    return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: null perturb, u, state, trace or flags");
-  if (f->iterations < 0 || !(f->restraint >= 0.0) || !(f->restraint_sc >= 0.0))
-    return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: iterations or a restraint < 0");
-  if (a->replicas < 1 || a->cycles < 0 || a->cycle0 < 0) return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: replicas < 1, cycles or cycle0 < 0");
-  if (!(a->temperature > 0.0) || !isfinite(a->temperature))
-    return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: temperature must be positive and finite");
-  if (!(a->step_init > 0.0)) return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: step_init must be positive");
-  if ((int64_t)f->n_samples * a->replicas > 0x7fffffff) return ddp_fail(DDP_EINVAL, "ddp_pose_search_flex: n_samples * replicas does not fit a launch");
+  if (const int rc = ddp_pose_check_chain(who, a, f->n_samples, f->n_mov == 0 || (a->cur_mov && a->best_mov),
+                                          f->iterations < 0 || !(f->restraint >= 0.0) || !(f->restraint_sc >= 0.0)
+                                              ? "iterations or a restraint < 0" : nullptr))
+    return rc;
   if (const int rc = score_check_constants(&f->form, who)) return rc;
   if (a->cycles == 0) return 0;
-  // the joint minimiser's plan: 18496 bytes fixed + 89 per ligand atom + 81 per moving atom + 4 per side-chain bond, at most 64 KiB
   hipLaunchKernelGGL(ddp_pose_search_flex_kernel, dim3((unsigned)(f->n_samples * a->replicas)), dim3(DDP_FX_THREADS),
                      fx_lds_bytes(f->n, f->n_mov, f->n_sc), (hipStream_t)stream, *a);
-  return ddp_launch_result("ddp_pose_search_flex");
+  return ddp_launch_result(who);
 }

@@ -906,6 +906,43 @@ def pose_minimize(pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, 
 
 
 # ------------------------------------------------------------------------------------------------ pose search (csrc/ddp_search.hip)
+def _search(who, cls, field, inner, width, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate,
+            replicas, cycle0, perturb, u, cur_pos, cur_e, best_pos, best_e, best_cycle, accepted, trace, flags, iterations, temperature,
+            step_init, restraint, grow, shrink, step_max, starts, side=None, moving=()):
+    """The call of both searches: the descent's struct `inner` under `field` of cls, the chain's tensors, energies [rows, width].  side
+    (the flexible search): as for _minimize, with it rec is per sample; moving: its (cur_mov, best_mov, starts_mov)."""
+    dev, S, n, m, rec_stride = pose_dims(who, anchor, rec, per_sample=side is not None)
+    T = 0 if bonds is None else int(bonds.shape[0])
+    replicas, cycle0, iterations = int(replicas), int(cycle0), int(iterations)
+    if replicas < 1 or cycle0 < 0 or iterations < 0:
+        raise L.DdpError(f"{who}: replicas < 1, cycle0 < 0 or iterations < 0")
+    if u is None or u.dim() != 2:
+        raise L.DdpError(f"{who}: u [cycles, rows]")
+    side_rows, optional, scalars = side(S, m) if side is not None else ([], (), {})
+    n_mov, n_sc = scalars.get("n_mov", 0), scalars.get("n_sc", 0)
+    Cn, rows = int(u.shape[0]), S * replicas
+    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+    ligand = [(anchor, f32, (S, n, 3), "anchor"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"), (rec, f32, None, "rec"),
+              (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (self_pairs, u8, (n, n), "self_pairs"),
+              (bonds, i32, (T, 2), "bonds"), (mask_rotate, u8, (T, n), "mask_rotate")] + side_rows
+    chain = [(perturb, f32, (Cn, rows, 6 + T + n_sc), "perturb"), (u, f64, (Cn, rows), "u"), (cur_pos, f32, (rows, n, 3), "cur_pos"),
+             (cur_e, f64, (rows, width), "cur_e"), (best_pos, f32, (rows, n, 3), "best_pos"), (best_e, f64, (rows, width), "best_e"),
+             (best_cycle, i32, (rows,), "best_cycle"), (accepted, i32, (rows,), "accepted"), (trace, f64, (Cn, rows, 2), "trace"),
+             (flags, u8, (Cn, rows), "flags"), (starts, f32, (Cn, rows, n, 3), "starts")]
+    if moving:
+        chain += [(moving[0], f32, (rows, n_mov, 3), "cur_mov"), (moving[1], f32, (rows, n_mov, 3), "best_mov"),
+                  (moving[2], f32, (Cn, rows, n_mov, 3), "starts_mov")]
+    a = cls(replicas=replicas, cycles=Cn, cycle0=cycle0, step_init=float(step_init), temperature=float(temperature))
+    optional = ("self_pairs",) + tuple(optional) + (("bonds", "mask_rotate") if T == 0 else ())
+    setattr(a, field, _pose_args(inner, who, dev, ligand, optional, config, n_samples=S, n=n, m=m, rec_stride=rec_stride, n_tor=T,
+                                 iterations=iterations, restraint=float(restraint), grow=float(grow), shrink=float(shrink),
+                                 step_max=float(step_max), **scalars))
+    check_tensors(who, dev, chain, ("starts", "starts_mov"))
+    for t, _, _, name in chain:
+        setattr(a, name, _p(t) or None)
+    L.check(getattr(L.load(), "ddp_" + who)(C.byref(a), stream()), "ddp_" + who)
+
+
 def pose_search(anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate, replicas, cycle0, perturb, u,
                 cur_pos, cur_e, best_pos, best_e, best_cycle, accepted, trace, flags, iterations, temperature, step_init=1.0, restraint=0.0,
                 grow=2.0, shrink=0.5, step_max=1024.0, starts=None):
@@ -914,31 +951,9 @@ def pose_search(anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config,
     of this call, is read off their shape); the row state cur_pos, best_pos [rows, n, 3] fp32, cur_e, best_e [rows, 4] fp64, best_cycle,
     accepted int32 [rows] (in/out; cycle0 = 0: written fresh by the kernel); trace [C, rows, 2] fp64, flags uint8 [C, rows]; starts
     [C, rows, n, 3] fp32 or None; iterations: of one descent.  Shapes and dtypes are checked here; no device tensor is downloaded."""
-    who = "pose_search"
-    dev, S, n, m, rec_stride = pose_dims(who, anchor, rec)
-    T = 0 if bonds is None else int(bonds.shape[0])
-    replicas, cycle0, iterations = int(replicas), int(cycle0), int(iterations)
-    if replicas < 1 or cycle0 < 0 or iterations < 0:
-        raise L.DdpError(f"{who}: replicas < 1, cycle0 < 0 or iterations < 0")
-    if u is None or u.dim() != 2:
-        raise L.DdpError(f"{who}: u [cycles, rows]")
-    Cn, rows = int(u.shape[0]), S * replicas
-    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
-    ligand = [(anchor, f32, (S, n, 3), "anchor"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"), (rec, f32, None, "rec"),
-              (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (self_pairs, u8, (n, n), "self_pairs"),
-              (bonds, i32, (T, 2), "bonds"), (mask_rotate, u8, (T, n), "mask_rotate")]
-    chain = [(perturb, f32, (Cn, rows, 6 + T), "perturb"), (u, f64, (Cn, rows), "u"), (cur_pos, f32, (rows, n, 3), "cur_pos"),
-             (cur_e, f64, (rows, 4), "cur_e"), (best_pos, f32, (rows, n, 3), "best_pos"), (best_e, f64, (rows, 4), "best_e"),
-             (best_cycle, i32, (rows,), "best_cycle"), (accepted, i32, (rows,), "accepted"), (trace, f64, (Cn, rows, 2), "trace"),
-             (flags, u8, (Cn, rows), "flags"), (starts, f32, (Cn, rows, n, 3), "starts")]
-    a = L.SearchArgs(replicas=replicas, cycles=Cn, cycle0=cycle0, step_init=float(step_init), temperature=float(temperature))
-    a.min = _pose_args(L.MinimizeArgs, who, dev, ligand, ("self_pairs",) + (("bonds", "mask_rotate") if T == 0 else ()), config, n_samples=S, n=n,
-                       m=m, rec_stride=rec_stride, n_tor=T, iterations=iterations, restraint=float(restraint), grow=float(grow),
-                       shrink=float(shrink), step_max=float(step_max))
-    check_tensors(who, dev, chain, ("starts",))
-    for t, _, _, name in chain:
-        setattr(a, name, _p(t) or None)
-    L.check(L.load().ddp_pose_search(C.byref(a), stream()), "ddp_pose_search")
+    _search("pose_search", L.SearchArgs, "min", L.MinimizeArgs, 4, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs,
+            bonds, mask_rotate, replicas, cycle0, perturb, u, cur_pos, cur_e, best_pos, best_e, best_cycle, accepted, trace, flags, iterations,
+            temperature, step_init, restraint, grow, shrink, step_max, starts)
 
 
 def pose_search_select(best_pos, best_e, best_cycle, replicas, pos_out=None, energy_out=None, replica_out=None, cycle_out=None):
@@ -988,13 +1003,9 @@ def flex_tables(sc, m: int, device) -> dict:
     return out
 
 
-def pose_minimize_flex(pos, anchor, lig_radii, lig_flags, rec, rec_anchor, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate,
-                       tables, step, accepted, energy_in, energy_out, iterations, restraint=0.0, restraint_sc=0.0, grow=2.0, shrink=0.5,
-                       step_max=1024.0, history=None, grad=None, grad_mov=None):
-    """ddp_pose_minimize_flex: `iterations` iterations of the joint line search of minimize_flex.py on every pose, in one launch.  As
-    pose_minimize, with: rec (in/out) and rec_anchor [S, m, 3] fp32, one receptor per sample; tables: what flex_tables returns (its
-    values are not looked at here); energy_in, energy_out [S, 6]; grad_mov [S, n_mov, 3] fp64 or None.  Shapes and dtypes are checked
-    here; no device tensor is downloaded."""
+def _flex_side(tables, rec_anchor, restraint_sc, grad_mov=None):
+    """The `side` of _minimize and _search for the joint entries: the rows of the side-chain tables (what flex_tables returns; its
+    values are not looked at here), rec_anchor and the optional grad_mov, and the side chains' scalars."""
     mov, edge, sub, mapping, pairs = (tables[k] for k in ("mov", "edge_idx", "sub", "mapping", "pairs"))
     n_mov, n_sc, n_sub = int(mov.shape[0]), int(edge.shape[0]), int(sub.shape[0])
 
@@ -1005,8 +1016,19 @@ def pose_minimize_flex(pos, anchor, lig_radii, lig_flags, rec, rec_anchor, rec_r
                 (grad_mov, torch.float64, (S, n_mov, 3), "grad_mov")]
         return rows, ("grad_mov",), dict(n_mov=n_mov, n_sc=n_sc, n_sub=n_sub, restraint_sc=float(restraint_sc))
 
+    return side
+
+
+def pose_minimize_flex(pos, anchor, lig_radii, lig_flags, rec, rec_anchor, rec_radii, rec_flags, config, self_pairs, bonds, mask_rotate,
+                       tables, step, accepted, energy_in, energy_out, iterations, restraint=0.0, restraint_sc=0.0, grow=2.0, shrink=0.5,
+                       step_max=1024.0, history=None, grad=None, grad_mov=None):
+    """ddp_pose_minimize_flex: `iterations` iterations of the joint line search of minimize_flex.py on every pose, in one launch.  As
+    pose_minimize, with: rec (in/out) and rec_anchor [S, m, 3] fp32, one receptor per sample; tables: what flex_tables returns (its
+    values are not looked at here); energy_in, energy_out [S, 6]; grad_mov [S, n_mov, 3] fp64 or None.  Shapes and dtypes are checked
+    here; no device tensor is downloaded."""
     _minimize("pose_minimize_flex", L.MinimizeFlexArgs, 6, pos, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config, self_pairs,
-              bonds, mask_rotate, step, accepted, energy_in, energy_out, iterations, restraint, grow, shrink, step_max, history, grad, side)
+              bonds, mask_rotate, step, accepted, energy_in, energy_out, iterations, restraint, grow, shrink, step_max, history, grad,
+              _flex_side(tables, rec_anchor, restraint_sc, grad_mov))
 
 
 # ------------------------------------------------------------------------------------------------ flexible search (csrc/ddp_search_flex.hip)
@@ -1019,37 +1041,10 @@ def pose_search_flex(anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, co
     6 + T + n_sc]; the moving atoms of the row state cur_mov, best_mov [rows, n_mov, 3] fp32; cur_e, best_e [rows, 6]; starts_mov
     [C, rows, n_mov, 3] or None; rec_anchor [S, m, 3]: the anchor of the side-chain restraint (None: rec, the definition).  Shapes and
     dtypes are checked here; no device tensor is downloaded."""
-    who = "pose_search_flex"
-    dev, S, n, m, rec_stride = pose_dims(who, anchor, rec, per_sample=True)
-    T = 0 if bonds is None else int(bonds.shape[0])
-    replicas, cycle0, iterations = int(replicas), int(cycle0), int(iterations)
-    if replicas < 1 or cycle0 < 0 or iterations < 0:
-        raise L.DdpError(f"{who}: replicas < 1, cycle0 < 0 or iterations < 0")
-    if u is None or u.dim() != 2:
-        raise L.DdpError(f"{who}: u [cycles, rows]")
-    mov, edge, sub, mapping, pairs = (tables[k] for k in ("mov", "edge_idx", "sub", "mapping", "pairs"))
-    n_mov, n_sc, n_sub = int(mov.shape[0]), int(edge.shape[0]), int(sub.shape[0])
-    rec_anchor = rec if rec_anchor is None else rec_anchor
-    Cn, rows = int(u.shape[0]), S * replicas
-    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
-    state = [(anchor, f32, (S, n, 3), "anchor"), (lig_radii, f32, (n,), "lig_radii"), (lig_flags, u8, (n,), "lig_flags"), (rec, f32, (S, m, 3), "rec"),
-             (rec_radii, f32, (m,), "rec_radii"), (rec_flags, u8, (m,), "rec_flags"), (self_pairs, u8, (n, n), "self_pairs"),
-             (bonds, i32, (T, 2), "bonds"), (mask_rotate, u8, (T, n), "mask_rotate"), (rec_anchor, f32, (S, m, 3), "rec_anchor"),
-             (mov, i32, (n_mov,), "mov"), (edge, i32, (n_sc, 2), "sc_edge_idx"), (sub, i32, (n_sub,), "sc_sub"), (mapping, i32, (n_sc, 2), "sc_map"),
-             (pairs, u8, (n_mov, m), "sc_pairs")]
-    chain = [(perturb, f32, (Cn, rows, 6 + T + n_sc), "perturb"), (u, f64, (Cn, rows), "u"), (cur_pos, f32, (rows, n, 3), "cur_pos"),
-             (cur_mov, f32, (rows, n_mov, 3), "cur_mov"), (cur_e, f64, (rows, 6), "cur_e"), (best_pos, f32, (rows, n, 3), "best_pos"),
-             (best_mov, f32, (rows, n_mov, 3), "best_mov"), (best_e, f64, (rows, 6), "best_e"), (best_cycle, i32, (rows,), "best_cycle"),
-             (accepted, i32, (rows,), "accepted"), (trace, f64, (Cn, rows, 2), "trace"), (flags, u8, (Cn, rows), "flags"),
-             (starts, f32, (Cn, rows, n, 3), "starts"), (starts_mov, f32, (Cn, rows, n_mov, 3), "starts_mov")]
-    a = L.SearchFlexArgs(replicas=replicas, cycles=Cn, cycle0=cycle0, step_init=float(step_init), temperature=float(temperature))
-    a.flex = _pose_args(L.MinimizeFlexArgs, who, dev, state, ("self_pairs",) + (("bonds", "mask_rotate") if T == 0 else ()), config, n_samples=S,
-                        n=n, m=m, rec_stride=rec_stride, n_tor=T, iterations=iterations, restraint=float(restraint), grow=float(grow),
-                        shrink=float(shrink), step_max=float(step_max), n_mov=n_mov, n_sc=n_sc, n_sub=n_sub, restraint_sc=float(restraint_sc))
-    check_tensors(who, dev, chain, ("starts", "starts_mov"))
-    for t, _, _, name in chain:
-        setattr(a, name, _p(t) or None)
-    L.check(L.load().ddp_pose_search_flex(C.byref(a), stream()), "ddp_pose_search_flex")
+    _search("pose_search_flex", L.SearchFlexArgs, "flex", L.MinimizeFlexArgs, 6, anchor, lig_radii, lig_flags, rec, rec_radii, rec_flags, config,
+            self_pairs, bonds, mask_rotate, replicas, cycle0, perturb, u, cur_pos, cur_e, best_pos, best_e, best_cycle, accepted, trace, flags,
+            iterations, temperature, step_init, restraint, grow, shrink, step_max, starts,
+            _flex_side(tables, rec if rec_anchor is None else rec_anchor, restraint_sc), (cur_mov, best_mov, starts_mov))
 
 
 # ------------------------------------------------------------------------------------------------ pocket finder (csrc/ddp_pockets.hip)

@@ -62,6 +62,7 @@ from typing import Optional
 
 import torch
 
+from . import _lib as _L
 from .guidance import MAX_ATOMS, MAX_TORSIONS, cap_factor
 from .guidance import step_weight  # noqa: F401  (w_t of the definition, the same rule as clash guidance: re-exported)
 from .scoring import ScoreConfig
@@ -124,8 +125,17 @@ def increments_torch(x, rec, tables: ScoreGuidanceTables, w_t: float, caps):
     return tuple((f[:, None] * v.double()).float() for v in d)
 
 
-# the limits of ddp_score_guidance_flex (include/ddp_hip.h: DDP_SCORE_GUIDANCE_FLEX_MAX_ATOMS, _MAX_TORSIONS, _MAX_MOVING, _MAX_BONDS)
-FLEX_MAX_ATOMS, FLEX_MAX_TORSIONS, FLEX_MAX_MOVING, FLEX_MAX_BONDS = 512, 1024, 256, 256
+# the limits of ddp_score_guidance_flex, the header's values
+FLEX_MAX_ATOMS, FLEX_MAX_TORSIONS = _L.DDP_SCORE_GUIDANCE_FLEX_MAX_ATOMS, _L.DDP_SCORE_GUIDANCE_FLEX_MAX_TORSIONS
+FLEX_MAX_MOVING, FLEX_MAX_BONDS = _L.DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING, _L.DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS
+
+
+def check_flex_limits(who: str, n: int, T: int, n_mov: int, n_sc: int):
+    """Raises above the limits of ddp_score_guidance_flex, whatever device the sampler runs on."""
+    if n > FLEX_MAX_ATOMS or T > FLEX_MAX_TORSIONS or n_mov > FLEX_MAX_MOVING or n_sc > FLEX_MAX_BONDS:
+        raise ValueError(f"{who}: {n} ligand atoms, {T} rotatable bonds, {n_mov} moving atoms and {n_sc} side-chain bonds exceed the "
+                         f"limits of ddp_score_guidance_flex ({FLEX_MAX_ATOMS} atoms, {FLEX_MAX_TORSIONS} bonds, {FLEX_MAX_MOVING} moving "
+                         f"atoms, {FLEX_MAX_BONDS} side-chain bonds)")
 
 
 def build_sidechain_tables(graph, tables: ScoreGuidanceTables):
@@ -136,11 +146,7 @@ def build_sidechain_tables(graph, tables: ScoreGuidanceTables):
     sc = sidechain_tables(graph)
     if sc is None:
         return None
-    T = int(tables.bonds.shape[0])
-    if tables.n > FLEX_MAX_ATOMS or T > FLEX_MAX_TORSIONS or sc.n_mov > FLEX_MAX_MOVING or sc.n_sc > FLEX_MAX_BONDS:
-        raise ValueError(f"score guidance of side chains: {tables.n} ligand atoms, {T} rotatable bonds, {sc.n_mov} moving atoms and "
-                         f"{sc.n_sc} side-chain bonds exceed the limits of ddp_score_guidance_flex ({FLEX_MAX_ATOMS} atoms, "
-                         f"{FLEX_MAX_TORSIONS} bonds, {FLEX_MAX_MOVING} moving atoms, {FLEX_MAX_BONDS} side-chain bonds)")
+    check_flex_limits("score guidance of side chains", tables.n, int(tables.bonds.shape[0]), sc.n_mov, sc.n_sc)
     return sc
 
 
@@ -189,29 +195,37 @@ class ScoreGuidanceWorkspace:
         a.bonds = self.bonds.data_ptr() if self.T else None
         a.mask_rotate = self.mask_rotate.data_ptr() if self.T else None
 
+    def _bind(self, who, a, lig_pos, atom_pos, upd, weight, energy, width, more, optional):
+        """Checks the tensors of a launch and binds what both argument structs hold: n_samples, pos, weight, rec, rec_stride,
+        upd[0 .. 2] and energy [S, width].  more: the caller's own (tensor, dtype, shape, name) entries for a given S; optional: the
+        names that may be None."""
+        from . import launch as LA
+        S = lig_pos.shape[0]
+        want = [(lig_pos, torch.float32, (S, self.n, 3), "lig_pos"), (upd[0], torch.float32, (S, 3), "upd tr"),
+                (upd[1], torch.float32, (S, 3), "upd rot"), (atom_pos, torch.float32, (S, self.m, 3), "atom_pos"),
+                (energy, torch.float64, (S, width), "energy")] + more(S)
+        if self.T:
+            want.append((upd[2], torch.float32, (S, self.T), "upd tor"))
+        LA.check_tensors(who, self.device, want, optional, error=ValueError)
+        if weight.dtype != torch.float32 or weight.device != self.device or weight.numel() < 1 or not weight.is_contiguous():
+            raise ValueError(f"{who}: weight = one fp32 value in device memory")
+        a.n_samples, a.pos, a.weight = S, lig_pos.data_ptr(), weight.data_ptr()
+        a.rec, a.rec_stride = (self.rec.data_ptr() or None, 0) if atom_pos is None else (atom_pos.data_ptr() or None, 3 * self.m)
+        a.upd[0], a.upd[1], a.upd[2] = upd[0].data_ptr(), upd[1].data_ptr(), (upd[2].data_ptr() if self.T else None)
+        a.energy = energy.data_ptr() if energy is not None else None
+        return torch._C._cuda_getCurrentRawStream(lig_pos.device.index)
+
     def launch(self, lig_pos, atom_pos, upd, weight, energy=None, grad=None):
         """lig_pos [S, n, 3]: the poses the scores were computed for; atom_pos: None (the graph's atom nodes, shared) or [S, m, 3]
         (each sample's own atom positions); upd = (tr [S, 3], rot [S, 3], tor [S, T] or None), updated in place; weight: one fp32 value
         in device memory; energy [S, 2] = (inter, intra), grad [S, n, 3] fp64: optional outputs.  All contiguous tensors on the
         workspace's device."""
         from . import launch as LA
-        S = lig_pos.shape[0]
-        want = [(lig_pos, torch.float32, (S, self.n, 3), "lig_pos"), (upd[0], torch.float32, (S, 3), "upd tr"),
-                (upd[1], torch.float32, (S, 3), "upd rot"), (atom_pos, torch.float32, (S, self.m, 3), "atom_pos"),
-                (energy, torch.float64, (S, 2), "energy"), (grad, torch.float64, (S, self.n, 3), "grad")]
-        if self.T:
-            want.append((upd[2], torch.float32, (S, self.T), "upd tor"))
-        LA.check_tensors("ScoreGuidanceWorkspace.launch", self.device, want, ("atom_pos", "energy", "grad"), error=ValueError)
-        if weight.dtype != torch.float32 or weight.device != self.device or weight.numel() < 1 or not weight.is_contiguous():
-            raise ValueError("ScoreGuidanceWorkspace.launch: weight = one fp32 value in device memory")
         a = self.args
-        a.n_samples, a.pos, a.weight = S, lig_pos.data_ptr(), weight.data_ptr()
-        a.rec, a.rec_stride = (self.rec.data_ptr() or None, 0) if atom_pos is None else (atom_pos.data_ptr() or None, 3 * self.m)
-        a.upd[0], a.upd[1], a.upd[2] = upd[0].data_ptr(), upd[1].data_ptr(), (upd[2].data_ptr() if self.T else None)
-        a.energy = energy.data_ptr() if energy is not None else None
+        st = self._bind("ScoreGuidanceWorkspace.launch", a, lig_pos, atom_pos, upd, weight, energy, 2,
+                        lambda S: [(grad, torch.float64, (S, self.n, 3), "grad")], ("atom_pos", "energy", "grad"))
         a.grad = grad.data_ptr() if grad is not None else None
-        LA.score_guidance(a, torch._C._cuda_getCurrentRawStream(lig_pos.device.index))
-
+        LA.score_guidance(a, st)
 
 
 class ScoreGuidanceFlexWorkspace(ScoreGuidanceWorkspace):
@@ -225,9 +239,7 @@ class ScoreGuidanceFlexWorkspace(ScoreGuidanceWorkspace):
         super().__init__(tables, device, caps)
         self.sc_tables = sc_tables
         self.n_mov, self.n_sc, self.n_sub = sc_tables.n_mov, sc_tables.n_sc, int(sc_tables.sub.shape[0])
-        if self.n > FLEX_MAX_ATOMS or self.T > FLEX_MAX_TORSIONS or self.n_mov > FLEX_MAX_MOVING or self.n_sc > FLEX_MAX_BONDS:
-            raise ValueError(f"ScoreGuidanceFlexWorkspace: {self.n} ligand atoms, {self.T} rotatable bonds, {self.n_mov} moving atoms, "
-                             f"{self.n_sc} side-chain bonds exceed the limits of ddp_score_guidance_flex")
+        check_flex_limits("ScoreGuidanceFlexWorkspace", self.n, self.T, self.n_mov, self.n_sc)
         self._sc_dev = LA.flex_tables(sc_tables, self.m, device)
         b, d = self.args, self._sc_dev
         a = self.flex_args = L.ScoreGuidanceFlexArgs(n=self.n, m=self.m, n_tor=self.T, form=b.form, max_tr=b.max_tr, max_rot=b.max_rot,
@@ -243,22 +255,10 @@ class ScoreGuidanceFlexWorkspace(ScoreGuidanceWorkspace):
         upd_sc [S, n_sc] fp32, updated in place (None with n_sc = 0); energy [S, 3] = (inter, intra, sc), grad_mov [S, n_mov, 3] fp64:
         optional outputs.  All contiguous tensors on the workspace's device."""
         from . import launch as LA
-        S = lig_pos.shape[0]
-        want = [(lig_pos, torch.float32, (S, self.n, 3), "lig_pos"), (upd[0], torch.float32, (S, 3), "upd tr"),
-                (upd[1], torch.float32, (S, 3), "upd rot"), (atom_pos, torch.float32, (S, self.m, 3), "atom_pos"),
-                (energy, torch.float64, (S, 3), "energy"), (grad_mov, torch.float64, (S, self.n_mov, 3), "grad_mov")]
-        if self.T:
-            want.append((upd[2], torch.float32, (S, self.T), "upd tor"))
-        if self.n_sc:
-            want.append((upd_sc, torch.float32, (S, self.n_sc), "upd sc"))
-        LA.check_tensors("ScoreGuidanceFlexWorkspace.launch", self.device, want, ("energy", "grad_mov"), error=ValueError)
-        if weight.dtype != torch.float32 or weight.device != self.device or weight.numel() < 1 or not weight.is_contiguous():
-            raise ValueError("ScoreGuidanceFlexWorkspace.launch: weight = one fp32 value in device memory")
         a = self.flex_args
-        a.n_samples, a.pos, a.weight = S, lig_pos.data_ptr(), weight.data_ptr()
-        a.rec, a.rec_stride = atom_pos.data_ptr() or None, 3 * self.m
-        a.upd[0], a.upd[1], a.upd[2] = upd[0].data_ptr(), upd[1].data_ptr(), (upd[2].data_ptr() if self.T else None)
+        more = lambda S: [(grad_mov, torch.float64, (S, self.n_mov, 3), "grad_mov")] + \
+            ([(upd_sc, torch.float32, (S, self.n_sc), "upd sc")] if self.n_sc else [])
+        st = self._bind("ScoreGuidanceFlexWorkspace.launch", a, lig_pos, atom_pos, upd, weight, energy, 3, more, ("energy", "grad_mov"))
         a.upd_sc = upd_sc.data_ptr() if self.n_sc else None
-        a.energy = energy.data_ptr() if energy is not None else None
         a.grad_mov = grad_mov.data_ptr() if grad_mov is not None else None
-        LA.score_guidance_flex(a, torch._C._cuda_getCurrentRawStream(lig_pos.device.index))
+        LA.score_guidance_flex(a, st)

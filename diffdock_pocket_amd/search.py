@@ -121,28 +121,47 @@ class SearchResult:
         return SearchResult(**{k: v.cpu() for k, v in self.__dict__.items()})
 
     def index(self, order) -> "SearchResult":
-        S = self.lig_pos.shape[0]
-        R = self.trace.shape[1] // S if S else 1
-        out = {}
-        for k, v in self.__dict__.items():
-            if isinstance(v, PoseScores):
-                out[k] = v.index(order)
-            elif k in ("trace", "flags"):
-                o = order.to(v.device).long()
-                out[k] = v[:, (o[:, None] * R + torch.arange(R, device=v.device)[None]).reshape(-1)]
-            else:
-                out[k] = v[order.to(v.device)]
-        return SearchResult(**out)
+        return index_result(self, order)
 
 
-def draw_random_numbers(config: SearchConfig, rows: int, T: int):
-    """(perturb [C, rows, 6 + T] fp32, u [C, rows] fp64) of the module docstring, on the host: one generator, randn then rand."""
+def index_result(result, order):
+    """A SearchResult or FlexSearchResult with the samples `order`: per-sample fields by sample, trace and flags by the samples' rows."""
+    S = result.lig_pos.shape[0]
+    R = result.trace.shape[1] // S if S else 1
+    out = {}
+    for k, v in result.__dict__.items():
+        if isinstance(v, PoseScores):
+            out[k] = v.index(order)
+        elif k in ("trace", "flags"):
+            o = order.to(v.device).long()
+            out[k] = v[:, (o[:, None] * R + torch.arange(R, device=v.device)[None]).reshape(-1)]
+        else:
+            out[k] = v[order.to(v.device)]
+    return type(result)(**out)
+
+
+def check_config(c: SearchConfig, sidechains: bool = False):
+    """Raises ValueError for constants no search can run with; sidechains: sigma_chi and sidechain_restraint are looked at too."""
+    if c.replicas < 1 or c.cycles < 0 or c.iterations < 0:
+        raise ValueError("SearchConfig: replicas must be at least 1, cycles and iterations must not be negative")
+    if not (c.temperature > 0) or c.temperature == float("inf"):
+        raise ValueError("SearchConfig: temperature must be positive and finite")
+    own = ((c.sidechain_restraint,), (c.sigma_chi,)) if sidechains else ((), ())
+    if not all(k >= 0 for k in (c.restraint,) + own[0]) or min(c.sigma_tr, c.sigma_rot, c.sigma_tor, *own[1]) < 0:
+        raise ValueError("SearchConfig: the restraints and the sigmas must not be negative" if sidechains else
+                         "SearchConfig: restraint and the sigmas must not be negative")
+
+
+def draw_random_numbers(config: SearchConfig, rows: int, T: int, n_sc: int = 0):
+    """(perturb [C, rows, 6 + T + n_sc] fp32, u [C, rows] fp64) of the module docstring (n_sc > 0: of search_flex.py's), on the host: one
+    generator, randn then rand; the four blocks of perturb scaled by sigma_tr, sigma_rot, sigma_tor and sigma_chi."""
     gen = torch.Generator().manual_seed(int(config.seed))
-    perturb = torch.randn(config.cycles, rows, 6 + T, generator=gen, dtype=torch.float32)
+    perturb = torch.randn(config.cycles, rows, 6 + T + n_sc, generator=gen, dtype=torch.float32)
     u = torch.rand(config.cycles, rows, generator=gen, dtype=torch.float64)
     perturb[..., 0:3] *= float(config.sigma_tr)
     perturb[..., 3:6] *= float(config.sigma_rot)
-    perturb[..., 6:] *= float(config.sigma_tor)
+    perturb[..., 6:6 + T] *= float(config.sigma_tor)
+    perturb[..., 6 + T:] *= float(config.sigma_chi)
     return perturb.contiguous(), u.contiguous()
 
 
@@ -151,32 +170,40 @@ def per_row(t, R: int):
     return t[:, None].expand(t.shape[0], R, *t.shape[1:]).reshape(t.shape[0] * R, *t.shape[1:])
 
 
-def select_torch(best_e, best_pos, best_cycle, R: int):
-    """The selection rule with tensor operations (any device, no synchronisation): (pos [S, n, 3], energy [S, 4], replica [S] int32,
-    cycle [S] int32).  argmin returns the first of equal values: the lower replica; NaN and +inf count as +inf."""
+def select_rows(best_e, best_cycle, R: int, *coords):
+    """The selection rule with tensor operations (any device, no synchronisation) on the last entry of best_e: (the rows of every tensor
+    of coords, energy [S, .], replica [S] int32, cycle [S] int32).  argmin returns the first of equal values: the lower replica; NaN and
+    +inf count as +inf."""
     S = best_e.shape[0] // R
-    e3 = best_e[:, 3].reshape(S, R)
-    key = torch.where(e3 < float("inf"), e3, torch.full_like(e3, float("inf")))
+    e = best_e[:, -1].reshape(S, R)
+    key = torch.where(e < float("inf"), e, torch.full_like(e, float("inf")))
     rep = key.argmin(1) if S else torch.zeros(0, dtype=torch.int64, device=best_e.device)
     q = torch.arange(S, device=best_e.device) * R + rep
-    return best_pos[q].clone(), best_e[q].clone(), rep.to(torch.int32), best_cycle[q].clone()
+    return [t[q].clone() for t in coords], best_e[q].clone(), rep.to(torch.int32), best_cycle[q].clone()
+
+
+def select_torch(best_e, best_pos, best_cycle, R: int):
+    """select_rows for the rigid state: (pos [S, n, 3], energy [S, 4], replica [S] int32, cycle [S] int32)."""
+    (pos,), e, rep, cyc = select_rows(best_e, best_cycle, R, best_pos)
+    return pos, e, rep, cyc
 
 
 class PoseSearcher:
     """The search around the poses of one complex (see the module docstring).
 
     graph, device, receptor, score_config, scorer: as PoseMinimizer.  One PoseMinimizer is built (iterations = config.iterations,
-    restraint = config.restraint, the default step constants) and its tables are reused."""
+    restraint = config.restraint, the default step constants) and its tables are reused.
+
+    The chain driver below (the fresh state, advance with its clone / early-out / "cycle 0 is a launch of its own" logic, steps 3 to 5
+    of a cycle, what a result derives from a state) serves search_flex.FlexPoseSearcher too: a state is the sampled input, the
+    coordinate tensors cur_X / best_X for X in _COORDS, which are always taken or kept together, and _WIDTH energies with the total
+    last."""
+    _State, _COORDS, _WIDTH = SearchState, ("pos",), 4
 
     def __init__(self, graph, device="cpu", receptor=None, score_config: Optional[ScoreConfig] = None,
                  config: Optional[SearchConfig] = None, scorer: Optional[PoseScorer] = None):
         c = self.config = config or SearchConfig()
-        if c.replicas < 1 or c.cycles < 0 or c.iterations < 0:
-            raise ValueError("SearchConfig: replicas must be at least 1, cycles and iterations must not be negative")
-        if not (c.temperature > 0) or c.temperature == float("inf"):
-            raise ValueError("SearchConfig: temperature must be positive and finite")
-        if not (c.restraint >= 0) or min(c.sigma_tr, c.sigma_rot, c.sigma_tor) < 0:
-            raise ValueError("SearchConfig: restraint and the sigmas must not be negative")
+        check_config(c)
         self.minimizer = PoseMinimizer(graph, device, receptor=receptor, score_config=score_config, scorer=scorer,
                                        config=MinimizeConfig(iterations=c.iterations, restraint=c.restraint))
         self.device = self.minimizer.device
@@ -184,59 +211,78 @@ class PoseSearcher:
         self.n, self.T = self.minimizer.n, self.minimizer.T
         self._ref_lig = self.minimizer._ref_lig.to(self.device)      # uploaded once: the cycles never synchronise
 
+    @property
+    def _rigid(self) -> PoseMinimizer:
+        """The minimiser that holds the ligand's torsion tables."""
+        return self.minimizer
+
     # ---- state
-    def start(self, lig_pos, atom_pos=None) -> SearchState:
-        """The fresh state of lig_pos [S, n, 3] with the random numbers of config.cycles cycles on the poses' device."""
-        mz, c = self.minimizer, self.config
-        mz._check(lig_pos, atom_pos)
-        x0 = lig_pos.float().contiguous().clone()
-        S, R, dev = x0.shape[0], c.replicas, x0.device
-        rows = S * R
-        perturb, u = draw_random_numbers(c, rows, self.T)
+    def _fresh(self, sampled: dict, coords, n_sc: int = 0):
+        """The fresh state: sampled = the inputs (x0 [S, n, 3] first), coords = the rows' coordinates in the order of _COORDS, with the
+        random numbers of config.cycles cycles on the poses' device."""
+        c, W = self.config, self._WIDTH
+        x0 = sampled["x0"]
+        S, dev = x0.shape[0], x0.device
+        rows = S * c.replicas
+        perturb, u = draw_random_numbers(c, rows, self.T, n_sc)
         if dev.type != "cpu":          # from pinned memory: the upload does not synchronise
             perturb, u = (t.pin_memory().to(dev, non_blocking=True) for t in (perturb, u))
         inf = float("inf")
         f64 = dict(dtype=torch.float64, device=dev)
-        xr = per_row(x0, R).contiguous()
-        return SearchState(x0, xr, torch.full((rows, 4), inf, **f64), xr.clone(), torch.full((rows, 4), inf, **f64),
-                           torch.full((rows,), -1, dtype=torch.int32, device=dev), torch.zeros(rows, dtype=torch.int32, device=dev),
-                           perturb, u, torch.full((c.cycles, rows, 2), float("nan"), **f64),
-                           torch.zeros(c.cycles, rows, dtype=torch.uint8, device=dev), torch.full((S, 4), inf, **f64), 0)
+        kw = {p + k: (t if p == "cur_" else t.clone()) for k, t in zip(self._COORDS, coords) for p in ("cur_", "best_")}
+        return self._State(**sampled, **kw, cur_e=torch.full((rows, W), inf, **f64), best_e=torch.full((rows, W), inf, **f64),
+                           best_cycle=torch.full((rows,), -1, dtype=torch.int32, device=dev),
+                           accepted=torch.zeros(rows, dtype=torch.int32, device=dev), perturb=perturb, u=u,
+                           trace=torch.full((c.cycles, rows, 2), float("nan"), **f64),
+                           flags=torch.zeros(c.cycles, rows, dtype=torch.uint8, device=dev), energy_minimized=torch.full((S, W), inf, **f64),
+                           cycle=0)
+
+    def start(self, lig_pos, atom_pos=None) -> SearchState:
+        """The fresh state of lig_pos [S, n, 3] with the random numbers of config.cycles cycles on the poses' device."""
+        self.minimizer._check(lig_pos, atom_pos)
+        x0 = lig_pos.float().contiguous().clone()
+        return self._fresh(dict(x0=x0), [per_row(x0, self.config.replicas).contiguous()])
+
+    def _advance(self, state, cycles: int, fused: bool, run_fused, cycle):
+        """`cycles` further cycles on a copy of `state`: run_fused(st, a, b) runs the cycles a ... b - 1 in one launch, cycle(st, c) one
+        cycle with tensor operations."""
+        R = self.config.replicas
+        c0, c1 = state.cycle, state.cycle + int(cycles)
+        if cycles < 0 or c1 > state.u.shape[0]:
+            raise ValueError(f"advance: {cycles} cycles from cycle {c0}, the state carries the random numbers of {state.u.shape[0]}")
+        moving = [p + k for k in self._COORDS + ("e",) for p in ("cur_", "best_")]
+        st = replace(state, **{k: getattr(state, k).clone() for k in moving + ["best_cycle", "accepted", "trace", "flags", "energy_minimized"]})
+        st.cycle = c1
+        if cycles == 0 or state.x0.shape[0] == 0:
+            return st
+        if fused:
+            with torch.cuda.device(state.x0.device):
+                if c0 == 0:      # cycle 0 is a launch of its own: the state between it and cycle 1 holds energy_minimized
+                    run_fused(st, 0, 1)
+                    st.energy_minimized = st.cur_e[::R].clone()
+                if c1 > max(c0, 1):
+                    run_fused(st, max(c0, 1), c1)
+        else:
+            for cyc in range(c0, c1):
+                cycle(st, cyc)
+        return st
 
     def advance(self, state: SearchState, cycles: int, atom_pos=None, fused: bool = True, starts=None) -> SearchState:
         """`cycles` further cycles on a copy of `state` (which is not modified): cycles state.cycle ... state.cycle + cycles - 1 with the
         state's own random numbers.  advance(a) followed by advance(b) equals advance(a + b) (the fused form: bit for bit).  starts: a
         list that receives the [S R, n, 3] start pose of every cycle run (device tensors, no synchronisation)."""
-        c, mz = self.config, self.minimizer
-        c0, c1 = state.cycle, state.cycle + int(cycles)
-        if cycles < 0 or c1 > state.u.shape[0]:
-            raise ValueError(f"advance: {cycles} cycles from cycle {c0}, the state carries the random numbers of {state.u.shape[0]}")
+        mz = self.minimizer
         mz._check(state.x0, atom_pos)
-        st = replace(state, **{k: getattr(state, k).clone() for k in ("cur_pos", "cur_e", "best_pos", "best_e", "best_cycle", "accepted",
-                                                                      "trace", "flags", "energy_minimized")})
-        if cycles == 0 or state.x0.shape[0] == 0:
-            st.cycle = c1
-            return st
         if not state.x0.is_cuda:
             fused = False
-        elif fused and not mz.fused_available():
+        elif fused and cycles > 0 and state.x0.shape[0] and not mz.fused_available():
             from . import _lib as L
             _warn_once(f"PoseSearcher: {self.n} ligand atoms / {self.T} rotatable bonds exceed the fused kernel's limits "
                        f"(DDP_MINIMIZE_MAX_ATOMS = {L.DDP_MINIMIZE_MAX_ATOMS}, DDP_MINIMIZE_MAX_TORSIONS = {L.DDP_MINIMIZE_MAX_TORSIONS}): "
                        "running cycle by cycle, launch by launch")
             fused = False
-        if fused:
-            with torch.cuda.device(state.x0.device):
-                if c0 == 0:      # cycle 0 is a launch of its own: the state between it and cycle 1 holds energy_minimized
-                    self._run_fused(st, 0, 1, atom_pos, starts)
-                    st.energy_minimized = st.cur_e[::c.replicas].clone()
-                if c1 > max(c0, 1):
-                    self._run_fused(st, max(c0, 1), c1, atom_pos, starts)
-        else:
-            for cyc in range(c0, c1):
-                self._cycle(st, cyc, atom_pos, starts)
-        st.cycle = c1
-        return st
+        return self._advance(state, cycles, fused, lambda st, a, b: self._run_fused(st, a, b, atom_pos, starts),
+                             lambda st, cyc: self._cycle(st, cyc, atom_pos, starts))
 
     def _run_fused(self, st: SearchState, a: int, b: int, atom_pos, starts):
         from . import launch as LA
@@ -252,47 +298,57 @@ class PoseSearcher:
         if starts is not None:
             starts.extend(so.unbind(0))
 
-    def _cycle(self, st: SearchState, cyc: int, atom_pos, starts):
-        """One cycle of all rows with tensor operations: the CPU form, and the launch-by-launch device form (it never synchronises)."""
-        c, mz = self.config, self.minimizer
-        R, dev = c.replicas, st.x0.device
-        rows = st.cur_pos.shape[0]
-        xc = st.cur_pos
-        # 1. start pose.  A row without finite coordinates goes through the pose map as the graph's own pose with a zero move (its
-        # NaNs never reach the batched SVD of the alignment) and then starts from its own pose: its energy is NaN, it never moves.
-        fin = torch.isfinite(xc).all(2).all(1)
+    def _start_pose(self, st, cyc: int, fin):
+        """Step 1 for the ligand of all rows: (p, keep, start) = the cycle's move, the rows that start where they are and the start pose.
+        A row without finite coordinates (fin false) goes through the pose map as the graph's own pose with a zero move (its NaNs never
+        reach the batched SVD of the alignment) and then starts from its own pose: its energy is NaN, it never moves."""
+        mz, T, dev, xc = self._rigid, self.T, st.x0.device, st.cur_pos
         p = torch.where(fin[:, None], st.perturb[cyc], torch.zeros_like(st.perturb[cyc]))
-        src = torch.where(fin[:, None, None], xc, self._ref_lig[None])
-        tor = p[:, 6:].contiguous() if self.T else None
+        src = torch.where(fin[:, None, None], xc, self._ref_lig.to(dev)[None])
+        tor = p[:, 6:6 + T].contiguous() if T else None
         if dev.type == "cpu":
             moved = modify_conformer(src, p[:, 0:3], p[:, 3:6], tor, mz.bonds, mz.rot_idx)
         else:
             moved = modify_conformer_hip(src, p[:, 0:3], p[:, 3:6], tor, mz._bonds_i32, mz._mask_u8)
         keep = ~fin
         if cyc == 0:
-            keep = keep | (torch.arange(rows, device=dev) % R == 0)
-        start = torch.where(keep[:, None, None], xc, moved).contiguous()
-        if starts is not None:
-            starts.append(start)
-        # 2. descent
-        step = torch.full((rows,), float(mz.config.step_init), dtype=torch.float64, device=dev)
-        zero = torch.zeros(rows, dtype=torch.int32, device=dev)
-        ap = None if atom_pos is None else per_row(atom_pos, R)
-        xl, _, taken, e_start, el = mz.advance(start, per_row(st.x0, R), step, zero, c.iterations, ap, fused=False)
-        # 3. Metropolis, 4. best, 5. record
-        d = el[:, 3] - st.cur_e[:, 3]
-        move = (el[:, 3] < st.cur_e[:, 3]) | (st.u[cyc] < torch.exp(-d / c.temperature))
-        improved = el[:, 3] < st.best_e[:, 3]
-        st.cur_pos = torch.where(move[:, None, None], xl, xc)
+            keep = keep | (torch.arange(xc.shape[0], device=dev) % self.config.replicas == 0)
+        return p, keep, torch.where(keep[:, None, None], xc, moved).contiguous()
+
+    def _descent_step(self, rows: int, dev):
+        """(step, accepted) every descent of a cycle starts with."""
+        return (torch.full((rows,), float(self.minimizer.config.step_init), dtype=torch.float64, device=dev),
+                torch.zeros(rows, dtype=torch.int32, device=dev))
+
+    def _decide(self, st, cyc: int, minimum, taken, e_start, el):
+        """Steps 3 to 5 of a cycle on all rows with tensor operations: 3. Metropolis, 4. best, 5. record.  minimum: the local minimum's
+        coordinates in the order of _COORDS; el, e_start: its energies and the start state's."""
+        R = self.config.replicas
+        d = el[:, -1] - st.cur_e[:, -1]
+        move = (el[:, -1] < st.cur_e[:, -1]) | (st.u[cyc] < torch.exp(-d / self.config.temperature))
+        improved = el[:, -1] < st.best_e[:, -1]
+        for k, xl in zip(self._COORDS, minimum):
+            setattr(st, "cur_" + k, torch.where(move[:, None, None], xl, getattr(st, "cur_" + k)))
+            setattr(st, "best_" + k, torch.where(improved[:, None, None], xl, getattr(st, "best_" + k)))
         st.cur_e = torch.where(move[:, None], el, st.cur_e)
-        st.best_pos = torch.where(improved[:, None, None], xl, st.best_pos)
         st.best_e = torch.where(improved[:, None], el, st.best_e)
         st.best_cycle = torch.where(improved, torch.full_like(st.best_cycle, cyc), st.best_cycle)
         st.accepted = st.accepted + taken
-        st.trace[cyc, :, 0], st.trace[cyc, :, 1] = e_start[:, 3], el[:, 3]
+        st.trace[cyc, :, 0], st.trace[cyc, :, 1] = e_start[:, -1], el[:, -1]
         st.flags[cyc] = move.to(torch.uint8) | (improved.to(torch.uint8) << 1)
         if cyc == 0:
             st.energy_minimized = st.cur_e[::R].clone()
+
+    def _cycle(self, st: SearchState, cyc: int, atom_pos, starts):
+        """One cycle of all rows with tensor operations: the CPU form, and the launch-by-launch device form (it never synchronises)."""
+        R = self.config.replicas
+        _, _, start = self._start_pose(st, cyc, torch.isfinite(st.cur_pos).all(2).all(1))
+        if starts is not None:
+            starts.append(start)
+        step, zero = self._descent_step(start.shape[0], start.device)
+        ap = None if atom_pos is None else per_row(atom_pos, R)
+        xl, _, taken, e_start, el = self.minimizer.advance(start, per_row(st.x0, R), step, zero, self.config.iterations, ap, fused=False)
+        self._decide(st, cyc, [xl], taken, e_start, el)
 
     # ---- results
     def select(self, state: SearchState, fused: bool = True):
@@ -304,19 +360,23 @@ class PoseSearcher:
                 return LA.pose_search_select(state.best_pos, state.best_e, state.best_cycle, R)
         return select_torch(state.best_e, state.best_pos, state.best_cycle, R)
 
-    def result(self, state: SearchState, atom_pos=None, fused: bool = True) -> SearchResult:
-        """The SearchResult of a state.  A state without a cycle (config.cycles = 0) gives the sampled poses back: the identity."""
-        mz, R = self.minimizer, self.config.replicas
-        x0 = state.x0
+    def _summary(self, state, e_before, e_after, pos, rep):
+        """What a result derives from a state and its selection: (energy_minimized, energy_after, moves [S] int32, rmsd_moved [S]
+        fp32).  A state without a cycle (config.cycles = 0) gives the sampled state back: the identity."""
+        x0, e_min = state.x0, state.energy_minimized
         S = x0.shape[0]
-        e_before, _ = mz.energy(x0, atom_pos=atom_pos) if S else (torch.zeros(0, 4, dtype=torch.float64, device=x0.device), None)
-        pos, e_after, rep, cyc = self.select(state, fused)
-        e_min = state.energy_minimized
         if state.cycle == 0:
             e_after, e_min = e_before.clone(), e_before.clone()
-        q = torch.arange(S, device=x0.device) * R + rep.long()
+        q = torch.arange(S, device=x0.device) * self.config.replicas + rep.long()
         moves = (state.flags[:state.cycle, q] & 1).sum(0).to(torch.int32) if S else torch.zeros(0, dtype=torch.int32, device=x0.device)
-        moved = (pos.double() - x0.double()).pow(2).sum(-1).mean(-1).sqrt().float()
+        return e_min, e_after, moves, (pos.double() - x0.double()).pow(2).sum(-1).mean(-1).sqrt().float()
+
+    def result(self, state: SearchState, atom_pos=None, fused: bool = True) -> SearchResult:
+        """The SearchResult of a state.  A state without a cycle (config.cycles = 0) gives the sampled poses back: the identity."""
+        x0 = state.x0
+        e_before = self.minimizer.energy(x0, atom_pos=atom_pos)[0] if x0.shape[0] else torch.zeros(0, 4, dtype=torch.float64, device=x0.device)
+        pos, e_after, rep, cyc = self.select(state, fused)
+        e_min, e_after, moves, moved = self._summary(state, e_before, e_after, pos, rep)
         return SearchResult(pos, e_before, e_min, e_after, self.scorer.score(x0, atom_pos), self.scorer.score(pos, atom_pos), rep, cyc, moves,
                             moved, state.trace, state.flags)
 

@@ -444,3 +444,30 @@ def test_rank_by_searched_score_reorders_everything_downstream(tmp_path, monkeyp
         assert [int(r["sample"]) for r in _rows(files["scores.csv"])] == b.order.tolist()
         assert [int(r["sample"]) for r in _rows(files["modes.csv"])] == b.order.tolist()
         assert int(b.clusters.labels[0]) == 0
+
+
+def test_the_random_numbers_of_a_seed_are_those_of_the_two_earlier_functions():
+    """draw_random_numbers(c, rows, T, 0), its flexible alias and the n_sc > 0 block against the bit patterns that
+    search.draw_random_numbers and search_flex.draw_random_numbers_flex gave for this seed before they became one function."""
+    from diffdock_pocket_amd import search_flex as SF
+    c = SE.SearchConfig(cycles=2, seed=1234, sigma_tr=0.75, sigma_rot=0.25, sigma_tor=0.5, sigma_chi=0.125)
+    rigid_p = [-1112827513, -1094799157, 1039825712, -1100892598, 1012713075, 1043012234, -1124836471, -1099998236, -1104850829, 1059698811,
+               -1089364555, -1111696319, -1112584649, -1095535664, 1042557945, -1090335686, 1058627640, -1114783505, -1090037706, -1093854668,
+               1033110668, 1039847514, -1102757193, -1095350298, -1107097606, -1081337046, 1042904919, 1031547265, -1096182928, 1043492177,
+               -1096172058, 1058774508, -1081114095, 1059661056, -1084076830, -1100015028, -1106163031, -1114771255, -1081361206, 1044107434,
+               1060379116, 1002445074, -1099887749, -1097593117, 1055629625, -1098761416, 1058803731, 1034156101]
+    rigid_u = [4589775617074355296, 4582122549441411424, 4602154245079702742, 4599424220006214562, 4606104959535090931, 4602067004820807288]
+    flex_p = [-1112827513, -1094799157, 1039825712, -1100892598, 1012713075, 1043012234, -1124836471, -1099998236, -1126405308, 1038240591,
+              -1089364555, -1098013391, -1098679639, -1095535664, 1034169337, -1098724294, 1053589579, -1120075457, -1112246882, -1102243276,
+              1046349522, 1052515396, -1097600503, -1103738906, -1121012402, -1095053597, 1038218356, 1039935873, -1104571536, 1035103569,
+              -1090609959, 1063873762, -1081114095, 1046578859, -1097409044, -1100015028, -1097774423, -1106382647, -1098138422, 1027330218,
+              1060379116, 1002445074, -1099887749, -1097593117, -1114103260, -1094394824, -1090310585, -1102999223, 1038941556, 1038924002,
+              1040986104, -1117624761, 1062836917, 1046066523, 1049023867, 1035797751, 1023449886, -1104622819, -1100610801, 1038053628]
+    flex_u = [4602717274791769084, 4598699351991666856, 4602485700219835424, 4601236618024812176, 4607034778996619500, 4594794340142202592]
+    for draw, args, want_p, want_u in ((SE.draw_random_numbers, (c, 3, 2), rigid_p, rigid_u), (SE.draw_random_numbers, (c, 3, 2, 0), rigid_p, rigid_u),
+                                       (SF.draw_random_numbers_flex, (c, 3, 2, 0), rigid_p, rigid_u),
+                                       (SF.draw_random_numbers_flex, (c, 3, 2, 2), flex_p, flex_u), (SE.draw_random_numbers, (c, 3, 2, 2), flex_p, flex_u)):
+        p, u = draw(*args)
+        assert p.dtype == torch.float32 and u.dtype == torch.float64 and p.is_contiguous() and u.is_contiguous()
+        assert tuple(p.shape) == (2, 3, 8 + (args[3] if len(args) > 3 else 0)) and tuple(u.shape) == (2, 3)
+        assert p.view(torch.int32).flatten().tolist() == want_p and u.view(torch.int64).flatten().tolist() == want_u

@@ -1,9 +1,12 @@
-"""python tools/descent_bits.py [out.json]  (needs an MI355X; profiles/descent_bits.json and profiles/pose_family_bits.json, DESIGN.md
-4.16 and 4.23)
+"""python tools/descent_bits.py [out.json]  (needs an MI355X; profiles/descent_bits.json, profiles/pose_family_bits.json and
+profiles/pose_family_loop_bits.json)
 SHA-256 of every output tensor's bytes of the entries that share csrc/ddp_pose_descent.h and csrc/ddp_horn.h, and of the rest of the
-pose family (ddp_pose_profile, ddp_pose_minimize_flex, ddp_clash_guidance), on seeded inputs only: the 3dpf fixture of tests/golden,
-synthetic ragged shapes and the small cases of tests/pose_form_cases.py at the default and at a non-default score form.  Run once per
-library (DDP_HIP_LIB selects one) in a fresh process; two libraries compute the same bits iff their digest lists are equal."""
+pose family (ddp_pose_profile, ddp_pose_minimize_flex, ddp_clash_guidance, ddp_pose_search, ddp_pose_search_select,
+ddp_pose_search_flex, ddp_score_guidance, ddp_score_guidance_flex with every intermediate state and the start poses), on seeded inputs
+only: the 3dpf fixture of tests/golden, synthetic ragged shapes, the small cases of tests/pose_form_cases.py at the default and at a
+non-default score form, and the small shapes of the searches' and the guidance terms' GPU tests through those tests' own launch
+helpers.  Run once per library (DDP_HIP_LIB selects one) in a fresh process; two libraries compute the same bits iff their digest
+lists are equal."""
 import hashlib
 import json
 import os
@@ -148,6 +151,57 @@ for fused in (True, False):
     r = mz.minimize(xd, history=h, fused=fused)
     put(f"PoseMinimizer.minimize fused={fused}", r.lig_pos, r.energy_before, r.energy_after, r.scores_before.terms, r.scores_before.total,
         r.scores_after.terms, r.scores_after.intra, r.scores_after.total, r.rmsd_moved, r.accepted, torch.stack(h))
+
+# ---- the searches and the score guidance, at the small shapes and through the launch helpers of their GPU tests
+import score_guidance_ref as SGR
+import test_gpu_score_guidance as GSG
+import test_gpu_score_guidance_flex as GSGF
+import test_gpu_search as GS
+import test_gpu_search_flex as GSF
+from test_minimize_cpu import chain_case
+from test_score_guidance_flex_cpu import CASES as FLEX_GUIDANCE_CASES, case as flex_guidance_case
+
+
+def put_state(name, st):
+    put(name, *(st[k] for k in sorted(st) if st[k] is not None))
+
+
+# ddp_pose_search, ddp_pose_search_select: 2 poses x 3 replicas x 4 cycles x 6 iterations, whole and as 1 + 3 cycles
+for n, T in ((1, 0), (12, 1), (37, 5)):
+    case = [a.to(dev) for a in chain_case(2, n, T, 1025, 31 + n + T)]
+    p, u = GS._numbers(4, 6, T, 7, dev)
+    for k in (0.0, 0.3):
+        whole = GS._search(case, 3, 6, p, u, starts=True, k=k)
+        a = GS._search(case, 3, 6, p[:1], u[:1], starts=True, k=k)
+        b = GS._search(case, 3, 6, p[1:], u[1:], a, cycle0=1, starts=True, k=k)
+        for tag, st in (("4", whole), ("1", a), ("1+3", b)):
+            put_state(f"pose_search n{n} T{T} k={k} cycles={tag}", st)
+        put(f"pose_search_select n{n} T{T} k={k}", *LA.pose_search_select(whole["best_pos"], whole["best_e"], whole["best_cycle"], 3))
+# ddp_pose_search_flex: the shapes of test_one_cycle_of_one_replica_is_ddp_pose_minimize_flex, 3 replicas x 4 cycles x 6 iterations
+TILE = GSF.TILE
+for S, n, m, n_mov, n_sc, T, seed, opt in ((3, 5, TILE - 1, 4, 1, 2, 1059, {}), (3, 37, TILE + 1, 5, 17, 5, 1093, dict(moving_at=[TILE - 1, TILE])),
+                                           (3, 5, TILE - 1, 4, 0, 2, 1059, {})):
+    t = GSF._case(S, n, m, n_mov, n_sc, T, seed, dev, **opt)
+    p, u = GSF._numbers(4, 3 * S, T, n_sc, 7, dev)
+    kw = dict(starts=True, k=0.1, k_sc=0.1)
+    whole = GSF._search(t, 3, 6, p, u, **kw)
+    a = GSF._search(t, 3, 6, p[:1], u[:1], **kw)
+    b = GSF._search(t, 3, 6, p[1:], u[1:], a, cycle0=1, **kw)
+    for tag, st in (("4", whole), ("1", a), ("1+3", b)):
+        put_state(f"pose_search_flex n{n} m{m} mov{n_mov} sc{n_sc} cycles={tag}", st)
+# ddp_score_guidance: shared and per-sample receptor, capped and uncapped samples in one launch (the weight of the case does that)
+for n in (1, 37, 256):
+    for m in (0, 1, 1025):
+        for T in ((0,) if n == 1 else (0, 5)):
+            for per_sample in (False, True):
+                c = SGR.random_case(4, n, m, T, seed=77 + 1000 * n + m + T, per_sample_rec=per_sample, with_pairs=True)
+                upd, e, g = GSG._launch(c, c["w"], c["caps"], c["upd0"])
+                put(f"score_guidance n{n} m{m} T{T} per_sample={per_sample} capped={c['ref']['capped'].tolist()}", *upd, e, g)
+# ddp_score_guidance_flex: the cases of its tests
+for shape in FLEX_GUIDANCE_CASES:
+    c = flex_guidance_case(shape)
+    upd, upd_sc, e, gm, _ = GSGF._launch(c, c["w"])
+    put(f"score_guidance_flex {shape}", *upd, upd_sc, e, gm)
 torch.cuda.synchronize()
 dst = sys.argv[1] if len(sys.argv) > 1 else "descent_bits.json"
 with open(dst, "w") as f:
