@@ -9,8 +9,8 @@ against, and let g = dE/dx be the fp64 gradient of E = E_cross + E_self of refin
 (assets/vdw_radii.json), overlap = OVERLAP_DISTANCE and receptor hydrogens ignored.
 
  1. Per-step weight.  w_t = clash_guidance_weight if t <= clash_guidance_t_max, else 0 (the weight as the fp32 value that travels in
-    the step's device parameter block).  A per-step constant: it is NOT multiplied by g^2 dt, so more inference steps mean more
-    total guidance.
+    the step's device parameter block, slot sampler.P_W_CLASH).  A per-step constant: it is NOT multiplied by g^2 dt, so more
+    inference steps mean more total guidance.
  2. Direction.  (d_tr, d_rot, d_tor) = descent.direction_torch(x, g) * w_t, rounded to fp32: exactly what ddp_refine_direction
     writes for step[s] = w_t.
  3. Cap factor.  f_s = min(1, max_tr / |d_tr|_2, max_rot / |d_rot|_2, max_tor / max_b |d_tor[b]|), in fp64 from those fp32 values; a

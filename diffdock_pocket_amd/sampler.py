@@ -10,9 +10,16 @@ the N samples in PyTorch-ROCm instead of a per-sample numpy/scipy loop.  North-s
 
 Random numbers are drawn for ALL n_total samples of the job from one seeded CPU generator and sliced by
 `sample_slice`, so results do not depend on how samples are sharded over GPUs.
+
+A step's arithmetic is written once and read by both forms of the step.  `step_plan` is the only place of sigma, g, lam, dt, the last-step
+rule and the guidance weights; `Sampler._draw_noise` is the only place the step's noise leaves the generator.  The CPU step
+(`Sampler.step`, PyTorch) applies the plan's coefficients itself; the device step writes plan and noise into one row of the parameter
+block (`_fill_step_row`, slots P_* below), copies it (`_upload_step`) and launches `_step_body`, whose kernels read it on the device.
+`_run_steps` is the run loop of `Sampler` and `PipelinedSampler`.
 """
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
@@ -156,8 +163,7 @@ def record_trajectory_hip(lig_pos, lig_traj, slot_dev, atom_pos=None, moving_i32
 
 def torsion_tables(g):
     """(bonds [T,2] (u,v), mask_rotate [T,n] bool) of a complex graph's ligand, on the host: the rotatable bonds are the ligand edges
-    flagged by edge_mask, in edge order: the statements of Sampler.__init__ below, for callers without a sampler
-    (refine.PoseRefiner)."""
+    flagged by edge_mask, in edge order (Sampler.__init__, refine.PoseRefiner)."""
     em = g["ligand"].edge_mask.bool()
     bonds = g["ligand", "ligand"].edge_index.t()[em].clone()
     mr = g["ligand"].mask_rotate
@@ -237,6 +243,92 @@ class SamplerConfig:
             raise ValueError(f"score_guidance_max_sc must not be negative or NaN, got {self.score_guidance_max_sc!r}")
 
 
+@dataclass(frozen=True)
+class StepPlan:
+    """Every host-side number of one denoising step: update_k = coef[2 k] * score_k + coef[2 k + 1] * z_k for k = tr, rot, tor, sc."""
+    t: float
+    dt: float
+    noise_off: bool        # no_random, or the last step with no_final_step_noise: z = 0 and nothing is drawn
+    g2dt: tuple            # g_k^2 dt [4], without the low-temperature and ODE factors (SVGD reads the first three)
+    coef: tuple            # a_tr b_tr a_rot b_rot a_tor b_tor a_sc b_sc
+    w_clash: float         # w_t of guidance.py / score_guidance.py as the fp32 value the device reads; 0.0 when the term is off
+    w_score: float
+
+
+def step_plan(cfg: SamplerConfig, t_idx: int, schedule) -> StepPlan:
+    """The plan of step t_idx of `schedule` (reference utils/sampling.py:125-193, 215-225): the only place where sigma, g, lam, dt and
+    the last-step rule are written."""
+    from .guidance import step_weight
+    sg, last = cfg.sigma, t_idx == len(schedule) - 1
+    t = float(schedule[t_idx])
+    dt = t if last else float(schedule[t_idx] - schedule[t_idx + 1])
+    g2dt, coef = [], []
+    for k, (lo, hi, two) in enumerate(((sg.tr_sigma_min, sg.tr_sigma_max, True), (sg.rot_sigma_min, sg.rot_sigma_max, False),
+                                       (sg.tor_sigma_min, sg.tor_sigma_max, True),
+                                       (sg.sidechain_tor_sigma_min, sg.sidechain_tor_sigma_max, True))):
+        sigma = lo ** (1 - t) * hi ** t
+        g = sigma * math.sqrt(2 * math.log(hi / lo)) if two else 2 * sigma * math.sqrt(math.log(hi / lo))
+        gd = g ** 2 * dt           # first, as Python associates g ** 2 * dt * (...) from the left: the bits of every product below
+        temp, psi = cfg.temp_sampling[k], cfg.temp_psi[k]
+        if cfg.ode:
+            a, b = 0.5 * gd, 0.0   # = 0.5 * g ** 2 * dt bit for bit: scaling by 0.5 is exact
+        elif temp != 1.0:
+            sigma_data = math.exp(cfg.temp_sigma_data * math.log(hi) + (1 - cfg.temp_sigma_data) * math.log(lo))
+            lam = (sigma_data + sigma) / (sigma_data + sigma / temp)
+            a, b = gd * (lam + temp * psi / 2), g * math.sqrt(dt * (1 + psi))
+        else:
+            a, b = gd, g * math.sqrt(dt)
+        g2dt.append(gd)
+        coef += [a, b]
+    return StepPlan(t, dt, cfg.no_random or (cfg.no_final_step_noise and last), tuple(g2dt), tuple(coef),
+                    step_weight(cfg.clash_guidance_weight, t, cfg.clash_guidance_t_max) if cfg.clash_guidance_weight > 0 else 0.0,
+                    step_weight(cfg.score_guidance_weight, t, cfg.score_guidance_t_max) if cfg.score_guidance_weight > 0 else 0.0)
+
+
+# Slots of the step's device parameter block (Sampler.params, one fp32 row per step): written by _fill_step_row, read on the device
+# through these views by the launches of _step_body.  Slot 7 is free; the noise follows from P_NOISE on (Sampler._off).
+P_T = slice(0, 1)            # diffusion time: the batch's time tensors are stride-0 views of it
+P_SLOT = slice(1, 2)         # trajectory slot t_idx + 1 of ddp_traj_record (exact as a float); 0 without record_trajectory
+P_G2DT = slice(2, 5)         # g^2 dt of tr, rot, tor, read by ddp_svgd_rows; 0 without SVGD
+P_W_CLASH = slice(5, 6)      # w_t of ddp_clash_guidance; 0 without it
+P_W_SCORE = slice(6, 7)      # w_t of ddp_score_guidance / ddp_score_guidance_flex; 0 without it
+P_COEF = slice(8, 16)        # StepPlan.coef, read by ddp_sde_update
+P_NOISE = 16
+
+
+def _add_increments(upd, inc):
+    """(tr, rot, tor) updates plus a guidance term's increments; a term that is off (inc None) and a component that is off (None) add
+    nothing."""
+    return upd if inc is None else [None if u is None else u + d for u, d in zip(upd, inc)]
+
+
+def _run_steps(smp, schedule):
+    """The run loop of Sampler and PipelinedSampler: every step of the schedule, the once-per-run h2 range check with its recovery, the
+    overflow check; returns the final poses."""
+    model = smp.model
+    snap = smp.snapshot() if smp.on_hip else None
+    for i in range(len(schedule)):
+        smp.step(i, schedule)
+    if smp.on_hip and hasattr(model, "range_flag_raised"):
+        # The fp16 hi/lo form of the fc products is not total (|v| > 65504 cannot be split); its kernels report such a value through a
+        # flag in pinned host memory.  One check per run: a raised flag puts the job back to its first step (poses, noise stream) and
+        # runs it again in the exact fp32 MFMA form - a new capture, the model's switch restored afterwards.
+        torch.cuda.synchronize(smp.device)
+        if model.range_flag_raised():
+            model.__dict__["h2_recoveries"] = model.__dict__.get("h2_recoveries", 0) + 1
+            prev = model.conv_h2
+            model.conv_h2 = False          # (bumps the packed epoch: the captured step is dropped and recaptured)
+            try:
+                smp.restore(snap)
+                for i in range(len(schedule)):
+                    smp.step(i, schedule)
+                torch.cuda.synchronize(smp.device)
+            finally:
+                model.conv_h2 = prev
+    smp.check_overflow()
+    return smp.lig_pos, smp.atom_pos
+
+
 class Sampler:
     """Holds the device-resident batch of `n_local` samples of one complex (samples `sample_slice` of `n_total`)."""
 
@@ -249,10 +341,8 @@ class Sampler:
         self.gen = torch.Generator().manual_seed(seed)
         g = complex_graph
         self.n_l, self.n_a = g["ligand"].pos.shape[0], g["atom"].pos.shape[0]
-        em = g["ligand"].edge_mask.bool()
-        self.bonds = g["ligand", "ligand"].edge_index.t()[em].clone()             # [T,2] (u,v)
-        mr = g["ligand"].mask_rotate
-        self.mask_rotate = torch.as_tensor(np.asarray(mr if isinstance(mr, np.ndarray) else mr[0])).bool().to(device)
+        self.bonds, mask_rotate = torsion_tables(g)                               # [T,2] (u,v), [T,n] bool
+        self.mask_rotate = mask_rotate.to(device)
         self.rot_idx = rotate_index_lists(self.mask_rotate)
         self.T = int(self.bonds.shape[0])
         self.bonds_i32 = self.bonds.to(torch.int32).contiguous().to(device)
@@ -279,6 +369,10 @@ class Sampler:
         self.lig_traj = self.atom_traj = None
         if cfg.record_trajectory:
             self._init_trajectory()
+        # layout of a row of the parameter block (host arithmetic only): the noise of tr, rot, tor, side chains behind the P_* slots
+        n, T = self.n, (0 if cfg.no_torsion else self.T)
+        self._off = {"z_tr": P_NOISE, "z_rot": P_NOISE + 3 * n, "z_tor": P_NOISE + 6 * n, "z_sc": P_NOISE + 6 * n + n * T}
+        self._n_par = P_NOISE + 6 * n + n * T + n * self.S
         if self.on_hip:
             self._init_step_buffers()
         self.svgd = cfg.svgd_weight > 0
@@ -303,11 +397,6 @@ class Sampler:
             self.guid_ws = guidance.GuidanceWorkspace(self.guid_tables, self.device, cfg.clash_guidance_max_tr, cfg.clash_guidance_max_rot,
                                                       cfg.clash_guidance_max_tor)
 
-    def _guidance_weight(self, t: float) -> float:
-        """w_t of guidance.py: the weight while t <= clash_guidance_t_max, else 0."""
-        from .guidance import step_weight
-        return step_weight(self.cfg.clash_guidance_weight, t, self.cfg.clash_guidance_t_max)
-
     # -- physics-score guidance (SamplerConfig.score_guidance_weight > 0; score_guidance.py) -------------------------
     def _init_score_guidance(self, g):
         """The host tables (once; a ligand above the kernel's limits raises here) and, on a HIP device, the workspace of the one
@@ -325,11 +414,6 @@ class Sampler:
                                                                       cfg.score_guidance_max_sc)
         elif self.on_hip:
             self.sguid_ws = score_guidance.ScoreGuidanceWorkspace(self.sguid_tables, self.device, self.sguid_caps)
-
-    def _score_guidance_weight(self, t: float) -> float:
-        """w_t of score_guidance.py: the weight while t <= score_guidance_t_max, else 0."""
-        from .score_guidance import step_weight
-        return step_weight(self.cfg.score_guidance_weight, t, self.cfg.score_guidance_t_max)
 
     # -- SVGD particle interaction (SamplerConfig.svgd_weight > 0; svgd.py) ------------------------------------------
     def _init_svgd(self, g):
@@ -353,25 +437,15 @@ class Sampler:
                                               w_tor=cfg.svgd_tor_rel_weight, svgd_only=cfg.svgd_only)
 
     def _svgd_gdt(self, t_idx, schedule):
-        """[g_tr^2 dt, g_rot^2 dt, g_tor^2 dt] of a step: the diffusion coefficients of _step_coefficients, without the
-        low-temperature and ODE factors (reference utils/sampling.py:215,219,225)."""
-        sg, steps = self.cfg.sigma, len(schedule)
-        t = float(schedule[t_idx])
-        dt = float(schedule[t_idx] - schedule[t_idx + 1]) if t_idx < steps - 1 else float(schedule[t_idx])
-        out = []
-        for lo, hi, two in ((sg.tr_sigma_min, sg.tr_sigma_max, True), (sg.rot_sigma_min, sg.rot_sigma_max, False),
-                            (sg.tor_sigma_min, sg.tor_sigma_max, True)):
-            sigma = lo ** (1 - t) * hi ** t
-            g = sigma * math.sqrt(2 * math.log(hi / lo)) if two else 2 * sigma * math.sqrt(math.log(hi / lo))
-            out.append(g ** 2 * dt)
-        return out
+        """[g_tr^2 dt, g_rot^2 dt, g_tor^2 dt] of a step, from its plan (an accessor the GPU tests of SVGD call)."""
+        return list(step_plan(self.cfg, t_idx, schedule).g2dt[:3])
 
     # -- reverse-process trajectory (SamplerConfig.record_trajectory) ----------------------------------------------
     def _init_trajectory(self):
         """lig_traj [n, inference_steps + 1, n_lig, 3] and, with flexible side chains, atom_traj [n, inference_steps + 1, n_moving,
         3] (the moving atoms = the sorted unique side-chain subcomponents, `moving_atoms`), pocket-centred fp32.  Slot 0 holds the
         poses the first step starts from (written by `randomize` / `restore`), slot t + 1 the poses after step t.  On a HIP device
-        the steps record through ddp_traj_record inside the step (captured with it): its slot is params[1] = t_idx + 1."""
+        the steps record through ddp_traj_record inside the step (captured with it): its slot is params[P_SLOT] = t_idx + 1."""
         n_slots = self.cfg.inference_steps + 1
         self.lig_traj = torch.zeros(self.n, n_slots, self.n_l, 3, device=self.device)
         self.moving_atoms = None
@@ -407,18 +481,17 @@ class Sampler:
         changes, so it can be captured once and replayed."""
         dev, n = self.device, self.n
         T, S_ = (self.T if not self.cfg.no_torsion else 0), self.S
-        self._off = {"t": 0, "coef": 8, "z_tr": 16, "z_rot": 16 + 3 * n, "z_tor": 16 + 6 * n, "z_sc": 16 + 6 * n + n * T}
-        self._n_par = 16 + 6 * n + n * T + n * S_
         self.params = torch.zeros(self._n_par, device=dev)
         o = self._off
-        self.t_dev = self.params[0:1]
-        self.coef = self.params[o["coef"]:o["coef"] + 8]
+        self.t_dev = self.params[P_T]
+        self.coef = self.params[P_COEF]
         self.z_tr = self.params[o["z_tr"]:o["z_tr"] + 3 * n].view(n, 3)
         self.z_rot = self.params[o["z_rot"]:o["z_rot"] + 3 * n].view(n, 3)
         self.z_tor = self.params[o["z_tor"]:o["z_tor"] + n * T].view(n, T) if T > 0 else None
         self.z_sc = self.params[o["z_sc"]:o["z_sc"] + n * S_].view(n, S_) if S_ > 0 else None
         self.upd = {"tr": torch.zeros(n, 3, device=dev), "rot": torch.zeros(n, 3, device=dev),
                     "tor": torch.zeros(n, T, device=dev) if T > 0 else None, "sc": torch.zeros(n, S_, device=dev) if S_ > 0 else None}
+        self._upd3 = (self.upd["tr"], self.upd["rot"], self.upd["tor"])      # what SVGD and the guidance launches add to
         self._views = {}
         self._pin = None
         self._bind_batch()
@@ -440,17 +513,24 @@ class Sampler:
         ts = (b["receptor"].node_t["tr"], b["atom"].node_t["tr"])
         b.ddp_time_hint = (tuple(id(t) for t in ts), tuple(t._version for t in ts), True)    # one time for all nodes (batch.set_time)
 
+    def _bind(self, t: float) -> HeteroBatch:
+        """The batch with the current poses and diffusion time t on it: on a HIP device views of the sampler's buffers, on the CPU
+        new tensors."""
+        b = self.batch
+        if self.on_hip:
+            self._bind_batch()
+            self.t_dev.fill_(t)
+        else:
+            b["ligand"].pos, b["atom"].pos = self.lig_pos.reshape(-1, 3), self.atom_pos.reshape(-1, 3)
+            set_time(b, t, t, t, t, device=self.device)
+        return b
+
     def scores(self, t: float):
         """The score model on the current poses at diffusion time t (no pose update)."""
         if not self.on_hip:
-            b = self.batch
-            b["ligand"].pos, b["atom"].pos = self.lig_pos.reshape(-1, 3), self.atom_pos.reshape(-1, 3)
-            set_time(b, t, t, t, t, device=self.device)
-            return self.model(b)
+            return self.model(self._bind(t))
         with torch.cuda.device(self.device):
-            self._bind_batch()
-            self.t_dev.fill_(t)
-            return self.model(self.batch)
+            return self.model(self._bind(t))
 
     def snapshot(self):
         """(poses, generator state): `restore` puts the sampler back there (bench.py warms up - and captures - on the timed
@@ -465,61 +545,42 @@ class Sampler:
             self._record()
 
     def _step_coefficients(self, t_idx, schedule):
-        """(t, [a_tr b_tr a_rot b_rot a_tor b_tor a_sc b_sc], noise on) of a step: update_k = a_k * score_k + b_k * z_k
-        (reference utils/sampling.py:125-193)."""
-        cfg, sg = self.cfg, self.cfg.sigma
-        steps = len(schedule)
-        t = float(schedule[t_idx])
-        dt = float(schedule[t_idx] - schedule[t_idx + 1]) if t_idx < steps - 1 else float(schedule[t_idx])
-        noise_off = cfg.no_random or (cfg.no_final_step_noise and t_idx == steps - 1)
-        coef = []
-        for k, (lo, hi, two) in enumerate(((sg.tr_sigma_min, sg.tr_sigma_max, True), (sg.rot_sigma_min, sg.rot_sigma_max, False),
-                                           (sg.tor_sigma_min, sg.tor_sigma_max, True),
-                                           (sg.sidechain_tor_sigma_min, sg.sidechain_tor_sigma_max, True))):
-            sigma = lo ** (1 - t) * hi ** t
-            g = sigma * math.sqrt(2 * math.log(hi / lo)) if two else 2 * sigma * math.sqrt(math.log(hi / lo))
-            if cfg.ode:
-                a, b = 0.5 * g ** 2 * dt, 0.0
-            elif cfg.temp_sampling[k] != 1.0:
-                sigma_data = math.exp(cfg.temp_sigma_data * math.log(hi) + (1 - cfg.temp_sigma_data) * math.log(lo))
-                lam = (sigma_data + sigma) / (sigma_data + sigma / cfg.temp_sampling[k])
-                a, b = g ** 2 * dt * (lam + cfg.temp_sampling[k] * cfg.temp_psi[k] / 2), g * math.sqrt(dt * (1 + cfg.temp_psi[k]))
-            else:
-                a, b = g ** 2 * dt, g * math.sqrt(dt)
-            coef += [a, b]
-        return t, coef, noise_off
+        """(t, [a_tr b_tr a_rot b_rot a_tor b_tor a_sc b_sc], noise off) of a step, from its plan (an accessor the GPU tests call)."""
+        plan = step_plan(self.cfg, t_idx, schedule)
+        return plan.t, list(plan.coef), plan.noise_off
 
-    def _upload_step(self, t_idx, schedule):
-        """Time, coefficients and noise of the step -> the device buffer: one asynchronous copy from a pinned row (_pinned_row; a
-        copy from pageable memory would make the host wait for the stream to drain).  Noise is drawn for ALL samples of the job from the seeded generator - in the
-        reference loop's order tr, rot, tor, side chains - and sliced to this shard."""
-        cfg, N, sl, n = self.cfg, self.n_total, self.slice, self.n
-        t, coef, noise_off = self._step_coefficients(t_idx, schedule)
-        host = self._pinned_row()
-        host[0] = t
-        host[1:8] = 0.0
+    def _draw_noise(self, noise_off: bool):
+        """The step's noise (z_tr [n, 3], z_rot [n, 3], z_tor [n, T] or None, z_sc [n, S] or None) as host tensors: drawn for ALL n_total
+        samples of the job from the seeded generator - in the reference loop's order tr, rot, tor, side chains - and sliced to this
+        shard.  With noise_off zeros, and nothing is drawn.  The only place a step reads the generator: the CPU and the device step see
+        the same stream."""
+        cfg, N = self.cfg, self.n_total
+        full = torch.zeros if noise_off else functools.partial(torch.randn, generator=self.gen)
+        cols = (3, 3, self.T if not cfg.no_torsion and self.T > 0 else None, self.S if self.has_flex else None)
+        return tuple(None if c is None else full((N, c))[self.slice] for c in cols)
+
+    def _fill_step_row(self, row, plan: StepPlan, noise, t_idx: int):
+        """Plan and noise of step t_idx -> `row`, one fp32 host row of the parameter block (slots P_*, then the noise at _off).  Host
+        arithmetic only.  A term that is off leaves its slot 0."""
+        row[P_T] = plan.t
+        row[P_T.stop:P_COEF.start] = 0.0
         if self.lig_traj is not None:
-            host[1] = t_idx + 1            # the trajectory slot of ddp_traj_record (exact as a float)
+            row[P_SLOT] = t_idx + 1
         if self.svgd:
-            host[2:5] = torch.tensor(self._svgd_gdt(t_idx, schedule), dtype=torch.float64).float()     # read by ddp_svgd_rows
+            row[P_G2DT] = torch.tensor(plan.g2dt[:3], dtype=torch.float64).float()
         if self.guidance:
-            host[5] = self._guidance_weight(t)                                                         # read by ddp_clash_guidance
+            row[P_W_CLASH] = plan.w_clash
         if self.score_guidance:
-            host[6] = self._score_guidance_weight(t)                                                   # read by ddp_score_guidance
-        host[8:16] = torch.tensor(coef, dtype=torch.float64).float()
-        o = self._off
+            row[P_W_SCORE] = plan.w_score
+        row[P_COEF] = torch.tensor(plan.coef, dtype=torch.float64).float()
+        for o, z in zip(self._off.values(), noise):
+            if z is not None:
+                row[o:o + z.numel()] = z.reshape(-1)
 
-        def z(shape, key, cols):
-            full = torch.zeros(shape) if noise_off else torch.randn(shape, generator=self.gen)
-            host[o[key]:o[key] + n * cols] = full[sl].reshape(-1)
-
-        z((N, 3), "z_tr", 3)
-        z((N, 3), "z_rot", 3)
-        if self.z_tor is not None:
-            z((N, self.T), "z_tor", self.T)
-        if self.z_sc is not None:
-            z((N, self.S), "z_sc", self.S)
-        self.params.copy_(host, non_blocking=True)
+    def _upload_step(self, row):
+        """The filled pinned row -> the device buffer: one asynchronous copy (a copy from pageable memory would make the host wait for
+        the stream to drain), and the event after which the row may be reused (_pinned_row)."""
+        self.params.copy_(row, non_blocking=True)
         self._pin_ev[self._pin_k].record()
 
     def _pinned_row(self):
@@ -561,18 +622,14 @@ class Sampler:
             a.score[k], a.z[k], a.out[k], a.n[k] = sc.data_ptr(), (0 if cfg.ode else zz.data_ptr()), out.data_ptr(), out.numel()
         st = torch._C._cuda_getCurrentRawStream(self.lig_pos.device.index)
         L.check(lib.ddp_sde_update(self.coef.data_ptr(), C.byref(a), st), "ddp_sde_update")
+        rec = self.atom_pos if self.has_flex else None      # each sample's own atoms, before this step's side-chain update
         if self.svgd:      # on the poses the scores were computed for, into the updates just written
-            self.svgd_ws.launch(self.lig_pos, (keep[0], keep[1], keep[2] if use_tor else None),
-                                (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[2:5])
-        if self.guidance:  # after SVGD (svgd_only does not erase it), against the receptor before this step's side-chain update
-            self.guid_ws.launch(self.lig_pos, self.atom_pos if self.has_flex else None,
-                                (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[5:6])
-        if self.score_guidance and self.score_guidance_sc:  # one launch for the ligand and the side-chain increments
-            self.sguid_ws.launch(self.lig_pos, self.atom_pos, (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None),
-                                 self.params[6:7], self.upd["sc"])
-        elif self.score_guidance:  # after clash guidance, on the same poses against the same receptor
-            self.sguid_ws.launch(self.lig_pos, self.atom_pos if self.has_flex else None,
-                                 (self.upd["tr"], self.upd["rot"], self.upd["tor"] if use_tor else None), self.params[6:7])
+            self.svgd_ws.launch(self.lig_pos, (keep[0], keep[1], keep[2] if use_tor else None), self._upd3, self.params[P_G2DT])
+        if self.guidance:  # after SVGD (svgd_only does not erase it)
+            self.guid_ws.launch(self.lig_pos, rec, self._upd3, self.params[P_W_CLASH])
+        if self.score_guidance:  # after clash guidance, on the same poses against the same receptor; with score_guidance_sc (a flexible
+            # run) the one launch of ddp_score_guidance_flex also adds the side-chain increments
+            self.sguid_ws.launch(self.lig_pos, rec, self._upd3, self.params[P_W_SCORE], *([self.upd["sc"]] if self.score_guidance_sc else []))
         if self.has_flex:
             L.check(lib.ddp_sidechain_update(self.atom_pos.data_ptr(), self.n, self.n_a, self.upd["sc"].data_ptr(), self.S,
                                              self.sc_edge_i32.data_ptr(), self.sc_sub_i32.data_ptr(), self.sc_map_i32.data_ptr(),
@@ -584,12 +641,14 @@ class Sampler:
                                     self.lig_pos.data_ptr(), st), "ddp_pose_update")
         torch.autograd.graph.increment_version(self.lig_pos)
         if self.lig_traj is not None:
-            self._record(self.params[1:2])
+            self._record(self.params[P_SLOT])
 
     def _step_hip(self, t_idx, schedule):
         with torch.cuda.device(self.device):
             self._bind_batch()
-            self._upload_step(t_idx, schedule)
+            plan, row = step_plan(self.cfg, t_idx, schedule), self._pinned_row()
+            self._fill_step_row(row, plan, self._draw_noise(plan.noise_off), t_idx)
+            self._upload_step(row)
             if self._graph and self._graph_epoch != getattr(self.model, "_packed_epoch", 0):
                 # the model dropped its packed weights / static caches (model.to(), load_state_dict, changed weights found by
                 # _refresh_weight_caches): the captured launches read memory that is no longer held - recapture from new state
@@ -628,9 +687,8 @@ class Sampler:
             self._graph = False
             torch.cuda.synchronize(self.device)
             # what the aborted capture left in the model's static-graph cache was never computed
-            for mdl in (self.model,):
-                if hasattr(mdl, "_static_cache"):
-                    mdl._static_cache = {}
+            if hasattr(self.model, "_static_cache"):
+                self.model._static_cache = {}
             self._step_body()
             return
         self._graph = g
@@ -732,102 +790,43 @@ class Sampler:
             self._check_slot(t_idx)
         if self.on_hip:
             return self._step_hip(t_idx, schedule)
-        cfg, sg, N, sl, dev = self.cfg, self.cfg.sigma, self.n_total, self.slice, self.device
-        steps = len(schedule)
-        t = float(schedule[t_idx])
-        dt = float(schedule[t_idx] - schedule[t_idx + 1]) if t_idx < steps - 1 else float(schedule[t_idx])
-        tr_s = sg.tr_sigma_min ** (1 - t) * sg.tr_sigma_max ** t
-        rot_s = sg.rot_sigma_min ** (1 - t) * sg.rot_sigma_max ** t
-        tor_s = sg.tor_sigma_min ** (1 - t) * sg.tor_sigma_max ** t
-        sc_s = sg.sidechain_tor_sigma_min ** (1 - t) * sg.sidechain_tor_sigma_max ** t
-
-        noise_off = cfg.no_random or (cfg.no_final_step_noise and t_idx == steps - 1)
-
-        def z(shape):  # drawn for all samples of the job, sliced to this shard
-            full = torch.zeros(shape) if noise_off else torch.randn(shape, generator=self.gen)
-            part = full[sl]
-            if torch.device(dev).type == "cuda":
-                # pinned staging + asynchronous copy: a copy from pageable memory makes the host wait until the stream has
-                # drained, i.e. for the previous step's conv layers - and everything the host could have queued behind them
-                # (time tensors, node encoders, the neighbour-search count passes) would start late
-                return part.contiguous().pin_memory().to(dev, non_blocking=True)
-            return part.to(dev)
-
-        # the step's noise does not depend on the scores: drawn (same generator order as the reference loop: tr, rot, tor,
-        # side chains) and uploaded before the model call, so that nothing between the model and the pose update waits
-        z_tr, z_rot = z((N, 3)), z((N, 3))
-        z_tor = z((N, self.T)) if (not cfg.no_torsion and self.T > 0) else None
-        z_sc = z((N, self.S)) if self.has_flex else None
-
-        b = self.batch
-        b["ligand"].pos = self.lig_pos.reshape(-1, 3)
-        b["atom"].pos = self.atom_pos.reshape(-1, 3)
-        set_time(b, t, t, t, t, device=dev)
-        tr_score, rot_score, tor_score, sc_score = self._call_model(self.model, b)
-        guid = None
-        if self.guidance:  # on the poses the scores were computed for, against the receptor before this step's side-chain update
+        cfg = self.cfg
+        plan = step_plan(cfg, t_idx, schedule)
+        noise = self._draw_noise(plan.noise_off)
+        use_tor = noise[2] is not None
+        tr_score, rot_score, tor_score, sc_score = self._call_model(self.model, self._bind(plan.t))
+        # the guidance terms, on the poses the scores were computed for, against the receptor before this step's side-chain update
+        lig, rec = self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else None
+        guid = sguid = sguid_sc = None
+        if self.guidance:
             from . import guidance
-            guid = guidance.increments_torch(self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else self.guid_tables.rec,
-                                             self.guid_tables, self._guidance_weight(t), cfg.clash_guidance_max_tr,
-                                             cfg.clash_guidance_max_rot, cfg.clash_guidance_max_tor)
-        sguid = sguid_sc = None
-        if self.score_guidance:  # the same poses and receptor; added after the clash increments
+            guid = guidance.increments_torch(lig, self.guid_tables.rec if rec is None else rec, self.guid_tables, plan.w_clash,
+                                             cfg.clash_guidance_max_tr, cfg.clash_guidance_max_rot, cfg.clash_guidance_max_tor)
+        if self.score_guidance:  # added after the clash increments
             from . import score_guidance
-            sguid = score_guidance.increments_torch(self.lig_pos.cpu(), self.atom_pos.cpu() if self.has_flex else self.sguid_tables.rec,
-                                                    self.sguid_tables, self._score_guidance_weight(t), self.sguid_caps)
+            sguid = score_guidance.increments_torch(lig, self.sguid_tables.rec if rec is None else rec, self.sguid_tables, plan.w_score,
+                                                    self.sguid_caps)
             if self.score_guidance_sc:  # the side chains' increments, on the same pose and receptor
-                sguid_sc = score_guidance.increments_sc_torch(self.lig_pos.cpu(), self.atom_pos.cpu(), self.sguid_tables, self.sguid_sc_tables,
-                                                              self._score_guidance_weight(t), cfg.score_guidance_max_sc)
+                sguid_sc = score_guidance.increments_sc_torch(lig, rec, self.sguid_tables, self.sguid_sc_tables, plan.w_score,
+                                                              cfg.score_guidance_max_sc)
 
-        def perturb(score, g, sigma, lo, hi, k, zz):
-            if cfg.ode:
-                return 0.5 * g ** 2 * dt * score
-            if cfg.temp_sampling[k] != 1.0:
-                sigma_data = math.exp(cfg.temp_sigma_data * math.log(hi) + (1 - cfg.temp_sigma_data) * math.log(lo))
-                lam = (sigma_data + sigma) / (sigma_data + sigma / cfg.temp_sampling[k])
-                return (g ** 2 * dt * (lam + cfg.temp_sampling[k] * cfg.temp_psi[k] / 2) * score
-                        + g * math.sqrt(dt * (1 + cfg.temp_psi[k])) * zz)
-            return g ** 2 * dt * score + g * math.sqrt(dt) * zz
+        def sde(k, score):  # a_k * score_k + b_k * z_k: one Python float times an fp32 tensor per term, as ddp_sde_update's coef
+            a, b = plan.coef[2 * k:2 * k + 2]
+            return a * score if cfg.ode else a * score + b * noise[k]
 
-        tr_g = tr_s * math.sqrt(2 * math.log(sg.tr_sigma_max / sg.tr_sigma_min))
-        rot_g = 2 * rot_s * math.sqrt(math.log(sg.rot_sigma_max / sg.rot_sigma_min))
-        tr_p = perturb(tr_score, tr_g, tr_s, sg.tr_sigma_min, sg.tr_sigma_max, 0, z_tr)
-        rot_p = perturb(rot_score, rot_g, rot_s, sg.rot_sigma_min, sg.rot_sigma_max, 1, z_rot)
-        tor_p = None
-        if not cfg.no_torsion and self.T > 0:
-            tor_g = tor_s * math.sqrt(2 * math.log(sg.tor_sigma_max / sg.tor_sigma_min))
-            tor_p = perturb(tor_score.reshape(self.n, self.T), tor_g, tor_s, sg.tor_sigma_min, sg.tor_sigma_max, 2, z_tor)
+        upd = [sde(0, tr_score), sde(1, rot_score), sde(2, tor_score.reshape(self.n, self.T)) if use_tor else None]
         if self.has_flex:
-            sc_g = sc_s * math.sqrt(2 * math.log(sg.sidechain_tor_sigma_max / sg.sidechain_tor_sigma_min))
-            sc_p = perturb(sc_score.reshape(self.n, self.S), sc_g, sc_s, sg.sidechain_tor_sigma_min,
-                           sg.sidechain_tor_sigma_max, 3, z_sc)
+            sc_p = sde(3, sc_score.reshape(self.n, self.S))
             if sguid_sc is not None:
-                sc_p = sc_p + sguid_sc.to(dev)
-            if self.atom_pos.is_cuda:
-                self.atom_pos = apply_sidechain_torsions_hip(self.atom_pos, self.sc_edge_i32, self.sc_sub_i32, self.sc_map_i32, sc_p)
-            else:
-                self.atom_pos = apply_sidechain_torsions(self.atom_pos, self.sc_edge_idx, self.sc_sub, self.sc_map, sc_p)
+                sc_p = sc_p + sguid_sc
+            self.atom_pos = apply_sidechain_torsions(self.atom_pos, self.sc_edge_idx, self.sc_sub, self.sc_map, sc_p)
         if self.svgd:
             from . import svgd
-            gdt = self._svgd_gdt(t_idx, schedule)
-            tot = svgd.totals(self.lig_pos, self.svgd_dih, tr_score, rot_score, tor_score if tor_p is not None else None, gdt,
+            tot = svgd.totals(self.lig_pos, self.svgd_dih, tr_score, rot_score, tor_score if use_tor else None, plan.g2dt,
                               cfg.svgd_repulsive_weight, cfg.svgd_rot_rel_weight, cfg.svgd_tor_rel_weight)
-            tr_p = cfg.svgd_weight * tot[0] + (0 if cfg.svgd_only else tr_p)
-            rot_p = cfg.svgd_weight * tot[1] + (0 if cfg.svgd_only else rot_p)
-            if tor_p is not None:
-                tor_p = cfg.svgd_weight * tot[2] + (0 if cfg.svgd_only else tor_p)
-        if guid is not None:
-            tr_p, rot_p = tr_p + guid[0].to(dev), rot_p + guid[1].to(dev)
-            if tor_p is not None:
-                tor_p = tor_p + guid[2].to(dev)
-        if sguid is not None:
-            tr_p, rot_p = tr_p + sguid[0].to(dev), rot_p + sguid[1].to(dev)
-            if tor_p is not None:
-                tor_p = tor_p + sguid[2].to(dev)
-        if self.lig_pos.is_cuda:   # one HIP launch; the PyTorch form below is the same arithmetic (CPU tests)
-            self.lig_pos = modify_conformer_hip(self.lig_pos, tr_p, rot_p, tor_p, self.bonds_i32, self.mask_u8)
-        else:
-            self.lig_pos = modify_conformer(self.lig_pos, tr_p, rot_p, tor_p, self.bonds, self.rot_idx)
+            upd = [None if u is None else cfg.svgd_weight * x + (0 if cfg.svgd_only else u) for x, u in zip(tot, upd)]
+        upd = _add_increments(_add_increments(upd, guid), sguid)
+        self.lig_pos = modify_conformer(self.lig_pos, *upd, self.bonds, self.rot_idx)
         if self.lig_traj is not None:
             self._record(slot=t_idx + 1)
 
@@ -861,14 +860,7 @@ class Sampler:
         """Runs the confidence model (TensorProductScoreModel(confidence_mode=True)) on the final poses at t = 0 and
         returns (confidence [n] or [n, k], order) with `order` = sample indices from most to least confident (for a
         multi-output head the reference ranks by the first column, inference.py:213-216)."""
-        b = self.batch
-        if self.on_hip:     # the batch's poses and times are views of the sampler's device buffers
-            self._bind_batch()
-            self.t_dev.zero_()
-        else:
-            b["ligand"].pos = self.lig_pos.reshape(-1, 3)
-            b["atom"].pos = self.atom_pos.reshape(-1, 3)
-            set_time(b, 0.0, 0.0, 0.0, 0.0, device=self.device)
+        b = self._bind(0.0)
         conf = self._call_model(confidence_model, b)
         if self.on_hip and hasattr(confidence_model, "check_overflow"):
             # a truncated ligand<-atom list is reported for THIS complex, before its scores are ranked (the flag is written by the
@@ -888,27 +880,7 @@ class Sampler:
             # replays never enter the model's Python forward: the value check (param.data.copy_, EMA) is made here, and a change
             # drops the packed weights -> the epoch test in _step_hip recaptures
             self.model._refresh_weight_caches()
-        snap = self.snapshot() if self.on_hip else None
-        for i in range(len(schedule)):
-            self.step(i, schedule)
-        if self.on_hip and hasattr(self.model, "range_flag_raised"):
-            # The fp16 hi/lo form of the fc products is not total (|v| > 65504 cannot be split); its kernels report such a value through a
-            # flag in pinned host memory.  One check per run: a raised flag puts the job back to its first step (poses, noise stream) and
-            # runs it again in the exact fp32 MFMA form - a new capture, the model's switch restored afterwards.
-            torch.cuda.synchronize(self.device)
-            if self.model.range_flag_raised():
-                self.model.__dict__["h2_recoveries"] = self.model.__dict__.get("h2_recoveries", 0) + 1
-                prev = self.model.conv_h2
-                self.model.conv_h2 = False          # (bumps the packed epoch: the captured step is dropped and recaptured)
-                try:
-                    self.restore(snap)
-                    for i in range(len(schedule)):
-                        self.step(i, schedule)
-                    torch.cuda.synchronize(self.device)
-                finally:
-                    self.model.conv_h2 = prev
-        self.check_overflow()
-        return self.lig_pos, self.atom_pos
+        return _run_steps(self, schedule)
 
     def check_overflow(self):
         """Raises if the ligand<-atom list of a step queued so far was truncated (model.la_capacity_per_atom).  Inside a replayed
@@ -1035,27 +1007,7 @@ class PipelinedSampler:
 
     def run(self, schedule: Optional[np.ndarray] = None):
         schedule = get_t_schedule(self.parts[0].cfg.inference_steps) if schedule is None else schedule
-        snap = self.snapshot() if self.on_hip else None
-        for i in range(len(schedule)):
-            self.step(i, schedule)
-        if self.on_hip and hasattr(self.model, "range_flag_raised"):
-            # The fp16 hi/lo form of the fc products is not total (|v| > 65504 cannot be split); its kernels report such a value through a
-            # flag in pinned host memory.  One check per run: a raised flag puts the job back to its first step (poses, noise stream) and
-            # runs it again in the exact fp32 MFMA form - a new capture, the model's switch restored afterwards.
-            torch.cuda.synchronize(self.device)
-            if self.model.range_flag_raised():
-                self.model.__dict__["h2_recoveries"] = self.model.__dict__.get("h2_recoveries", 0) + 1
-                prev = self.model.conv_h2
-                self.model.conv_h2 = False          # (bumps the packed epoch: the captured step is dropped and recaptured)
-                try:
-                    self.restore(snap)
-                    for i in range(len(schedule)):
-                        self.step(i, schedule)
-                    torch.cuda.synchronize(self.device)
-                finally:
-                    self.model.conv_h2 = prev
-        self.check_overflow()
-        return self.lig_pos, self.atom_pos
+        return _run_steps(self, schedule)
 
     def check_overflow(self):
         """Raises if a ligand<-atom list of any group's steps was truncated (see Sampler.check_overflow)."""

@@ -10,7 +10,7 @@ against, and let g = dE/dx be the fp64 gradient of E(x) = inter(x, rec) + intra(
 0, not divided by the torsion factor, with the ScoreConfig form, the typing, the cutoff and the NaN rule of scoring.py.
 
  1. Per-step weight.  w_t = score_guidance_weight if t <= score_guidance_t_max, else 0 (the weight as the fp32 value that travels in
-    the step's device parameter block, params[6]).  A per-step constant: it is NOT multiplied by g^2 dt, exactly as clash guidance,
+    the step's device parameter block, slot sampler.P_W_SCORE).  A per-step constant: it is NOT multiplied by g^2 dt, exactly as clash guidance,
     so more inference steps mean more total guidance.
  2. Direction.  (d_tr, d_rot, d_tor) = descent.direction_torch(x, g) * w_t, rounded to fp32: exactly what ddp_refine_direction
     writes for step[s] = w_t on this gradient.
@@ -26,7 +26,7 @@ against, and let g = dE/dx be the fp64 gradient of E(x) = inter(x, rec) + intra(
 
 Side chains (SamplerConfig.score_guidance_sidechains, off by default; a flexible run only, otherwise a no-op).  The ligand part above
 is unchanged - the ligand increments of a flexible run are exactly what they are without the flag.  For sample s of a flexible run at
-a step with w_t > 0 (the same w_t, the same params[6]), with x as above and y the sample's current atom_pos, before this step's
+a step with w_t > 0 (the same w_t, the same slot), with x as above and y the sample's current atom_pos, before this step's
 side-chain update:
 
  S1. Gradient.  g_y = dE/dy_a over the moving atoms Mv of E(x, y) = inter(x, y) + intra(x) + sc(y): the joint energy of
