@@ -474,8 +474,10 @@ __global__ __launch_bounds__(256) void ddp_flex_mark_kernel(const float* __restr
   auto off = [&](int x) {   // node x = (s, j) of the b kind (atoms)
     if (flag) return flag[x] != 0;
     const int x0 = x - s * n_b_per_graph;
-    return pos[3 * (size_t)x] != pos[3 * (size_t)x0] || pos[3 * (size_t)x + 1] != pos[3 * (size_t)x0 + 1] ||
-           pos[3 * (size_t)x + 2] != pos[3 * (size_t)x0 + 2];
+    bool d = false;   // bit patterns, not values: -0.0 against +0.0 is a difference (and a NaN equals its own copy)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d = d || __float_as_uint(pos[3 * (size_t)x + c]) != __float_as_uint(pos[3 * (size_t)x0 + c]);
+    return d;
   };
   const int ai = a[e], bi = b[e];
   bool m = off(bi);
