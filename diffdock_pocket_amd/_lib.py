@@ -27,7 +27,7 @@ DDP_SCORE_GUIDANCE_FLEX_MAX_MOVING, DDP_SCORE_GUIDANCE_FLEX_MAX_BONDS = DDP_MINI
 DDP_PAIRWISE_MAX_SAMPLES, DDP_CLUSTER_MAX_SAMPLES = 32768, 1024
 EXPORTS = ["ddp_conv_messages", "ddp_conv_rows", "ddp_stage_a_gh", "ddp_stage_a_gh3", "ddp_segment_reduce", "ddp_edge_featurize", "ddp_edge_featurize_jobs", "ddp_torsion_sh", "ddp_stage_a", "ddp_stage_a_h2",
            "ddp_pose_update", "ddp_sidechain_update", "ddp_sde_update", "ddp_radius_count", "ddp_radius_fill", "ddp_knn", "ddp_group_by_key", "ddp_node_linear", "ddp_scan_jobs", "ddp_mark_jobs", "ddp_rowcopy_jobs", "ddp_select_jobs",
-           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_score_guidance", "ddp_score_guidance_flex", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pose_search", "ddp_pose_search_select", "ddp_pose_search_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_conv_deal_tile", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
+           "ddp_gather_rows", "ddp_clean_pair_maps", "ddp_flex_mark", "ddp_fallback_rowmap", "ddp_step_prologue", "ddp_trrot_head", "ddp_tor_head", "ddp_radius_search_jobs", "ddp_group_by_key_jobs", "ddp_front_lists", "ddp_set_occupancy_shaping", "ddp_pose_rmsd", "ddp_pose_contacts", "ddp_pose_pairwise_rmsd", "ddp_pose_cluster", "ddp_traj_record", "ddp_svgd_tau", "ddp_svgd_pairs", "ddp_svgd_rows", "ddp_refine_energy", "ddp_refine_direction", "ddp_refine_accept", "ddp_clash_guidance", "ddp_score_guidance", "ddp_score_guidance_flex", "ddp_pose_score", "ddp_pose_profile", "ddp_pose_minimize", "ddp_pose_minimize_flex", "ddp_pose_search", "ddp_pose_search_select", "ddp_pose_search_flex", "ddp_pocket_occupancy", "ddp_pocket_buriedness", "ddp_pocket_label", "ddp_conv_deal_tile", "ddp_abi_version", "ddp_last_error", "ddp_source_hash"]
 
 
 class Seg(C.Structure):
@@ -221,6 +221,34 @@ class GroupJob(C.Structure):
                 ("out_key", _P), ("out", _P * 3), ("key_map", _P), ("scratch", _P)]
 
 
+DDP_FRONT_MAX_LIG, DDP_FRONT_MAX_REC, DDP_FRONT_MAX_ATOM, DDP_FRONT_MAX_BONDS = 64, 256, 2048, 256
+
+
+class FrontView(C.Structure):
+    """ddp_front_view_t of include/ddp_hip.h."""
+    _fields_ = [("rowptr", _P), ("perm", _P), ("key", _P), ("out0", _P), ("out1", _P)]
+
+
+class FrontLists(C.Structure):
+    """ddp_front_lists_t of include/ddp_hip.h."""
+    _fields_ = [("n_graphs", _I), ("n_lig", _I), ("n_rec", _I), ("n_atom", _I), ("n_tor", _I),
+                ("max_lig", _I), ("max_rec", _I), ("max_atom", _I), ("max_tor", _I), ("max_bonds", _I),
+                ("lig_pos", _P), ("rec_pos", _P), ("atom_pos", _P), ("tor_pos", _P),
+                ("lig_ptr", _P), ("rec_ptr", _P), ("atom_ptr", _P), ("tor_ptr", _P),
+                ("r_lig", C.c_float), ("r_cross", C.c_float), ("cross_div", _P),
+                ("ll_neighbors", _I), ("tor_neighbors", _I), ("cross_neighbors", _I), ("la_neighbors", _I),
+                ("radius_flags", _I), ("e_bond", _I),
+                ("ll0", _P), ("ll1", _P), ("cap_ll", _I), ("cnt_ll", _P),
+                ("lr0", _P), ("lr1", _P), ("cap_lr", _I), ("cnt_lr", _P),
+                ("la0", _P), ("la1", _P), ("cap_la", _I), ("cnt_la", _P), ("overflow", _P),
+                ("tor_q", _P), ("tor_x", _P), ("cap_tor", _I), ("cnt_tor", _P),
+                ("touched", _P), ("near_rows", _P), ("cnt_near", _P),
+                ("rp_lr", _P), ("rp_la", _P), ("rp_tor", _P),
+                ("c_ll", FrontView), ("c_la", FrontView), ("c_lr", FrontView),
+                ("so_ll", FrontView), ("so_la", FrontView), ("so_lr", FrontView),
+                ("scratch", _P)]
+
+
 
 DDP_MAX_FEATURIZE_JOBS = 8
 
@@ -346,6 +374,8 @@ def load():
                       ("ddp_select_jobs", SelectJob), ("ddp_radius_search_jobs", RadiusJob), ("ddp_group_by_key_jobs", GroupJob)):
         getattr(lib, name).argtypes = [C.POINTER(job), C.c_int, C.c_void_p]
         getattr(lib, name).restype = C.c_int
+    lib.ddp_front_lists.argtypes = [C.POINTER(FrontLists), C.POINTER(C.c_int32), C.c_void_p]
+    lib.ddp_front_lists.restype = C.c_int
     lib.ddp_sde_update.argtypes = [C.c_void_p, C.POINTER(SdeArgs), C.c_void_p]
     lib.ddp_sde_update.restype = C.c_int
     lib.ddp_gather_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]

@@ -14,9 +14,9 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["ddp_conv.hip", "ddp_conv_rows.hip", "ddp_conv_rows16.hip", "ddp_misc.hip", "ddp_gemm.hip", "ddp_pose.hip", "ddp_graph.hip", "ddp_views.hip", "ddp_lists.hip", "ddp_node.hip", "ddp_heads.hip",
+SOURCES = ["ddp_conv.hip", "ddp_conv_rows.hip", "ddp_conv_rows16.hip", "ddp_misc.hip", "ddp_gemm.hip", "ddp_pose.hip", "ddp_graph.hip", "ddp_views.hip", "ddp_lists.hip", "ddp_front_lists.hip", "ddp_node.hip", "ddp_heads.hip",
            "ddp_eval.hip", "ddp_traj.hip", "ddp_svgd.hip", "ddp_refine.hip", "ddp_guidance.hip", "ddp_score_guidance.hip", "ddp_score_guidance_flex.hip", "ddp_score.hip", "ddp_profile.hip", "ddp_minimize.hip", "ddp_minimize_flex.hip", "ddp_search.hip", "ddp_search_flex.hip", "ddp_pockets.hip", "ddp_capi.hip"]
-HEADERS = [os.path.join(HERE, "csrc", "ddp_internal.h"), os.path.join(HERE, "csrc", "ddp_conv_diag.h"), os.path.join(HERE, "csrc", "ddp_conv_common.h"), os.path.join(HERE, "csrc", "ddp_conv_deal.h"), os.path.join(HERE, "csrc", "ddp_conv_rows_common.h"), os.path.join(HERE, "csrc", "ddp_horn.h"), os.path.join(HERE, "csrc", "ddp_pockets_uf.h"), os.path.join(HERE, "csrc", "ddp_score_pair.h"), os.path.join(HERE, "csrc", "ddp_pose_descent.h"), os.path.join(HERE, "csrc", "ddp_minimize_loop.h"), os.path.join(HERE, "csrc", "ddp_minimize_flex_loop.h"), os.path.join(HERE, "csrc", "ddp_clash_energy.h"),
+HEADERS = [os.path.join(HERE, "csrc", "ddp_internal.h"), os.path.join(HERE, "csrc", "ddp_conv_diag.h"), os.path.join(HERE, "csrc", "ddp_conv_common.h"), os.path.join(HERE, "csrc", "ddp_conv_deal.h"), os.path.join(HERE, "csrc", "ddp_conv_rows_common.h"), os.path.join(HERE, "csrc", "ddp_horn.h"), os.path.join(HERE, "csrc", "ddp_pockets_uf.h"), os.path.join(HERE, "csrc", "ddp_score_pair.h"), os.path.join(HERE, "csrc", "ddp_pose_descent.h"), os.path.join(HERE, "csrc", "ddp_minimize_loop.h"), os.path.join(HERE, "csrc", "ddp_minimize_flex_loop.h"), os.path.join(HERE, "csrc", "ddp_clash_energy.h"), os.path.join(HERE, "csrc", "ddp_radius_math.h"),
            os.path.join(ROOT, "include", "ddp_hip.h")]
 OUT = os.path.join(HERE, "libddp_hip.so")
 OBJ_DIR = os.path.join(HERE, "csrc", ".obj")

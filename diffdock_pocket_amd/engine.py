@@ -74,6 +74,17 @@ class LazyStats(Mapping):
         return len(self._resolve())
 
 
+def front_lists_fusable(m, S):
+    """Whether a step's pose-dependent lists go through ddp_front_lists: the switch is on, the run is rigid (flexible runs add the
+    side-chain graph and rebuild the atom kNN views every step, which the fused form does not cover) and the batch's largest sample
+    lies inside the entry's limits (include/ddp_hip.h; the entry checks the same and declines, but by then its arrays are allocated)."""
+    if not m.fused_front_lists or S.num_flex != 0 or S.sc is not None:
+        return False
+    big = lambda lay: max(lay.counts_host) if lay.counts_host else 0      # noqa: E731
+    return (big(S.lay_l) <= L.DDP_FRONT_MAX_LIG and big(S.lay_r) <= L.DDP_FRONT_MAX_REC and big(S.lay_a) <= L.DDP_FRONT_MAX_ATOM
+            and S.max_bonds <= L.DDP_FRONT_MAX_BONDS and (S.tor is None or big(S.tor.lay) <= L.DDP_FRONT_MAX_LIG))
+
+
 def _i32(t):
     return t.to(torch.int32).contiguous()
 
@@ -213,6 +224,14 @@ class ForwardEngine:
         S.bond_ei = bond_ei
         S.bond32 = m._cached("bond32", (bond_ei,), lambda: (_i32(bond_ei[0]), _i32(bond_ei[1])))
         S.E_bond = int(bond_ei.shape[1])
+
+        def bond_stats():   # most bond entries of one ligand; a bond across two graphs (never built by the loaders) rules the fused lists out
+            if S.E_bond == 0:
+                return 0
+            gb = lbatch[bond_ei[0].long()]
+            same = bool((gb == lbatch[bond_ei[1].long()]).all())
+            return int(torch.bincount(gb, minlength=B).max()) if same else 1 << 30
+        S.max_bonds = m._cached("max_bonds", (bond_ei, lig.batch), bond_stats)
         rr, ar = data["receptor", "receptor"].edge_index, data["atom", "receptor"].edge_index
         S.rr, S.ar = rr, ar
         S.num_flex = 0
@@ -333,6 +352,71 @@ class ForwardEngine:
         L.check(L.load().ddp_step_prologue(C.byref(a), K.stream()), "ddp_step_prologue")
         F.keep_pro = (keep, a)
 
+    def _search_chain(self, S, F, dev, ll0, ll1, lr0, lr1, la0, la1, cut, b32_l, b32_a):
+        """The pose-dependent neighbour searches as a chain of list calls: one batched count / scan / fill sequence + the near rows."""
+        m = self.m
+        Nl, Nr, Na, Eb = S.Nl, S.Nr, S.Na, S.E_bond
+        lpos, rpos, apos, cnt = F.lpos, F.rpos, F.apos, F.cnt
+        ptr_l, ptr_r, ptr_a = S.lay_l._ptr32, S.lay_r._ptr32, S.lay_a._ptr32
+        i32e = lambda n: torch.empty(n, dtype=torch.int32, device=dev)      # noqa: E731
+        jobs = [K.radius_job(lpos, ptr_l, lpos, b32_l, m.lig_max_radius, 33, _DROP_SELF, i32e(Nl), i32e(Nl + 1), base=Eb,
+                             total=cnt["ll"], out_query=ll1, out_x=ll0, capacity=S.cap_ll)]
+        if m.dynamic_max_cross:     # (:548-556) both point sets divided by 3 sigma_tr + 20, searched with r = 1
+            jobs.append(K.radius_job(rpos, ptr_r, lpos, b32_l, 1.0, 10000, 0, i32e(Nl), i32e(Nl + 1), total=cnt["lr"],
+                                     out_query=lr0, out_x=lr1, capacity=S.cap_lr, graph_div=cut))
+        else:
+            jobs.append(K.radius_job(rpos, ptr_r, lpos, b32_l, m.cross_max_distance, 10000, 0, i32e(Nl), i32e(Nl + 1), total=cnt["lr"],
+                                     out_query=lr0, out_x=lr1, capacity=S.cap_lr))
+        jobs.append(K.radius_job(apos, ptr_a, lpos, b32_l, m.lig_max_radius, 10000, 0, i32e(Nl), i32e(Nl + 1), total=cnt["la"],
+                                 out_query=la0, out_x=la1, capacity=S.cap_la, overflow=m.overflow_flag(dev)))
+        # atoms with a ligand atom of their graph within the radius = the sources of ligand<-atom edges = the atoms an
+        # atom<-ligand message reaches ("touched"): the same search with the roles swapped, count pass only
+        jobs.append(K.radius_job(lpos, ptr_l, apos, b32_a, m.lig_max_radius, 10000, 0, F.touched))
+        for name, st, pos, ptr_x in (("tor", S.tor, lpos, ptr_l), ("sc", S.sc, apos, ptr_a)):
+            if st is None:
+                continue
+            # build_bond_conv_graph / build_sidechain_conv_graph (:586-636): atoms around the bond centres, default cap 32
+            h = getattr(F, name)      # (bond centres and directions: ddp_step_prologue)
+            h.q, h.x = i32e(st.cap), i32e(st.cap)
+            jobs.append(K.radius_job(pos, ptr_x, h.bond_pos, G._batch32(st.lay, st.T), m.lig_max_radius, 32, 0, i32e(st.T),
+                                     i32e(st.T + 1), total=cnt[name], out_query=h.q, out_x=h.x, capacity=st.cap))
+            setattr(F, name, h)
+        K.radius_search_jobs(jobs)
+        F.keep += [jobs, cut]
+        K.scan_jobs([K.scan_job(Na, flag=F.touched, lst=F.near_rows, total=cnt["near"])])
+
+    def _fused_lists(self, S, F, dev, ll0, ll1, lr0, lr1, la0, la1, cut):
+        """ddp_front_lists for the rigid step: the searches, the near rows and both grouping calls.  Returns the views' arrays, or None
+        when the batch lies outside the fused form's limits (nothing was written)."""
+        m = self.m
+        Nl, Nr, Na, cnt = S.Nl, S.Nr, S.Na, F.cnt
+        i32e = lambda n: torch.empty(n, dtype=torch.int32, device=dev)      # noqa: E731
+
+        def view(n_keys, cap, o1=False):
+            return SimpleNamespace(rp=i32e(n_keys + 1), perm=i32e(cap), key=i32e(cap), o0=i32e(cap), o1=i32e(cap) if o1 else None)
+        V = SimpleNamespace(c_ll=view(Nl, S.cap_ll), c_la=view(Na, S.cap_la), c_lr=view(Nr, S.cap_lr), so_ll=view(Nl, S.cap_ll, True),
+                            so_la=view(Nl, S.cap_la, True), so_lr=view(Nl, S.cap_lr, True), rp_lr=i32e(Nl + 1), rp_la=i32e(Nl + 1))
+        h, tor, T, max_t = F.tor, None, 0, 0
+        if h is not None:
+            st = h.st
+            T, max_t = st.T, max(st.lay.counts_host)
+            h.q, h.x, h.rp = i32e(st.cap), i32e(st.cap), i32e(T + 1)
+            tor = (h.q, h.x, st.cap, cnt["tor"], h.rp)
+        scratch = i32e(8 * S.B)
+        maxes = (max(S.lay_l.counts_host), max(S.lay_r.counts_host), max(S.lay_a.counts_host), max_t, S.max_bonds)
+        taken = K.front_lists(
+            n_graphs=S.B, sizes=(Nl, Nr, Na, T), maxes=maxes, pos=(F.lpos, F.rpos, F.apos, h.bond_pos if h is not None else None),
+            ptrs=(S.lay_l._ptr32, S.lay_r._ptr32, S.lay_a._ptr32, h.st.lay._ptr32 if h is not None else None),
+            r_lig=m.lig_max_radius, r_cross=1.0 if cut is not None else m.cross_max_distance, cross_div=cut, neighbors=(33, 32, 10000, 10000),
+            e_bond=S.E_bond, ll=(ll0, ll1, S.cap_ll, cnt["ll"]), lr=(lr0, lr1, S.cap_lr, cnt["lr"]),
+            la=(la0, la1, S.cap_la, cnt["la"], m.overflow_flag(dev)), tor=tor, touched=F.touched, near_rows=F.near_rows,
+            cnt_near=cnt["near"], rp_lr=V.rp_lr, rp_la=V.rp_la,
+            views={k: getattr(V, k) for k in ("c_ll", "c_la", "c_lr", "so_ll", "so_la", "so_lr")}, scratch=scratch)
+        if not taken:
+            return None
+        F.keep += [V, scratch, cut]
+        return V
+
     # ================================================================================================ front
     def _front(self, data, S, lig, rec, atom, dev, mark, ff=None):
         m = self.m
@@ -375,35 +459,15 @@ class ForwardEngine:
         F.aa = aa
         S.stats["E_aa"] = int(aa.shape[1])
         lr0, lr1, la0, la1 = i32e(S.cap_lr), i32e(S.cap_lr), i32e(S.cap_la), i32e(S.cap_la)
-        jobs = [K.radius_job(lpos, ptr_l, lpos, b32_l, m.lig_max_radius, 33, _DROP_SELF, i32e(Nl), i32e(Nl + 1), base=Eb,
-                             total=cnt["ll"], out_query=ll1, out_x=ll0, capacity=S.cap_ll)]
-        cut = None
-        if m.dynamic_max_cross:     # (:548-556) both point sets divided by 3 sigma_tr + 20, searched with r = 1
-            cut = F.cut
-            jobs.append(K.radius_job(rpos, ptr_r, lpos, b32_l, 1.0, 10000, 0, i32e(Nl), i32e(Nl + 1), total=cnt["lr"],
-                                     out_query=lr0, out_x=lr1, capacity=S.cap_lr, graph_div=cut))
-        else:
-            jobs.append(K.radius_job(rpos, ptr_r, lpos, b32_l, m.cross_max_distance, 10000, 0, i32e(Nl), i32e(Nl + 1), total=cnt["lr"],
-                                     out_query=lr0, out_x=lr1, capacity=S.cap_lr))
-        jobs.append(K.radius_job(apos, ptr_a, lpos, b32_l, m.lig_max_radius, 10000, 0, i32e(Nl), i32e(Nl + 1), total=cnt["la"],
-                                 out_query=la0, out_x=la1, capacity=S.cap_la, overflow=m.overflow_flag(dev)))
-        # atoms with a ligand atom of their graph within the radius = the sources of ligand<-atom edges = the atoms an
-        # atom<-ligand message reaches ("touched"): the same search with the roles swapped, count pass only
-        F.touched = i32e(Na)
-        jobs.append(K.radius_job(lpos, ptr_l, apos, b32_a, m.lig_max_radius, 10000, 0, F.touched))
-        for name, st, pos, ptr_x in (("tor", S.tor, lpos, ptr_l), ("sc", S.sc, apos, ptr_a)):
-            if st is None:
-                continue
-            # build_bond_conv_graph / build_sidechain_conv_graph (:586-636): atoms around the bond centres, default cap 32
-            h = getattr(F, name)      # (bond centres and directions: ddp_step_prologue)
-            h.q, h.x = i32e(st.cap), i32e(st.cap)
-            jobs.append(K.radius_job(pos, ptr_x, h.bond_pos, G._batch32(st.lay, st.T), m.lig_max_radius, 32, 0, i32e(st.T),
-                                     i32e(st.T + 1), total=cnt[name], out_query=h.q, out_x=h.x, capacity=st.cap))
-            setattr(F, name, h)
-        K.radius_search_jobs(jobs)
-        F.keep = [jobs, cut]
-        F.near_rows = i32e(Na)
-        K.scan_jobs([K.scan_job(Na, flag=F.touched, lst=F.near_rows, total=cnt["near"])])
+        F.touched, F.near_rows = i32e(Na), i32e(Na)
+        cut = F.cut if m.dynamic_max_cross else None
+        F.keep = []
+        # one workgroup per sample builds every pose-dependent list and view of the rigid step in two launches (ddp_front_lists);
+        # outside its limits (None) the chain of list calls below runs
+        fv = self._fused_lists(S, F, dev, ll0, ll1, lr0, lr1, la0, la1, cut) if front_lists_fusable(m, S) else None
+        S.stats["front_fused"] = int(fv is not None)
+        if fv is None:
+            self._search_chain(S, F, dev, ll0, ll1, lr0, lr1, la0, la1, cut, b32_l, b32_a)
         mark("searches")
 
         # ---- which receptor-side work is the same in every graph (sampling batch: N poses of ONE complex at one time)
@@ -481,21 +545,26 @@ class ForwardEngine:
         c[5] = static_csr("c_ar", 5, S.ar, S.ar[0], S.ar[1], Na)
         c[6] = static_csr("c_rr", 6, rr, rr[0], rr[1], Nr)
         c[8] = static_csr("c_ra", 8, S.ar, S.ar[1], S.ar[0], Nr)
-        v = SimpleNamespace(rp=i32e(Nl + 1), perm=i32e(S.cap_ll), key=i32e(S.cap_ll), o0=i32e(S.cap_ll))
-        g1.append(K.group_job(ll0, S.cap_ll, Nl, [ll1], v.rp, v.perm, v.key, [v.o0], i32e(Nl + S.cap_ll), n_dev=cnt["ll"]))
+        v = fv.c_ll if fv is not None else SimpleNamespace(rp=i32e(Nl + 1), perm=i32e(S.cap_ll), key=i32e(S.cap_ll), o0=i32e(S.cap_ll))
+        if fv is None:
+            g1.append(K.group_job(ll0, S.cap_ll, Nl, [ll1], v.rp, v.perm, v.key, [v.o0], i32e(Nl + S.cap_ll), n_dev=cnt["ll"]))
         c[0] = EdgeView(S.cap_ll, v.key, v.o0, v.perm, rowptr=v.rp, cnt=cnt["ll"])
         for k, q0, x1, cap, name in ((1, lr0, lr1, S.cap_lr, "lr"), (2, la0, la1, S.cap_la, "la")):
-            rp = i32e(Nl + 1)       # (query-major search output: already grouped by the receiving ligand atom)
-            g1.append(K.group_job(q0, cap, Nl, [], rp, scratch=i32e(Nl), n_dev=cnt[name]))
+            # (query-major search output: already grouped by the receiving ligand atom)
+            rp = getattr(fv, "rp_" + name) if fv is not None else i32e(Nl + 1)
+            if fv is None:
+                g1.append(K.group_job(q0, cap, Nl, [], rp, scratch=i32e(Nl), n_dev=cnt[name]))
             c[k] = EdgeView(cap, q0, x1, G.iota32(cap, dev), rowptr=rp, cnt=cnt[name])
         for k, key, pay, cap, n_keys, name in ((4, la1, la0, S.cap_la, Na, "la"), (7, lr1, lr0, S.cap_lr, Nr, "lr")):
-            v = SimpleNamespace(rp=i32e(n_keys + 1), perm=i32e(cap), key=i32e(cap), o0=i32e(cap))
-            g1.append(K.group_job(key, cap, n_keys, [pay], v.rp, v.perm, v.key, [v.o0], i32e(n_keys + cap), n_dev=cnt[name]))
+            v = getattr(fv, "c_" + name) if fv is not None else SimpleNamespace(rp=i32e(n_keys + 1), perm=i32e(cap), key=i32e(cap), o0=i32e(cap))
+            if fv is None:
+                g1.append(K.group_job(key, cap, n_keys, [pay], v.rp, v.perm, v.key, [v.o0], i32e(n_keys + cap), n_dev=cnt[name]))
             c[k] = EdgeView(cap, v.key, v.o0, v.perm, rowptr=v.rp, cnt=cnt[name])
         for h, name in ((F.tor, "tor"), (F.sc, "sc")):
             if h is not None:
-                h.rp = i32e(h.st.T + 1)
-                g1.append(K.group_job(h.q, h.st.cap, h.st.T, [], h.rp, scratch=i32e(h.st.T), n_dev=cnt[name]))
+                if fv is None:
+                    h.rp = i32e(h.st.T + 1)
+                    g1.append(K.group_job(h.q, h.st.cap, h.st.T, [], h.rp, scratch=i32e(h.st.T), n_dev=cnt[name]))
                 h.csr = EdgeView(h.st.cap, h.q, h.x, G.iota32(h.st.cap, dev), rowptr=h.rp, cnt=cnt[name])
         K.group_jobs(g1)
         F.keep.append(g1)
@@ -521,9 +590,12 @@ class ForwardEngine:
                 g2.append(K.group_job(c[3].src, E3, Na, [c[3].recv, c[3].eid], v.rp, v.perm, v.key, [v.o0, v.o1], i32e(Na + E3)))
                 so[3] = G.SourceOrder(E3, v.o0, v.key, v.o1, v.perm)
             for k, cap, name in ((0, S.cap_ll, "ll"), (4, S.cap_la, "la"), (7, S.cap_lr, "lr")):
-                v = SimpleNamespace(rp=i32e(Nl + 1), perm=i32e(cap), key=i32e(cap), o0=i32e(cap), o1=i32e(cap))
-                g2.append(K.group_job(c[k].src, cap, Nl, [c[k].recv, c[k].eid], v.rp, v.perm, v.key, [v.o0, v.o1], i32e(Nl + cap),
-                                      n_dev=cnt[name]))
+                if fv is not None:
+                    v = getattr(fv, "so_" + name)
+                else:
+                    v = SimpleNamespace(rp=i32e(Nl + 1), perm=i32e(cap), key=i32e(cap), o0=i32e(cap), o1=i32e(cap))
+                    g2.append(K.group_job(c[k].src, cap, Nl, [c[k].recv, c[k].eid], v.rp, v.perm, v.key, [v.o0, v.o1], i32e(Nl + cap),
+                                          n_dev=cnt[name]))
                 so[k] = EdgeView(cap, v.o0, v.key, v.o1, pos=v.perm, cnt=cnt[name])
             K.group_jobs(g2)
             F.keep.append(g2)

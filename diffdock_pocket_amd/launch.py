@@ -576,6 +576,38 @@ def group_jobs(jobs: Sequence[L.GroupJob]):
     _run_jobs("ddp_group_by_key_jobs", L.GroupJob, list(jobs), "ddp_group_by_key_jobs")
 
 
+def front_lists(*, n_graphs, sizes, maxes, pos, ptrs, r_lig, r_cross, cross_div, neighbors, e_bond, ll, lr, la, tor, touched, near_rows,
+                cnt_near, rp_lr, rp_la, views, scratch, flags=0) -> bool:
+    """ddp_front_lists: the step's pose-dependent edge lists and their views in two launches.  sizes / maxes: (lig, rec, atom, tor)
+    node totals and largest per-graph sizes, maxes with the largest per-graph bond-entry count as fifth; pos / ptrs: (lig, rec, atom,
+    tor) coordinates and graph pointers (tor None: no torsion graph); ll / lr: (query array, point array, capacity, count) in the
+    argument order of the struct, la with the overflow flag as fifth, tor: (q, x, capacity, count, rowptr) or None; views: name ->
+    namespace with rp / perm / key / o0 / o1; scratch: int32 [8 * n_graphs].  False: outside the fused form's limits, nothing was
+    written and the caller runs the chain of radius_search_jobs / scan_jobs / group_jobs."""
+    a = L.FrontLists()
+    a.n_graphs = n_graphs
+    a.n_lig, a.n_rec, a.n_atom, a.n_tor = sizes
+    a.max_lig, a.max_rec, a.max_atom, a.max_tor, a.max_bonds = maxes
+    a.lig_pos, a.rec_pos, a.atom_pos, a.tor_pos = (_p(t) for t in pos)
+    a.lig_ptr, a.rec_ptr, a.atom_ptr, a.tor_ptr = (_p(t) for t in ptrs)
+    a.r_lig, a.r_cross, a.cross_div = float(r_lig), float(r_cross), _p(cross_div)
+    a.ll_neighbors, a.tor_neighbors, a.cross_neighbors, a.la_neighbors = neighbors
+    a.radius_flags, a.e_bond = int(flags), int(e_bond)
+    a.ll0, a.ll1, a.cap_ll, a.cnt_ll = _p(ll[0]), _p(ll[1]), int(ll[2]), _p(ll[3])
+    a.lr0, a.lr1, a.cap_lr, a.cnt_lr = _p(lr[0]), _p(lr[1]), int(lr[2]), _p(lr[3])
+    a.la0, a.la1, a.cap_la, a.cnt_la, a.overflow = _p(la[0]), _p(la[1]), int(la[2]), _p(la[3]), _p(la[4])
+    if tor is not None:
+        a.tor_q, a.tor_x, a.cap_tor, a.cnt_tor, a.rp_tor = _p(tor[0]), _p(tor[1]), int(tor[2]), _p(tor[3]), _p(tor[4])
+    a.touched, a.near_rows, a.cnt_near, a.rp_lr, a.rp_la = _p(touched), _p(near_rows), _p(cnt_near), _p(rp_lr), _p(rp_la)
+    for name, v in views.items():
+        f = getattr(a, name)
+        f.rowptr, f.perm, f.key, f.out0, f.out1 = _p(v.rp), _p(v.perm), _p(v.key), _p(v.o0), _p(getattr(v, "o1", None))
+    a.scratch = _p(scratch)
+    taken = C.c_int32(0)
+    L.check(L.load().ddp_front_lists(C.byref(a), C.byref(taken), stream()), "ddp_front_lists")
+    return bool(taken.value)
+
+
 def gather_rows(x, idx, n, out, ncols, n_dev=None):
     lib = L.load()
     if n > 0:

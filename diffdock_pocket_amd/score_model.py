@@ -489,6 +489,7 @@ class TensorProductScoreModel(nn.Module):
         # than the per-edge MFMA work it replaces).  0 disables it (every conv on the direct path).
         self.factorize_min_degree = 3.0
         self.prune_last_receptor_layer = True   # layer L-2 receptor-side convs only where the final layer reads them
+        self.fused_front_lists = True  # the step's pose-dependent edge lists in two launches (ddp_front_lists), within its limits
         self.share_layer0 = True       # layer-0 receptor-side convs once per batch of identical receptors (forward)
         self.share_clean_layer1 = True  # layer-1 atom<-atom messages between atoms no ligand message has reached: once (forward)
         self.share_flex_layer0 = True   # flexible side chains: layer-0 atom-side convs per sample only where an atom moved nearby

@@ -658,6 +658,83 @@ typedef struct {
 } ddp_group_job_t;
 int ddp_group_by_key_jobs(const ddp_group_job_t* jobs, int njobs, void* stream);
 
+/* ---- the pose-dependent edge lists of a step's front in two launches (csrc/ddp_front_lists.hip): one workgroup per sample
+ * graph builds the sample's match matrices as bit masks in LDS; counts, offsets and every view follow from popcounts and
+ * prefix sums over them.  Launch 1 writes one total per (sample, list), launch 2 sums the totals of the earlier samples for
+ * its offsets and writes everything.  The result is, bit for bit, what this chain of the entries above produces:
+ *   ddp_radius_search_jobs { ligand radius graph behind the e_bond bond entries of ll0 / ll1 (DDP_RADIUS_DROP_SELF, first
+ *     ll_neighbors in index order), ligand x receptor (both sides divided by cross_div[g] when given), ligand x atom (with
+ *     the overflow flag), the role-swapped count `touched`, bond centres x ligand atoms (first tor_neighbors) }
+ *   ddp_scan_jobs { near_rows = the atoms with touched != 0 }
+ *   ddp_group_by_key_jobs { c_ll = ll by ll0; row pointers of lr by lr0, la by la0, tor by tor_q; c_la = la by la1;
+ *     c_lr = lr by lr1 }, each with the device-side count of its list
+ *   ddp_group_by_key_jobs { so_x = c_x grouped by its payload out0 with the payloads (key, perm) } for x = ll, la, lr
+ * A view's arrays are those of ddp_group_by_key (rowptr [n_keys + 1], perm / key / out0 / out1 [capacity]); so_x.rowptr may
+ * be NULL.  Words behind a list's count keep their content.  ll0 / ll1 [0, e_bond) are inputs (a bond lies inside one graph).
+ * Limits of the fused form, per sample graph: DDP_FRONT_MAX_LIG ligand atoms and as many torsion bonds, DDP_FRONT_MAX_REC
+ * receptor nodes, DDP_FRONT_MAX_ATOM atoms, DDP_FRONT_MAX_BONDS bond entries; cross_neighbors / la_neighbors must not bind
+ * (>= max_rec / max_atom).  Outside them - or with DDP_RADIUS_NEAREST in radius_flags - nothing is launched or written and
+ * *taken = 0: the caller runs the chain above.  tor_pos == NULL or n_tor == 0: no torsion graph.  max_* are trusted (the graph
+ * pointers live on the device); a sample that exceeds them all the same writes nothing out of bounds: no lists, zero totals.
+ * scratch: int32 [8 * n_graphs]. */
+#define DDP_FRONT_MAX_LIG 64
+#define DDP_FRONT_MAX_REC 256
+#define DDP_FRONT_MAX_ATOM 2048
+#define DDP_FRONT_MAX_BONDS 256
+typedef struct {
+  int32_t* rowptr;
+  int32_t* perm;
+  int32_t* key;
+  int32_t* out0;
+  int32_t* out1;
+} ddp_front_view_t;
+typedef struct {
+  int32_t n_graphs;
+  int32_t n_lig, n_rec, n_atom, n_tor;                      /* node totals */
+  int32_t max_lig, max_rec, max_atom, max_tor, max_bonds;   /* largest per-graph sizes */
+  const float* lig_pos;
+  const float* rec_pos;
+  const float* atom_pos;
+  const float* tor_pos;
+  const int32_t* lig_ptr;                                   /* [n_graphs + 1] each */
+  const int32_t* rec_ptr;
+  const int32_t* atom_ptr;
+  const int32_t* tor_ptr;
+  float r_lig;                                              /* ligand-ligand, ligand-atom and bond-centre radius */
+  float r_cross;
+  const float* cross_div;
+  int32_t ll_neighbors, tor_neighbors, cross_neighbors, la_neighbors;
+  int32_t radius_flags;
+  int32_t e_bond;
+  int32_t* ll0;
+  int32_t* ll1;
+  int32_t cap_ll;
+  int32_t* cnt_ll;
+  int32_t* lr0;
+  int32_t* lr1;
+  int32_t cap_lr;
+  int32_t* cnt_lr;
+  int32_t* la0;
+  int32_t* la1;
+  int32_t cap_la;
+  int32_t* cnt_la;
+  int32_t* overflow;                                        /* optional, of the ligand x atom list */
+  int32_t* tor_q;
+  int32_t* tor_x;
+  int32_t cap_tor;
+  int32_t* cnt_tor;
+  int32_t* touched;
+  int32_t* near_rows;
+  int32_t* cnt_near;
+  int32_t* rp_lr;
+  int32_t* rp_la;
+  int32_t* rp_tor;
+  ddp_front_view_t c_ll, c_la, c_lr;
+  ddp_front_view_t so_ll, so_la, so_lr;
+  int32_t* scratch;
+} ddp_front_lists_t;
+int ddp_front_lists(const ddp_front_lists_t* a, int32_t* taken, void* stream);
+
 /* ---- node encoders + sigma-dependent columns of the edge-embedding MLPs (csrc/ddp_node.hip), one launch for all jobs.
  * A job is a gathered-row Linear over n_rows nodes:
  *   out[n, :ncols] = (emb_mode == 2 ? emb_sum(n) : 0) + bias + [ emb_sum(n) | dense[0](n) | dense[1](n) | sigma_emb(n) ] @ w
